@@ -4,6 +4,8 @@ point-clouds/sec fwd+bwd, KITTI car voxel grid, batch=2 per GPU).
 
     python bench.py --gpus 1 --steps K --warmup W                      (default workload: BASELINE configs[1])
     python bench.py --config ped | dense                               (BASELINE configs[2] / configs[4])
+    python bench.py --full ...                                         (every extra measurement and check below)
+    python bench.py --dump-outputs DIR ...                             (the last timed step's outputs as DIR/<name>.npy)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One step = the reference's train step (train.py:148-155) on one batch of synthetic KITTI-shaped frames whose raw (N,4)
@@ -16,11 +18,19 @@ SURVEY.md 8a-a8 — so the backward starts from a fixed seeded upstream gradient
 
 Targets: by default every timed step generates the RPN targets from the frames' label lines ON THE DEVICE inside the step
 (model.py:309 is part of RPN3D.forward in the reference too); --precomputed-targets takes seeded target maps instead (the
-round-1/2 behaviour; the default run also reports that rate as `value_precomputed_targets`).
-The timed region of `--steps` steps is the headline (`value`); it is repeated `--windows` - 1 more times in the same run and
-`value_min / value_median / value_max` give the spread over all windows (box-to-box variance on this pool is larger).
+round-1/2 behaviour; a --full run also reports that rate as `value_precomputed_targets`).
+The timed region of `--steps` steps is the headline (`value`, `ms_per_step`).  A plain run does only that: set-up, `--warmup`
+steps, the timed steps, the outputs (--dump-outputs) and the result line.  Everything else is measured with --full only:
+the timed region repeated `--windows` - 1 more times (`value_min / value_median / value_max`: the spread over all windows),
+the precomputed-targets window, the un-throttled host cost of a step, the exposed all-reduce time, the per-kernel figures
+and the roofline below, the fp32 / fp32x3 parity-mode runs, the N > 1 cross-rank checksums and the CPU baseline.
 
-Rank 0 prints ONE JSON line.
+--dump-outputs DIR writes what the timed path computed in its last timed step, as float32 (float64 for integer counters):
+the values the step returns (prob, reg and, with the loss, loss / cls_loss / reg_loss / cls_pos_loss / cls_neg_loss) and
+the model state it leaves (param.<state_dict key>: the updated parameters and the BatchNorm running statistics).  Inputs
+and initial weights are seeded, so two builds can be compared output for output; rank 0 writes.
+
+Rank 0 prints ONE JSON line.  With --full it also carries:
   roofline      the dominant kernel family — the implicit-GEMM convolutions (k_conv_patch + k_gather_gemm: forward and data
                 gradient of every layer) — measured live: HIP events around every launch ON THE STREAM IT IS LAUNCHED ON,
                 inside the same native executor path the timed region runs (vn_net_timing_begin/_read), in
@@ -59,6 +69,9 @@ CONFIGS = {
     "ped": (2, 3, "Pedestrian", 45, 2, "KITTI pedestrian/cyclist config (grid 10x200x240, T=45)"),
     "dense": (4, 5, "Car", 64, 4, "dense synthetic scene (~300k pts/frame, 40k voxels, T=64, car grid)"),
 }
+# what one train step returns (RPN3D.forward's tuple, model.py:362); without the loss (ped) only the first two
+OUTPUT_NAMES = ("prob", "reg", "loss", "cls_loss", "reg_loss", "cls_pos_loss", "cls_neg_loss")
+DUMP_LIMIT_BYTES = 64_000_000
 KIND_NAMES = ["conv_fwd", "conv_dgrad", "wgrad", "bn_apply", "bn_bwd_reduce", "bn_bwd_apply", "bn_finalize", "unpack_wgrads",
               "pack_weights", "first_layer_sparse", "misc"]
 
@@ -70,6 +83,22 @@ def synthetic_targets(B, h, w, seed, device):
     neg = ((rng.random((B, h, w, 2)) < 0.98) & (pos == 0)).astype(np.float32)
     tgt = (rng.standard_normal((B, h, w, 14)) * 0.1).astype(np.float32)
     return tuple(torch.from_numpy(a).to(device) for a in (pos, neg, tgt))
+
+
+def dump_outputs(out_dir, outputs, model):
+    """--dump-outputs: the step's returned tensors and the model state it left, one DIR/<name>.npy each (float32; float64
+    for float64 and integer tensors).  Beyond DUMP_LIMIT_BYTES in all (large --batch), every array is cut to the same
+    fixed, seeded sample of its flattened elements."""
+    tensors = dict(zip(OUTPUT_NAMES, outputs))
+    tensors.update(("param." + k, v) for k, v in model.state_dict().items())
+    arrays = {n: t.detach().to("cpu", torch.float32 if t.is_floating_point() and t.dtype != torch.float64 else torch.float64).numpy()
+              for n, t in tensors.items()}
+    keep = min(1.0, 0.95 * DUMP_LIMIT_BYTES / sum(a.nbytes for a in arrays.values()))
+    os.makedirs(out_dir, exist_ok=True)
+    for i, (n, a) in enumerate(arrays.items()):
+        if keep < 1.0 and a.size > 1:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(i).choice(a.size, max(1, int(a.size * keep)), replace=False))]
+        np.save(os.path.join(out_dir, n + ".npy"), a)
 
 
 def cpu_model_string():
@@ -171,10 +200,16 @@ def main():
                     help="diagnostic: voxelize once, outside the timed steps (NOT the benchmark configuration)")
     ap.add_argument("--precomputed-targets", action="store_true",
                     help="seeded target maps instead of generating the RPN targets from label lines inside every step")
-    ap.add_argument("--windows", type=int, default=5, help="timed windows of --steps steps each (the first is the headline)")
+    ap.add_argument("--windows", type=int, default=None,
+                    help="timed windows of --steps steps each (the first is the headline; default: 5 with --full, else 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every extra measurement and check (see the module docstring); default: the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy")
     ap.add_argument("--direct-rccl", action="store_true",
                     help="N > 1: all-reduce through the library's own RCCL wrapper (vn_allreduce_bucket) instead of torch.distributed")
     args = ap.parse_args()
+    if args.windows is None:
+        args.windows = 5 if args.full else 1
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -321,9 +356,11 @@ def main():
             else:
                 out = m((None, None, feats, None, coords, None, None), dev, targets=targets)
             out[2].backward()                                              # train.py:151
+            state["last"] = out
             return out[2]
         prob, reg = m.detect(feats, coords)
         torch.autograd.backward([prob, reg], list(upstream))
+        state["last"] = (prob, reg)
         return prob.flatten()[0]
 
     gap_events = [] if os.environ.get("VN_BENCH_GAPS") else None   # diagnostic: idle time of the training stream between steps
@@ -346,6 +383,7 @@ def main():
             m = state["model"]
             out = m.train_step((None, labels if mode["gen"] else None, feats, None, coords, None, None), dev, state["opt"],
                                targets=None if mode["gen"] else targets)
+            state["last"] = out
             loss = out[2]
         else:
             loss = fwd_bwd(feats, coords)
@@ -409,6 +447,8 @@ def main():
         print("VN_BENCH_GAPS: training-stream time between the last launch of a step and the first of the next: median %.1f us, "
               "p90 %.1f, max %.1f; first-to-last launch of a step: median %.1f us"
               % (gaps[len(gaps) // 2], gaps[int(len(gaps) * 0.9)], gaps[-1], inside[len(inside) // 2]), file=sys.stderr)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, state["last"], model)
     # ---- the spread: the same timed region again, --windows - 1 times (every rank: a step holds the collectives)
     window_dts = [dt]
     for _ in range(max(0, args.windows - 1)):
@@ -419,7 +459,7 @@ def main():
         sync_all()
         window_dts.append(time.perf_counter() - tw)
     dt_pre = None
-    if gen_targets:                      # the same window with precomputed target maps (what rounds 1-2 timed)
+    if gen_targets and args.full:        # the same window with precomputed target maps (what rounds 1-2 timed)
         mode["gen"] = False
         for _ in range(2):
             step_eager()
@@ -450,6 +490,7 @@ def main():
         dt = float(t[0].item())
         dt_pre = float(t[1].item()) if dt_pre is not None else None
         window_dts = [float(v) for v in t[2:].tolist()]
+    if world > 1 and args.full:
         # self-check of the data-parallel path (outside the timed region): every rank started from rank 0's weights
         # and applied the same averaged gradients, so the parameters must still be bit-identical on all ranks ...
         with torch.no_grad():
@@ -470,27 +511,29 @@ def main():
     # ---- host cost of one step, un-throttled: the enqueue of ONE step into an EMPTY queue (the timed loop's enqueue time is
     #      paced by the GPU: the host runs into the queue's back-pressure), median of 7
     #      (every rank runs them: a step holds the gradient collectives)
-    samples = []
-    for _ in range(7):
+    host_free = None
+    if args.full:
+        samples = []
+        for _ in range(7):
+            torch.cuda.synchronize()
+            th = time.perf_counter()
+            step_eager()
+            samples.append(time.perf_counter() - th)
         torch.cuda.synchronize()
-        th = time.perf_counter()
-        step_eager()
-        samples.append(time.perf_counter() - th)
-    torch.cuda.synchronize()
-    host_free = 1e3 * sorted(samples)[len(samples) // 2]
-    if world > 1:           # the line carries the SLOWEST rank's host cost (and the fastest beside it)
-        hf_ = torch.tensor([host_free], dtype=torch.float64, device=dev)
-        hlo, hhi = hf_.clone(), hf_.clone()
-        dist.all_reduce(hlo, op=dist.ReduceOp.MIN)
-        dist.all_reduce(hhi, op=dist.ReduceOp.MAX)
-        per_rank["host_enqueue_ms_per_step_min"], per_rank["host_enqueue_ms_per_step_max"] = float(hlo.item()), float(hhi.item())
-        host_free = float(hhi.item())
-    sync_all()
+        host_free = 1e3 * sorted(samples)[len(samples) // 2]
+        if world > 1:           # the line carries the SLOWEST rank's host cost (and the fastest beside it)
+            hf_ = torch.tensor([host_free], dtype=torch.float64, device=dev)
+            hlo, hhi = hf_.clone(), hf_.clone()
+            dist.all_reduce(hlo, op=dist.ReduceOp.MIN)
+            dist.all_reduce(hhi, op=dist.ReduceOp.MAX)
+            per_rank["host_enqueue_ms_per_step_min"], per_rank["host_enqueue_ms_per_step_max"] = float(hlo.item()), float(hhi.item())
+            host_free = float(hhi.item())
+        sync_all()
 
     # ---- N > 1: how long the main stream waits for the gradient exchange at the end of a step (the part of the bucketed
     #      all-reduce that the backward did not hide), HIP events around GradAllReducer.finish on the training stream
     exposed_ms = None
-    if model.grad_reducer is not None:
+    if model.grad_reducer is not None and args.full:
         state["exposed"] = []
         for _ in range(10):
             step_eager()
@@ -507,7 +550,7 @@ def main():
     #      torch events around the launch groups the Python side issues (voxelizer, VFE, loss, optimizer)
     recs, sect = None, None
     native_timed = bool(model.native_executor)
-    if not args.no_kernel_timer and (rank == 0 or world > 1):
+    if args.full and not args.no_kernel_timer and (rank == 0 or world > 1):
         sect = E.KernelTimer()
         E.SECTIONS = sect
         recs = []
@@ -527,7 +570,7 @@ def main():
     # ---- the same step in the fp32 parity mode (the mode the <= 1e-3 parity tests run in) and in bf16x3, a few steps each,
     #      and how far the three modes' RPN maps are apart on this batch (same weights: the seed of build_model)
     parity = None
-    if rank == 0 and world == 1 and args.precision == "bf16" and not args.no_parity_mode:
+    if args.full and rank == 0 and world == 1 and args.precision == "bf16" and not args.no_parity_mode:
         feats0, coords0 = voxelize_batch()
         maps = {}
 
@@ -596,11 +639,13 @@ def main():
                                                               and model._step_fused_ok(args.precision, opt)) else "")},
             # un-throttled: one step enqueued into an empty queue (what the host needs); in_loop: the timed loop's enqueue
             # time, which the GPU paces through queue back-pressure
-            "host_enqueue_ms_per_step": host_free, "host_enqueue_in_loop_ms_per_step": 1e3 * t_enq / args.steps,
+            "host_enqueue_in_loop_ms_per_step": 1e3 * t_enq / args.steps,
             # dense-equivalent model FLOPs (the first Conv3d's skipped zeros NOT subtracted) over the whole step
             "model_flops_fraction_of_peak": value / world * FLOP_PER_PC[args.config] / (peak * 1e12),
         }
         res["library"] = _lib.load().vn_build_info().decode()       # build + every VN_* tuning override in effect
+        if host_free is not None:
+            res["host_enqueue_ms_per_step"] = host_free
         if per_rank is not None:
             per_rank["cpu_affinity_rank0"] = affinity if affinity is None else "%d cores: %d-%d" % (len(affinity), affinity[0], affinity[-1])
             res["per_rank"] = per_rank          # host_enqueue_ms_per_step above is the MAX over ranks
@@ -709,7 +754,7 @@ def main():
                                        for k, v in kern.items() if "achieved_gbs" in v and "achieved_tflops" not in v]
         if parity is not None:
             res["parity_mode"] = parity
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 ncpu = len(os.sched_getaffinity(0))
             except AttributeError:

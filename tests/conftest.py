@@ -52,12 +52,13 @@ def pytest_sessionstart(session):
                                           stdout=log, stderr=subprocess.STDOUT, env=env, cwd=ROOT))
         DDP_REHEARSAL.update(procs=procs, dir=d)
         # tests/test_gpu_bench_contract.py: bench.py's N = 1 path with the reducer attached, 2 steps, as its own process
-        # (started here for the same reason as the ranks above)
+        # (started here for the same reason as the ranks above); --full: the contract covers the extra measurements too
         blog = open(os.path.join(d, "bench.err"), "w")
         bout = open(os.path.join(d, "bench.json"), "w")
         BENCH_RUN.update(dir=d, proc=subprocess.Popen(
-            [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--windows", "1", "--timer-steps", "1",
-             "--force-reducer", "--no-parity-mode"], stdout=bout, stderr=blog, env=env, cwd=ROOT))
+            [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--windows", "1",
+             "--timer-steps", "1", "--force-reducer", "--no-parity-mode", "--dump-outputs", os.path.join(d, "outputs")],
+            stdout=bout, stderr=blog, env=env, cwd=ROOT))
     except Exception as e:  # noqa: BLE001 - reported by the test
         DDP_REHEARSAL["error"] = repr(e)
 

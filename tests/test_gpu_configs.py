@@ -27,6 +27,14 @@ def rel_err(a, b):
     return float((a - b).abs().max() / b.abs().max().clamp(min=1e-12))
 
 
+def state_dict_f64(cls):
+    """tr.make_state_dict in float64: the full-size comparisons below run the oracle in float64.  Its float32 run is no
+    reference at the 1e-3 bar there: on these frames it lies 1.4e-3 - 2.4e-2 off the float64 maps (and up to 0.28
+    relative L2 off the first layers' gradients), and how far depends on the host's thread count (its BatchNorm and
+    convolution sums are split by thread)."""
+    return {k: (v.double() if v.is_floating_point() else v) for k, v in tr.make_state_dict(cls).items()}
+
+
 def voxelize_frames(frames, grid):
     from voxelnet_amd.voxelize import voxelize_device
     feats, coords = [], []
@@ -113,8 +121,8 @@ def test_ped_full_size_fp32_maps_and_bf16_step():
 def test_car_full_size_batch2_fp32_maps():
     """BASELINE configs[1] — the shape the metric is quoted on: car grid 10 x 400 x 352, T = 35, BATCH 2 (train-mode
     BatchNorm statistics over both frames; the full-size car tests of test_gpu_model.py are batch 1): RPN maps of the fp32
-    parity mode vs the reference op sequence (model.py:91-108, 257-281) on this box's CPU, same voxel buffers,
-    <= 1e-3 of the map maximum (BASELINE.json north_star); the benchmarked bf16 mode's distance is reported."""
+    parity mode vs the reference op sequence (model.py:91-108, 257-281) in float64 on the host CPU (state_dict_f64), same
+    voxel buffers, <= 1e-3 of the map maximum (BASELINE.json north_star); the benchmarked bf16 mode's distance is reported."""
     from voxelnet_amd import model as M
     from voxelnet_amd import synth
     from voxelnet_amd.config import grid_config
@@ -123,9 +131,9 @@ def test_car_full_size_batch2_fp32_maps():
     frames = synth.workload_frames(2, batch=2)                    # bench.py's frames: workload 2 = BASELINE configs[1] (bench.py CONFIGS["car"])
     feats, coords = voxelize_frames(frames, grid)
     assert len(feats) == 2 and feats[0].shape[1:] == (35, 7)
-    sd = tr.make_state_dict("Car")
+    sd = state_dict_f64("Car")
     with torch.no_grad():
-        dense = tr.feature_net([f.cpu() for f in feats], [c.cpu() for c in coords], dict(sd), grid.dims, True)
+        dense = tr.feature_net([f.cpu().double() for f in feats], [c.cpu() for c in coords], dict(sd), grid.dims, True)
         rp, rr = tr.middle_rpn(dense, dict(sd), "Car", True)
     assert rp.shape == (2, 2, 200, 176) and rr.shape == (2, 14, 200, 176)
     try:
@@ -294,8 +302,8 @@ def test_dense_config_fp32_step_vs_oracle():      # (and fp32x3, since round 5)
     mode against the CPU oracle: at this voxel count the native executor leaves the sparse routes of the first layer's
     boundary (the active-site list would cover every site: csrc/runtime.hip make_plan, `acap * 10 <= M * 3`) and runs
     middle_layer.1's data / weight gradient and middle_layer.0's BatchNorm backward DENSE — the route the car / ped
-    fixtures never take.  Maps <= 1e-3 (BASELINE.json); gradients: relative L2 <= 0.1 like test_car_full_backward (the
-    reference's own fp32-vs-fp64 band), the first layers and the VFE — everything downstream of that boundary — printed."""
+    fixtures never take.  Oracle in float64 (state_dict_f64).  Maps <= 1e-3 (BASELINE.json); gradients: relative L2 <= 0.1
+    like test_car_full_backward, the first layers and the VFE — everything downstream of that boundary — printed."""
     from voxelnet_amd import model as M
     from voxelnet_amd import synth
     from voxelnet_amd.config import grid_config
@@ -308,8 +316,8 @@ def test_dense_config_fp32_step_vs_oracle():      # (and fp32x3, since round 5)
     rng = np.random.default_rng(78)
     dp = torch.from_numpy((rng.standard_normal((1, 2, 200, 176)) * 1e-2).astype(np.float32))
     dr = torch.from_numpy((rng.standard_normal((1, 14, 200, 176)) * 1e-2).astype(np.float32))
-    rp, rr, ref = tr.forward_backward([f.cpu() for f in feats], [c.cpu() for c in coords], tr.make_state_dict("Car"),
-                                      (10, 400, 352), "Car", dp, dr)
+    rp, rr, ref = tr.forward_backward([f.cpu().double() for f in feats], [c.cpu() for c in coords], state_dict_f64("Car"),
+                                      (10, 400, 352), "Car", dp.double(), dr.double())
     # both fp32-grade modes against the one oracle run: the exact fp32 mode and fp32x3 (round 5: the dense route of the
     # first layers on split storage, the Conv3d weight gradients forked in front of their data gradients)
     try:

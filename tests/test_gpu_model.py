@@ -187,13 +187,14 @@ def test_rpn3d_forward_loss(golden):
 
 
 def test_car_full_backward():
-    """Full-size car frame (B=1), fp32 mode: maps AND all 104 parameter gradients against the oracle run on
-    this box's CPU cores (fp32, same inputs).  Bar for the maps: 1e-3 (BASELINE.json).  Bar for the chained
-    gradients: relative L2 <= 0.1 — the reference's own gradients are not defined more tightly than that:
-    its fp32 and fp64 runs (same torch ops, this frame) differ by 1.5e-3 / 1.1e-3 on the prob / reg maps and by
-    0.08-0.22 relative L2 on the gradients upstream of the heads (the first Conv3d's BatchNorm normalises
-    channels that are constant on 99 % of the sites, which amplifies fp32 rounding; DESIGN.md "Parity").
-    Measured here: <= 0.06.  Tight gradient parity is asserted per layer in test_gpu_layers.py."""
+    """Full-size car frame (B=1), fp32 mode: maps AND all 104 parameter gradients against the oracle run in float64 on
+    the host CPU (same inputs).  Bar for the maps: 1e-3 (BASELINE.json).  Bar for the chained gradients: relative
+    L2 <= 0.1 — fp32 gradients are not defined more tightly than that: the oracle's own fp32 and fp64 runs (same torch
+    ops, this frame) differ by 1.5e-3 / 1.1e-3 on the prob / reg maps and by up to 0.28 relative L2 on the gradients
+    upstream of the heads, by an amount that depends on the host's thread count (the first Conv3d's BatchNorm normalises
+    channels that are constant on 99 % of the sites, which amplifies fp32 rounding; DESIGN.md "Parity") — so the
+    reference is the float64 run.  Measured: maps 1.1e-5, gradients <= 0.035.  Tight gradient parity is asserted per
+    layer in test_gpu_layers.py."""
     from oracle import voxelize as ov
     from voxelnet_amd import synth
     w = synth.WORKLOADS[1]
@@ -204,7 +205,8 @@ def test_car_full_backward():
     rng = np.random.default_rng(77)
     dp = torch.from_numpy((rng.standard_normal((1, 2, 200, 176)) * 1e-2).astype(np.float32))
     dr = torch.from_numpy((rng.standard_normal((1, 14, 200, 176)) * 1e-2).astype(np.float32))
-    rp, rr, ref = tr.forward_backward(feats, coords, tr.make_state_dict("Car"), (10, 400, 352), "Car", dp, dr)
+    sd64 = {k: (v.double() if v.is_floating_point() else v) for k, v in tr.make_state_dict("Car").items()}
+    rp, rr, ref = tr.forward_backward([f.double() for f in feats], coords, sd64, (10, 400, 352), "Car", dp.double(), dr.double())
     m = make_model("Car", mode="fp32")
     m.train()
     prob, reg = m.detect([feats[0].to(DEV)], [coords[0].to(DEV)])
