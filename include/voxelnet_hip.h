@@ -420,6 +420,27 @@ typedef struct {
     float *weight, *bias, *gamma, *beta;   /* overwritten */
 } vnLayerGrads;
 size_t vn_net_workspace_bytes(const vnNetConfig *cfg, int64_t K);
+/* Read-only plan query (tests and diagnostics): where vn_net_forward leaves a layer's tensors in the workspace.  Runs the
+ * same deterministic walk as vn_net_workspace_bytes; launches nothing and touches no memory.  layer: 0..22 in execution
+ * order (as above); which: VN_NET_Y the conv output (pre-BatchNorm), VN_NET_A the activation, VN_NET_STATS the BatchNorm
+ * statistics.  out: byte offset from the workspace base, dtype (VN_F32, VN_BF16, or VN_F32X3S for split storage: fp32x3
+ * mode, layers >= 1 that are not transposed), B, D, H, W, C and element strides (the channel stride is 1).  Layouts:
+ *   a of deconv3 / deconv2 / deconv1 is the channel slice at 0 / 256 / 512 of the 768-wide concatenation the heads read
+ *   (C = 256, sW = 768);  a of middle_layer.2 is the BEV fold (B,1,H,W,128) with channel d*64 + c;
+ *   y of middle_layer.0 with sparse_first holds values only where an occupied voxel is in reach (elsewhere it is the conv
+ *   bias in the network's function, but the training forward may leave those sites unwritten; its a is complete);
+ *   stats is a 4 x 256-float block whose first 4*C floats are [4][C] = mean | invstd | gamma*invstd | beta — the same
+ *   vector as engine.layer_forward's (reported as W = 4 rows of C, sW = C).
+ * VN_EINVAL for a null pointer, K < 0, layer or which out of range; VN_EUNSUPPORTED for a config vn_net_workspace_bytes
+ * refuses. */
+enum { VN_NET_Y = 0, VN_NET_A = 1, VN_NET_STATS = 2 };
+typedef struct {
+    int64_t offset;          /* bytes from the workspace base */
+    int32_t dtype;           /* vnDtype */
+    int32_t B, D, H, W, C;
+    int64_t sB, sD, sH, sW;  /* element strides (4-byte elements for VN_F32X3S, as its producers count them) */
+} vnNetTensorInfo;
+int vn_net_tensor_info(const vnNetConfig *cfg, int64_t K, int32_t layer, int32_t which, vnNetTensorInfo *out);
 /* Executor context: the HIP events of the two-stream schedule (fork / join ring, "parameter group final" events), created
  * on the current device.  Caller-owned (one per executor instance, e.g. one RPN3D module on one device) — the library
  * keeps no mutable state of its own.  Calls sharing a context must not overlap on the host. */

@@ -125,7 +125,7 @@ def test_ctypes_structures_match_the_header_layout(tmp_path):
     pairs = [("vnGrid", _lib.VnGrid), ("vnConv", _lib.VnConv), ("vnVfeWeights", _lib.VnVfeWeights), ("vnVfeGrads", _lib.VnVfeGrads),
              ("vnNetConfig", _lib.VnNetConfig), ("vnTimingRecord", _lib.VnTimingRecord), ("vnLayerParams", _lib.VnLayerParams),
              ("vnLayerGrads", _lib.VnLayerGrads), ("vnPackJob", _lib.VnPackJob), ("vnUnpackJob", _lib.VnUnpackJob),
-             ("vnParamChunk", _lib.VnParamChunk), ("vnStep", _lib.VnStep)]
+             ("vnParamChunk", _lib.VnParamChunk), ("vnStep", _lib.VnStep), ("vnNetTensorInfo", _lib.VnNetTensorInfo)]
     lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "voxelnet_hip.h"', 'int main(void) {']
     for cname, st in pairs:
         lines.append(f'  printf("{cname} %zu", sizeof({cname}));')
@@ -167,3 +167,99 @@ def test_profile_tools_delimit_steps_by_a_kernel_the_library_has():
         assert marks, f"tools/{t}: no step marker found"
         for m in marks:
             assert any(k.startswith(m) for k in kernels), f"tools/{t} delimits steps by {m}, which csrc/vfe.hip no longer has"
+
+
+# vn_net_tensor_info: the BASELINE plans the native-executor gradient tests read (tests/test_gpu_native_chain.py)
+NET_PLANS = {"car": (2, 10, 400, 352, 2, 12000), "ped": (2, 10, 200, 240, 1, 10000), "dense": (1, 10, 400, 352, 2, 40000)}
+
+
+def _tensor_info(lib, _lib, cfg, K, layer, which):
+    info = _lib.VnNetTensorInfo()
+    assert lib.vn_net_tensor_info(ctypes.byref(cfg), K, layer, which, ctypes.byref(info)) == 0, (layer, which)
+    return info
+
+
+@pytest.mark.parametrize("mode", [0, 1, 2])
+@pytest.mark.parametrize("plan", sorted(NET_PLANS))
+def test_net_tensor_info_describes_the_forward_arena(plan, mode):
+    """vn_net_tensor_info (host only: the plan walk of vn_net_workspace_bytes) for the training plans of the car, ped and
+    dense configs in every mode: every y / a / stats region lies inside the workspace, no two regions overlap except the
+    three deconv activations, which tile the 768-wide concatenation exactly (deconv3 | deconv2 | deconv1), the shapes follow
+    the layer table, `a` is split-stored (VN_F32X3S) exactly for the fp32x3 mode's layers >= 1 that are not transposed,
+    and the answer does not change between calls."""
+    from voxelnet_amd import _lib
+    from voxelnet_amd import net as N
+    lib = _lib.load()
+    B, D, H, W, stride, K = NET_PLANS[plan]
+    cfg = _lib.VnNetConfig(B, D, H, W, stride, mode, 1, 1, 0, 0, 0, 0)
+    ws = lib.vn_net_workspace_bytes(ctypes.byref(cfg), K)
+    assert ws > 0
+    table = N.layer_table(stride)
+    esz = 2 if mode == 0 else 4
+    adt = _lib.VN_BF16 if mode == 0 else _lib.VN_F32
+    regions = []          # (begin, end, what)
+    dims = (D, H, W)
+    cat = {}
+    for l, (name, spec) in enumerate(table):
+        if name in ("block2.0", "deconv1"):
+            dims = x1
+        if name in ("block3.0", "deconv2"):
+            dims = x2
+        if name == "block1.0":
+            dims = (1,) + dims[1:]
+        od = spec.out_dims(dims)
+        infos = [_tensor_info(lib, _lib, cfg, K, l, w) for w in (_lib.VN_NET_Y, _lib.VN_NET_A, _lib.VN_NET_STATS)]
+        again = [_tensor_info(lib, _lib, cfg, K, l, w) for w in (_lib.VN_NET_Y, _lib.VN_NET_A, _lib.VN_NET_STATS)]
+        for i0, i1 in zip(infos, again):
+            assert bytes(i0) == bytes(i1), name
+        y, a, st = infos
+        assert (y.B, y.D, y.H, y.W, y.C) == (B,) + od + (spec.cout,) and y.dtype == adt, name
+        assert (y.sW, y.sH, y.sD, y.sB) == (spec.cout, od[2] * spec.cout, od[1] * od[2] * spec.cout, od[0] * od[1] * od[2] * spec.cout)
+        split = mode == 2 and l >= 1 and not spec.transposed
+        assert a.dtype == (_lib.VN_F32X3S if split else adt), (name, a.dtype)
+        if name == "middle_layer.2":          # BEV fold: (B,1,H,W,128), channel d*64 + c
+            assert od[0] == 2 and (a.B, a.D, a.H, a.W, a.C, a.sW) == (B, 1, od[1], od[2], 128, 128), name
+        else:
+            assert (a.B, a.D, a.H, a.W, a.C) == (B,) + od + (spec.cout,), name
+            assert a.sW == (768 if spec.transposed else spec.cout), name
+        assert a.sH == a.W * a.sW and a.sD == a.H * a.sH and a.sB == a.D * a.sD, name
+        assert st.dtype == _lib.VN_F32 and (st.B, st.D, st.H, st.W, st.C, st.sW) == (1, 1, 1, 4, spec.cout, spec.cout), name
+        for what, r in (("y", y), ("stats", st)) + ((() if spec.transposed else (("a", a),))):
+            span = ((r.B - 1) * r.sB + (r.D - 1) * r.sD + (r.H - 1) * r.sH + (r.W - 1) * r.sW + r.C) * (2 if r.dtype == _lib.VN_BF16 else 4)
+            regions.append((r.offset, r.offset + span, f"{name}.{what}"))
+        if spec.transposed:
+            cat[name] = a
+        if not spec.transposed:
+            dims = od if name != "middle_layer.2" else (1,) + od[1:]
+        if name == "block1.4":
+            x1 = dims
+        if name == "block2.5":
+            x2 = dims
+    # the three deconv slices tile the concatenation: channels 0 / 256 / 512 of (B,1,hf,wf,768), nothing else in it
+    d3, d2, d1 = cat["deconv3"], cat["deconv2"], cat["deconv1"]
+    assert d2.offset - d3.offset == 256 * esz and d1.offset - d2.offset == 256 * esz
+    assert all((d.B, d.D, d.H, d.W, d.C, d.sW, d.dtype) == (d3.B, 1, d3.H, d3.W, 256, 768, adt) for d in (d1, d2))
+    regions.append((d3.offset, d3.offset + d3.B * d3.H * d3.W * 768 * esz, "concat"))
+    regions.sort()
+    assert regions[0][0] >= 0 and regions[-1][1] <= ws, (regions[0], regions[-1], ws)
+    for (b0, e0, n0), (b1, e1, n1) in zip(regions, regions[1:]):
+        assert e0 <= b1, (n0, n1)
+        assert b0 % 256 == 0, n0                          # (every region is an arena allocation, 256-byte aligned)
+
+
+def test_net_tensor_info_argument_checks():
+    from voxelnet_amd import _lib
+    lib = _lib.load()
+    cfg = _lib.VnNetConfig(2, 10, 400, 352, 2, 0, 1, 1, 0, 0, 0, 0)
+    info = _lib.VnNetTensorInfo()
+    q = lambda c, K, layer, which, out: lib.vn_net_tensor_info(c, K, layer, which, out)      # noqa: E731
+    assert q(ctypes.byref(cfg), 12000, 22, _lib.VN_NET_STATS, ctypes.byref(info)) == 0
+    assert q(None, 12000, 0, 0, ctypes.byref(info)) == -1
+    assert q(ctypes.byref(cfg), 12000, 0, 0, None) == -1
+    assert q(ctypes.byref(cfg), -1, 0, 0, ctypes.byref(info)) == -1
+    assert q(ctypes.byref(cfg), 12000, 23, 0, ctypes.byref(info)) == -1
+    assert q(ctypes.byref(cfg), 12000, -1, 0, ctypes.byref(info)) == -1
+    assert q(ctypes.byref(cfg), 12000, 0, 3, ctypes.byref(info)) == -1
+    bad = _lib.VnNetConfig(2, 10, 401, 352, 2, 0, 1, 1, 0, 0, 0, 0)         # H % 8 != 0: vn_net_workspace_bytes refuses it too
+    assert lib.vn_net_workspace_bytes(ctypes.byref(bad), 12000) == 0
+    assert q(ctypes.byref(bad), 12000, 0, 0, ctypes.byref(info)) == -2

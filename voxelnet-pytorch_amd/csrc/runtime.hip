@@ -63,8 +63,10 @@ void out_dims(const Spec &sp, const int in[3], int out[3]) {
 struct Arena {
     char *base;
     size_t off, cap;
+    size_t last;        // offset of the last region handed out (valid with a null base too: vn_net_tensor_info)
     void *take(size_t bytes) {
         void *r = base ? base + off : nullptr;
+        last = off;
         off += vn_align(bytes, 256);
         return r;
     }
@@ -83,6 +85,7 @@ struct Plan {
     float *slab[NL]; int64_t slab_rows[NL];
     double *fsums[NL];           // forward bn_stats sums (deconvs)
     float *stats[NL];
+    size_t y_off[NL], a_off[NL], stats_off[NL];   // byte offsets of y / a / stats into the arena (vn_net_tensor_info)
     // backward
     float *bslab[NL]; int64_t bslab_rows[NL];
     float *coef[NL];
@@ -193,7 +196,7 @@ bool make_plan(const vnNetConfig *c, int64_t K, char *base, Plan *P) {
     P->cdt = (gs & 1) ? VN_F32 : P->adt;
     P->exact_heads = f32 ? false : (gs & 8) != 0;
     const int B = c->B;
-    Arena A{base, 0, 0};
+    Arena A{base, 0, 0, 0};
     auto rows_new = [&](int dtype, const int d[3], int C, int64_t width = 0) {
         if (!width) width = C;
         void *p = A.take((size_t)B * d[0] * d[1] * d[2] * width * (dtype == VN_BF16 ? 2 : 4));
@@ -238,10 +241,13 @@ bool make_plan(const vnNetConfig *c, int64_t K, char *base, Plan *P) {
     // ---- concat buffer and activations
     const int fm[3] = {1, P->hf, P->wf};
     P->cat = rows_new(P->adt, fm, 768);
+    const size_t cat_off = A.last;
     for (int l = 0; l < NL; ++l) {
         const Spec &sp = P->spec[l];
         P->y[l] = rows_new(P->ydt, P->odims[l], sp.cout);
+        P->y_off[l] = A.last;
         P->stats[l] = (float *)A.take(4 * 256 * sizeof(float));
+        P->stats_off[l] = A.last;
         const int64_t M = P->y[l].M();
         P->slab_rows[l] = 0;
         P->slab[l] = nullptr;
@@ -256,14 +262,17 @@ bool make_plan(const vnNetConfig *c, int64_t K, char *base, Plan *P) {
         if (sp.transposed) {   // activation = channel slice of the concat: cat([d3,d2,d1]) (model.py:271-273)
             const int off = l == L_D3 ? 0 : (l == L_D2 ? 256 : 512);
             Rows r = P->cat;
-            r.ptr += (size_t)off * P->esz;
+            if (r.ptr) r.ptr += (size_t)off * P->esz;     // (null base: vn_net_workspace_bytes / vn_net_tensor_info)
             r.C = 256;
             P->a[l] = r;
+            P->a_off[l] = cat_off + (size_t)off * P->esz;
         } else if (l == L_M2) {   // BEV fold (model.py:262): stored channel d*64 + c
             const int bd[3] = {1, P->odims[l][1], P->odims[l][2]};
             P->a[l] = rows_new(P->adt, bd, 128);
+            P->a_off[l] = A.last;
         } else {
             P->a[l] = rows_new(P->adt, P->odims[l], sp.cout);
+            P->a_off[l] = A.last;
         }
         // fp32x3: the activations that only convolutions and weight gradients read are STORED split (VN_F32X3S: per 8
         // channels their hi bf16 parts, then their lo parts — same bytes as fp32), written that way by the BatchNorm apply:
@@ -619,6 +628,29 @@ extern "C" size_t vn_net_workspace_bytes(const vnNetConfig *cfg, int64_t K) {
     Plan P;
     if (K < 0 || !make_plan(cfg, K, nullptr, &P)) return 0;
     return P.bytes;
+}
+
+// where the forward leaves layer `layer`'s y / a / stats in the arena: the same walk as vn_net_workspace_bytes, with
+// offsets instead of pointers (nothing is launched, no memory is touched)
+extern "C" int vn_net_tensor_info(const vnNetConfig *cfg, int64_t K, int32_t layer, int32_t which, vnNetTensorInfo *out) {
+    VN_CHECK_ARG(cfg && out && K >= 0 && layer >= 0 && layer < NL && which >= VN_NET_Y && which <= VN_NET_STATS);
+    Plan P;
+    if (!make_plan(cfg, K, nullptr, &P)) return VN_EUNSUPPORTED;
+    memset(out, 0, sizeof(*out));
+    if (which == VN_NET_STATS) {   // [4][C] = mean | invstd | gamma*invstd | beta (the first 4 C floats of a 4 x 256 block)
+        const int C = P.spec[layer].cout;
+        out->offset = (int64_t)P.stats_off[layer];
+        out->dtype = VN_F32;
+        out->B = out->D = out->H = 1; out->W = 4; out->C = C;
+        out->sB = out->sD = out->sH = 4 * (int64_t)C; out->sW = C;
+        return VN_OK;
+    }
+    const Rows &r = which == VN_NET_Y ? P.y[layer] : P.a[layer];
+    out->offset = (int64_t)(which == VN_NET_Y ? P.y_off[layer] : P.a_off[layer]);
+    out->dtype = r.dtype;
+    out->B = r.B; out->D = r.D; out->H = r.H; out->W = r.W; out->C = r.C;
+    out->sB = r.sB; out->sD = r.sD; out->sH = r.sH; out->sW = r.sW;
+    return VN_OK;
 }
 
 // Everything of the forward that does not depend on the voxel features: weight packing (all layers, both

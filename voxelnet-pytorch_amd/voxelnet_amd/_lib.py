@@ -20,6 +20,7 @@ LIB_PATH = os.environ.get("VN_LIB_PATH") or os.path.join(_HERE, "lib", "libvoxel
 c_i32, c_i64, c_f32, c_vp, c_sz = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
 
 VN_F32, VN_BF16 = 0, 1
+VN_F32X3S = 3       # split fp32 storage (vnDtype)
 
 
 class VnGrid(ctypes.Structure):
@@ -46,6 +47,14 @@ class VnVfeGrads(ctypes.Structure):
 
 class VnNetConfig(ctypes.Structure):
     _fields_ = [(n, c_i32) for n in ("B", "D", "H", "W", "block1_stride", "mode", "training", "sparse_first", "prepared", "bucket_events", "defer_join", "grad_storage")]
+
+
+class VnNetTensorInfo(ctypes.Structure):   # vnNetTensorInfo (vn_net_tensor_info)
+    _fields_ = [("offset", c_i64), ("dtype", c_i32)] + [(n, c_i32) for n in ("B", "D", "H", "W", "C")] + \
+        [(n, c_i64) for n in ("sB", "sD", "sH", "sW")]
+
+
+VN_NET_Y, VN_NET_A, VN_NET_STATS = 0, 1, 2       # vn_net_tensor_info's `which`
 
 
 class VnTimingRecord(ctypes.Structure):
@@ -124,6 +133,7 @@ SIGNATURES = {
     "vn_scatter_dense_bwd": (c_i32, [c_vp, c_i32, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "vn_conv_gather_gemm": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, _P(VnConv), c_i32, c_vp, c_vp]),
     "vn_net_workspace_bytes": (c_sz, [_P(VnNetConfig), c_i64]),
+    "vn_net_tensor_info": (c_i32, [_P(VnNetConfig), c_i64, c_i32, c_i32, _P(VnNetTensorInfo)]),
     "vn_net_create": (c_i32, [_P(c_vp)]),
     "vn_net_destroy": (c_i32, [c_vp]),
     "vn_net_step": (c_i32, [c_vp, _P(VnNetConfig), _P(VnStep)]),
