@@ -247,6 +247,26 @@ def test_net_tensor_info_describes_the_forward_arena(plan, mode):
         assert b0 % 256 == 0, n0                          # (every region is an arena allocation, 256-byte aligned)
 
 
+@pytest.mark.parametrize("mode", [0, 1, 2])
+@pytest.mark.parametrize("plan", sorted(NET_PLANS))
+def test_net_tensor_info_eval_plan_is_the_training_plan(plan, mode):
+    """the eval-mode forward (cfg.training = 0: what RPN3D.detect runs after model.eval()) leaves every layer's y / a / stats
+    exactly where the training forward does, in the same dtype and shape, in a workspace of the same size: the layout the
+    test above checks is the one tests/test_gpu_eval.py reads after an eval forward"""
+    from voxelnet_amd import _lib
+    lib = _lib.load()
+    B, D, H, W, stride, K = NET_PLANS[plan]
+    train = _lib.VnNetConfig(B, D, H, W, stride, mode, 1, 1, 0, 0, 0, 0)
+    ev = _lib.VnNetConfig(B, D, H, W, stride, mode, 0, 1, 0, 0, 0, 0)
+    ws = lib.vn_net_workspace_bytes(ctypes.byref(train), K)
+    assert ws > 0 and lib.vn_net_workspace_bytes(ctypes.byref(ev), K) == ws
+    for layer in range(23):
+        for which in (_lib.VN_NET_Y, _lib.VN_NET_A, _lib.VN_NET_STATS):
+            t, e = _tensor_info(lib, _lib, train, K, layer, which), _tensor_info(lib, _lib, ev, K, layer, which)
+            assert bytes(e) == bytes(t), (plan, mode, layer, which)
+            assert bytes(_tensor_info(lib, _lib, ev, K, layer, which)) == bytes(e), (plan, mode, layer, which)
+
+
 def test_net_tensor_info_argument_checks():
     from voxelnet_amd import _lib
     lib = _lib.load()

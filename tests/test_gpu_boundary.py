@@ -182,7 +182,8 @@ def test_backward_through_eval_forward(golden, mode):
     assert float(m.middle_rpn.block1[1].conv.bias.grad.abs().max()) > 0
     print(f"eval-mode backward, {mode}: worst gradient rel-L2", worst)
     with torch.no_grad():                       # the inference call pattern (predict.py:58-60): native executor, unaffected
-        m.detect(feats, coords)
+        prob2, reg2 = m.detect(feats, coords)
+    assert rel(prob2, rp) < tol and rel(reg2, rr) < tol, (rel(prob2, rp), rel(reg2, rr))
     M.set_precision("bf16")
 
 

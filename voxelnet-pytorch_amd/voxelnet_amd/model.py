@@ -601,7 +601,7 @@ class _DetectorFn(torch.autograd.Function):
             vparams = [p.detach() for p in flat[:nv]]
         # the native executor's backward is the train-mode one: an eval-mode forward that will be differentiated goes through
         # the per-layer orchestration (eval-mode BatchNorm backward, engine.layer_backward)
-        native = rpn._native_ok(mode) and (bool(training) or not any(ctx.needs_input_grad))   # (needs_input_grad is all False under no_grad)
+        native = rpn._native_ok(mode) and (bool(training) or not any(ctx.needs_input_grad))   # (all False under no_grad: detect)
         if ctx.anchor and not native:
             raise _lib.VoxelnetHipError("internal: the one-tensor (anchor) call needs the native executor (RPN3D._native_ok)")
         if not native:          # (the per-launch Python orchestration works on name -> tensor dicts)
@@ -1097,6 +1097,10 @@ class RPN3D(nn.Module):
                 and self._all_need_grad(flat)):
             prob, reg = _DetectorFn.apply(feature, coord, bs, self, self.training, self._anchor(feature.device))
         else:
+            if not torch.is_grad_enabled():
+                # (an autograd Function's needs_input_grad follows requires_grad, not the grad mode: without this, an eval
+                # forward under no_grad — the validation / predict call — left the native executor for the per-layer path)
+                flat = [p.detach() for p in flat]
             prob, reg = _DetectorFn.apply(feature, coord, bs, self, self.training, *flat)
         self._tick()
         return prob, reg
