@@ -170,7 +170,8 @@ def test_profile_tools_delimit_steps_by_a_kernel_the_library_has():
 
 
 # vn_net_tensor_info: the BASELINE plans the native-executor gradient tests read (tests/test_gpu_native_chain.py)
-NET_PLANS = {"car": (2, 10, 400, 352, 2, 12000), "ped": (2, 10, 200, 240, 1, 10000), "dense": (1, 10, 400, 352, 2, 40000)}
+NET_PLANS = {"car": (2, 10, 400, 352, 2, 12000), "ped": (2, 10, 200, 240, 1, 10000), "dense": (1, 10, 400, 352, 2, 40000),
+             "dense4": (4, 10, 400, 352, 2, 160000)}
 
 
 def _tensor_info(lib, _lib, cfg, K, layer, which):
@@ -283,3 +284,60 @@ def test_net_tensor_info_argument_checks():
     bad = _lib.VnNetConfig(2, 10, 401, 352, 2, 0, 1, 1, 0, 0, 0, 0)         # H % 8 != 0: vn_net_workspace_bytes refuses it too
     assert lib.vn_net_workspace_bytes(ctypes.byref(bad), 12000) == 0
     assert q(ctypes.byref(bad), 12000, 0, 0, ctypes.byref(info)) == -2
+
+
+def _layer_inputs(B, D, H, W, stride):
+    """[(name, spec, input dims)] of the 23 layers as the executor runs them (the walk of test_net_tensor_info_...)"""
+    from voxelnet_amd import net as N
+    out, dims = [], (D, H, W)
+    for name, spec in N.layer_table(stride):
+        if name in ("block2.0", "deconv1"):
+            dims = x1
+        if name in ("block3.0", "deconv2"):
+            dims = x2
+        if name == "block1.0":
+            dims = (1,) + dims[1:]
+        out.append((name, spec, dims))
+        od = spec.out_dims(dims)
+        if not spec.transposed:
+            dims = od if name != "middle_layer.2" else (1,) + od[1:]
+        if name == "block1.4":
+            x1 = dims
+        if name == "block2.5":
+            x2 = dims
+    return out
+
+
+def _kind(spec):
+    return (spec.dim, spec.transposed, spec.cin, spec.cout, spec.k, spec.stride, spec.pad)
+
+
+# the benchmarked configs (bench.py --config car / ped / dense at their default batch): (B, D, H, W, block1 stride)
+BENCH_PLANS = {"car": (2, 10, 400, 352, 2), "ped": (2, 10, 200, 240, 1), "dense4": (4, 10, 400, 352, 2)}
+
+
+def test_every_production_plan_id_has_a_case():
+    """the (forward, data-gradient, weight-gradient) kernel ids the library picks (vn_conv_plan_id /
+    vn_conv_wgrad_plan_id, host only) for every layer of the three benchmarked configs are each covered by a row of
+    tests/test_gpu_bf16_parity.CASES for a layer of the same geometry and the same stage: retuning a tile so that a
+    benchmarked layer lands on a kernel no stage test compares with its float64 oracle fails here, on the CPU.
+    middle_layer.0 is exempt: its forward is the rulebook (test_gpu_bf16_parity.test_bf16_rulebook_first_layer), its
+    weight and data gradients run over the active-site list, checked through the executor
+    (test_gpu_native_chain.test_bf16_native_gradients_vs_exact_chain_on_the_native_forward, every config)."""
+    from test_gpu_bf16_parity import CASES, make_spec, plan_ids
+    from voxelnet_amd import _lib
+    covered = set()
+    for case in CASES:
+        spec = make_spec(case)
+        for stage, i in zip(("forward", "data gradient", "weight gradient"), case[10]):
+            covered.add((_kind(spec), stage, i))
+    missing = []
+    for plan, (B, D, H, W, stride) in sorted(BENCH_PLANS.items()):
+        for name, spec, dims in _layer_inputs(B, D, H, W, stride):
+            if name == "middle_layer.0":
+                continue
+            ids = plan_ids(_lib, spec, B, dims)
+            for stage, i in zip(("forward", "data gradient", "weight gradient"), ids):
+                if (_kind(spec), stage, i) not in covered:
+                    missing.append((plan, name, stage, i))
+    assert missing == [], f"production kernel ids without a test_gpu_bf16_parity.CASES row: {missing}"

@@ -154,6 +154,11 @@ CASES = [
     ("block3.0", "conv", 2, 128, 256, 3, (2, 2), (1, 1), (2, (100, 88)), (2, (100, 88)), (2, 1, 44)),
     ("block3.1", "conv", 2, 256, 256, 3, (1, 1), (1, 1), (2, (50, 44)), (2, (50, 44)), (123, 123, WG9)),
     ("deconv3", "deconv", 2, 256, 256, 4, (4, 4), (0, 0), (2, (50, 44)), (2, (50, 44)), (4, 2, 44)),
+    # the dense config's batch of 4 (bench.py --config dense) moves these three layers onto other tiles (ped B = 2 runs
+    # deconv2's and deconv3's forward on the same tile 1); test_abi.test_every_production_plan_id_has_a_case holds the list
+    ("deconv2-B4", "deconv", 2, 128, 256, 2, (2, 2), (0, 0), (4, (100, 88)), (4, (100, 88)), (1, 1, 44)),
+    ("block3.0-B4", "conv", 2, 128, 256, 3, (2, 2), (1, 1), (4, (100, 88)), (4, (100, 88)), (1, 1, 44)),
+    ("deconv3-B4", "deconv", 2, 256, 256, 4, (4, 4), (0, 0), (4, (50, 44)), (4, (50, 44)), (1, 1, 44)),
 ]
 
 

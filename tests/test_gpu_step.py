@@ -30,23 +30,28 @@ def _inputs(B=2):
     return batches
 
 
-def _model(mode, reducer):
+def _model(mode, reducer, cls="Car", grid=None):
     from voxelnet_amd import model as M
     from voxelnet_amd import parallel
     from voxelnet_amd.config import GRADIENT_CLIP, LR
     from voxelnet_amd.optim import ClipSGD
     M.set_precision(mode)
     torch.manual_seed(4321)
-    m = M.RPN3D("Car").to(DEV).train()
+    m = M.RPN3D(cls)
+    if grid is not None:
+        m.feature_net._grid = grid
+    m = m.to(DEV).train()
     if reducer:
         m.grad_reducer = parallel.GradAllReducer(list(m.named_parameters()))
     return m, ClipSGD(list(m.parameters()), LR, GRADIENT_CLIP)
 
 
-def _run(mode, reducer, fused, batches, given_targets=None):
-    m, opt = _model(mode, reducer)
+def _run(mode, reducer, fused, batches, given_targets=None, cls="Car", grid=None):
+    m, opt = _model(mode, reducer, cls, grid)
     outs = []
     for x in batches:
+        if isinstance(x, tuple) and len(x) == 2:         # (batch, its targets)
+            x, given_targets = x
         if fused:
             assert m._step_fused_ok(mode, opt)
             out = m.train_step(x, DEV, opt, targets=given_targets)
@@ -83,6 +88,55 @@ def test_one_call_step_is_bit_identical_to_the_separate_calls(mode, reducer):
         assert torch.equal(a[2][k], b[2][k]), (mode, k)
     assert int(a[2]["feature_net.vfe_1.bn.num_batches_tracked"]) == 3
     assert float(a[0][0][2]) != float(a[0][2][2])        # (the three steps saw different batches and moving weights)
+
+
+# the other two benchmarked steps (bench.py --config ped / dense at their default batch): (class, workload id, B, grid args)
+OTHER_CONFIGS = {"ped": ("Pedestrian", 3, 2, {}), "dense4": ("Car", 5, 4, {"T": 64})}
+
+
+@pytest.mark.parametrize("config", sorted(OTHER_CONFIGS))
+def test_one_call_step_is_bit_identical_on_the_other_benchmarked_configs(config):
+    """bf16, ped B = 2 (block1 at stride 1, 100 x 120 maps) and dense B = 4 (~160k voxels, T = 64: the dense first-layer
+    route, the batch-4 tiles), two steps with given targets: the one-call step (vn_net_step) is bit-identical to the separate
+    calls — so what test_gpu_train_layers.py and test_gpu_native_chain.py check on the separate-call route holds for
+    train_step too.  (bench.py's ped step has no loss — the reference's anchor grid does not fit that class — and starts
+    its backward from a seeded gradient; the given targets here run the one-call route on ped's shapes all the same.)"""
+    from voxelnet_amd import model as M
+    from voxelnet_amd import synth
+    from voxelnet_amd.config import grid_config
+    from voxelnet_amd.voxelize import voxelize_device
+    cls, wid, B, kw = OTHER_CONFIGS[config]
+    grid = grid_config(cls, **kw)
+    h, w = grid.H // grid.block1_stride, grid.W // grid.block1_stride
+    rng = np.random.default_rng(5150)
+    batches = []
+    for step in range(2):
+        feats, coords = [], []
+        for b, f in enumerate(synth.workload_frames(wid, batch=B, frame0=step * B)):
+            fb, cb, _ = voxelize_device(torch.from_numpy(f).to(DEV), grid, b, coord_cols=4)
+            feats.append(fb)
+            coords.append(cb)
+        pos = (rng.random((B, h, w, 2)) < 0.002).astype(np.float32)
+        neg = ((rng.random((B, h, w, 2)) < 0.98) & (pos == 0)).astype(np.float32)
+        tgt = (rng.standard_normal((B, h, w, 14)) * 0.1).astype(np.float32)
+        batches.append(((None, None, feats, None, coords, None, None), (pos, neg, tgt)))
+    try:
+        a = _run("bf16", False, False, batches, cls=cls, grid=grid)
+        b = _run("bf16", False, True, batches, cls=cls, grid=grid)
+    finally:
+        M.set_precision("bf16")
+    assert a[0][0][0].shape == (B, 2, h, w)
+    for step, (oa, ob) in enumerate(zip(a[0], b[0])):
+        for i, (ta, tb) in enumerate(zip(oa, ob)):
+            assert torch.isfinite(ta).all(), (config, "output", i, "of step", step)
+            assert torch.equal(ta, tb), (config, "output", i, "of step", step)
+    assert a[3] == b[3] and np.isfinite(a[3]) and a[3] > 0
+    assert a[1].keys() == b[1].keys() and all(torch.equal(a[1][k], b[1][k]) for k in a[1]), "last step's gradients"
+    assert a[2].keys() == b[2].keys()
+    for k in a[2]:
+        assert torch.equal(a[2][k], b[2][k]), (config, k)
+    assert int(a[2]["feature_net.vfe_1.bn.num_batches_tracked"]) == 2
+    assert float(a[0][0][2]) != float(a[0][1][2])
 
 
 def test_one_call_step_with_given_targets_and_without_optimizer():
