@@ -373,6 +373,36 @@ int vn_fov_crop(const float *points, int64_t n, const float *P_3x4, const float 
                 int32_t *out_index, int32_t *out_count, void *workspace, size_t workspace_bytes, vnStream stream);
 
 /* ------------------------------------------------------------------------
+ * Point-cloud augmentation — the per-point half of pcl_augmentation (voxelnet/dataset.py:122-219; the moves are
+ * point_transform, dataset.py:264): the stage between the field-of-view crop and the voxelizer (csrc/augment.hip).  The
+ * random draw, the collision test (calc_iou2d, :222-240) and the moved labels are O(boxes) host work
+ * (voxelnet_amd/augment.py).  points / out: (n,4) fp32 [x,y,z,reflectance], 16-byte aligned; out may BE points (in
+ * place) and must not overlap it otherwise.  Reflectance is copied.
+ *   rigid motion (translate, then the ROW vector times the z-rotation: a rotation by -rz about the lidar origin), in
+ *   float64 exactly as written, no contraction, rounded once to fp32:
+ *     X = x + tx, Y = y + ty, Z = z + tz;   x' = X*c + Y*s,   y' = -(X*s) + Y*c,   z' = Z
+ *   VN_AUGMENT_BOXES : boxes = DEVICE table of n_boxes <= VN_AUGMENT_MAX_BOXES entries (16-byte aligned).  A point
+ *                      walks the table in index order on its CURRENT value and is moved by every entry whose bounds
+ *                      hold it (lo <= p <= hi on the three axes, fp32, inclusive) — the reference's in-place loop.
+ *                      c, s, scale are ignored.  n_boxes == 0: a copy (nothing at all when out == points).
+ *   VN_AUGMENT_ROTATE: the motion with t = 0 and the HOST's c = cos(angle), s = sin(angle) for every point.
+ *   VN_AUGMENT_SCALE : x, y, z each multiplied by scale in fp32.
+ * A NaN point (the padding rows of vn_fov_crop) fails every bounds test and stays NaN in the other two modes.
+ * n == 0 is a no-op.  Asynchronous; no workspace.
+ * ---------------------------------------------------------------------- */
+#define VN_AUGMENT_MAX_BOXES 128
+#define VN_AUGMENT_BOXES 0
+#define VN_AUGMENT_ROTATE 1
+#define VN_AUGMENT_SCALE 2
+typedef struct vnAugmentBox {
+    float lo[3], hi[3];   /* x, y, z bounds of the UNMOVED box: axis-aligned hull of its eight corners */
+    double tx, ty, tz;    /* translation, applied first */
+    double c, s;          /* cos(rz), sin(rz) */
+} vnAugmentBox;           /* 64 bytes */
+int vn_augment_points(const float *points, int64_t n, int32_t mode, const vnAugmentBox *boxes, int32_t n_boxes, double c,
+                      double s, float scale, float *out, vnStream stream);
+
+/* ------------------------------------------------------------------------
  * Native step executor — MiddleConvNet.forward (model.py:257-281) and its backward as ONE call
  * each (csrc/runtime.hip): layer table, launch geometry and workspace arena live in C++, so the
  * ~450 launches of a step cost microseconds of host time instead of a Python round trip each.

@@ -98,6 +98,15 @@ class VnStep(ctypes.Structure):       # vnStep (vn_net_step): field for field
                 ("side_stream", c_vp)]
 
 
+class VnAugmentBox(ctypes.Structure):   # vnAugmentBox (vn_augment_points): one entry of the device box table, 64 bytes
+    _fields_ = [("lo", c_f32 * 3), ("hi", c_f32 * 3), ("tx", ctypes.c_double), ("ty", ctypes.c_double), ("tz", ctypes.c_double),
+                ("c", ctypes.c_double), ("s", ctypes.c_double)]
+
+
+VN_AUGMENT_BOXES, VN_AUGMENT_ROTATE, VN_AUGMENT_SCALE = 0, 1, 2       # vn_augment_points' `mode`
+VN_AUGMENT_MAX_BOXES = 128
+
+
 # name -> (restype, argtypes); mirrors include/voxelnet_hip.h one to one
 _P = ctypes.POINTER
 SIGNATURES = {
@@ -117,6 +126,7 @@ SIGNATURES = {
                                  c_sz, c_vp]),
     "vn_fov_crop_workspace_bytes": (c_sz, [c_i64]),
     "vn_fov_crop": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "vn_augment_points": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i32, ctypes.c_double, ctypes.c_double, c_f32, c_vp, c_vp]),
     "vn_comm_rccl_version": (c_i32, []),
     "vn_comm_unique_id": (c_i32, [c_vp]),
     "vn_comm_create": (c_i32, [_P(c_vp), c_vp, c_i32, c_i32]),

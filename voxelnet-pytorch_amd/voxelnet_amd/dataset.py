@@ -8,8 +8,13 @@
               no host synchronisation -> the reference's 7-tuple with the voxel buffers already in HBM.
 
 `DeviceBatcher` wraps any iterable of per-sample 5-tuples lists (a DataLoader with `collate_fn=list`) and keeps one
-batch in flight: batch i+1 is copied and voxelized while batch i trains.  Data augmentation (dataset.py:122-…,
-`pcl_augmentation`) is outside the hot path and not provided; pass `augment=False`."""
+batch in flight: batch i+1 is copied and voxelized while batch i trains.
+
+Data augmentation (dataset.py:122-219, `pcl_augmentation`: per-box perturbation, global rotation, global scaling) is a
+stage of this pipeline, not of the dataset: copy -> [field-of-view crop] -> augment -> voxelize.  `DeviceCollate(...,
+augment=True)` / `DeviceBatcher(..., augment=True)` draw the parameters per sample on the host (augment.py, after the
+sample's shuffle), move the points on the device (csrc/augment.hip) and hand the model the moved label lines.  The
+dataset itself runs in DataLoader workers, which must not touch the GPU: `KITTIDataset(augment=True)` still raises."""
 import glob
 import os
 
@@ -36,7 +41,8 @@ class KITTIDataset(torch.utils.data.Dataset):
 
     def __init__(self, data_dir, shuffle=True, augment=False, test=False, load_images=True):
         if augment:
-            raise NotImplementedError("pcl_augmentation (dataset.py:122) is outside the accelerated path; use augment=False")
+            raise NotImplementedError("pcl_augmentation (dataset.py:122) runs on the device, not in dataset workers: use "
+                                      "KITTIDataset(augment=False) with DeviceCollate / DeviceBatcher(..., augment=True)")
         self.data_dir, self.shuffle, self.test, self.load_images = data_dir, shuffle, test, load_images
         self.images = sorted(glob.glob(os.path.join(data_dir, "image_2") + "/*.png"))
         self.pcls = sorted(glob.glob(os.path.join(data_dir, "velodyne") + "/*.bin"))
@@ -64,8 +70,12 @@ class DeviceCollate:
     feature (K_i,T,7) f32, number (K_i,) i64, coordinate (K_i,4) i64 [b,z,y,x].  Must run in the process that owns the
     GPU (not in a DataLoader worker)."""
 
-    def __init__(self, device="cuda:0", target="Car", shuffle_points=True, fov_calib_dir=None, image_shape=(375, 1242)):
-        """fov_calib_dir: RAW sweeps — crop every cloud to the camera field of view on the device before it is voxelized
+    def __init__(self, device="cuda:0", target="Car", shuffle_points=True, fov_calib_dir=None, image_shape=(375, 1242),
+                 augment=False):
+        """augment: the reference's pcl_augmentation (dataset.py:122-219) per sample — drawn from np.random after the
+        sample's shuffle, applied to the (cropped) cloud on the device in front of the voxelizer; the batch's `label`
+        element then holds the MOVED label lines (augment.augment_labels), its raw-lidar element the host cloud as shuffled.
+        fov_calib_dir: RAW sweeps — crop every cloud to the camera field of view on the device before it is voxelized
         (the reference does this offline, preprocess_data.py:42-154, and trains on the rewritten .bin files):
         `<fov_calib_dir>/<tag>.txt` is the sample's KITTI object calibration file, the image size is the sample's image's
         (or image_shape when images are not loaded).  The crop keeps the input order, so shuffling the raw cloud first
@@ -76,16 +86,23 @@ class DeviceCollate:
         self.grid = grid_config("Car" if target == "Car" else "Pedestrian")    # utils.py:24-33 ('Car' else ped/cyc)
         self.shuffle_points = shuffle_points
         self.fov_calib_dir, self.image_shape = fov_calib_dir, tuple(image_shape)
+        self.augment = bool(augment)
         self.stream = pipeline_stream(self.device)      # (shared with the target generator: see voxelize.pipeline_stream)
 
     def launch(self, parts):
         """enqueue the copies and the voxelization of one batch on the pipeline's stream; returns a handle"""
         handles = []
+        if self.augment:
+            from . import augment as A
+            parts = list(parts)
         with torch.cuda.stream(self.stream):
             for b, p in enumerate(parts):
                 pcl = p[2]
                 if self.shuffle_points:
                     np.random.shuffle(pcl)                                     # utils.py:35, in place like the reference
+                if self.augment:
+                    params = A.draw_augmentation(p[3])                         # dataset.py:122-219, host: O(boxes)
+                    parts[b] = (p[0], p[1], p[2], A.augment_labels(p[3], params), *p[4:])
                 host = torch.from_numpy(np.ascontiguousarray(pcl[:, :4], dtype=np.float32)).pin_memory()
                 pts = host.to(self.device, non_blocking=True)
                 if self.fov_calib_dir is not None:
@@ -95,6 +112,11 @@ class DeviceCollate:
                     # padded form: no 4-byte read-back per sample (it would stall the host behind everything queued
                     # on this stream); the rows past the device-side count are NaN points, which the voxelizer drops
                     pts, _ = fov_crop_device(pts, P, Tr, R, rows, cols, padded=True)
+                if self.augment:
+                    # in place, behind the copy / the crop on this stream; `keep` = the staged box table, referenced
+                    # by the handle until the batch is consumed, like `host`
+                    pts, keep = A.enqueue_augment_points(pts, params, out=pts)
+                    host = (host, keep)
                 handles.append((voxelize_device_async(pts, self.grid, b, coord_cols=4), pts, host))
         return parts, handles
 
@@ -136,9 +158,10 @@ class DeviceBatcher:
     device-resident 7-tuples, one batch ahead: while the model trains on batch i, batch i+1 is being copied and
     voxelized on the pipeline's own stream."""
 
-    def __init__(self, loader, device="cuda:0", target="Car", shuffle_points=True, fov_calib_dir=None, image_shape=(375, 1242)):
+    def __init__(self, loader, device="cuda:0", target="Car", shuffle_points=True, fov_calib_dir=None, image_shape=(375, 1242),
+                 augment=False):
         self.loader = loader
-        self.collate = DeviceCollate(device, target, shuffle_points, fov_calib_dir, image_shape)
+        self.collate = DeviceCollate(device, target, shuffle_points, fov_calib_dir, image_shape, augment)
 
     def __len__(self):
         return len(self.loader)
