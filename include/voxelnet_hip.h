@@ -849,6 +849,45 @@ int vn_rpn_predict(const float *probs, const float *deltas, const double *anchor
                    float score_thres, double nms_thres, int32_t top_k, double anchor_h, float *boxes, float *scores,
                    int32_t *counts, void *workspace, size_t workspace_bytes, vnStream stream);
 
+/* ---- detection scoring (eval.py:4-5 is empty in the reference; protocol: DESIGN.md section 1b) --------------
+ * Box = (x, y, z, h, w, l, r), lidar frame: footprint corners (+-l/2, +-w/2) turned by r about (x, y), vertical
+ * extent [z, z+h].  All IoU arithmetic is float64 (csrc/eval.hip).
+ *   BEV intersection I: both footprints translated so that A's centre is the origin, A's rectangle clipped by the
+ *   four half-planes of B (Sutherland-Hodgman), shoelace area.
+ *   iou_bev = I / (wa*la + wb*lb - I);   iou_3d = I*zo / (ha*wa*la + hb*wb*lb - I*zo),
+ *   zo = max(0, min(za+ha, zb+hb) - max(za, zb)).  A pair scores 0, never NaN, when a field is not finite, when w, l
+ *   or h of either box is <= 0, or when the denominator is <= 0.
+ * vn_box_iou_rotated: a [na,7], b [nb,7] float64 (device) -> out [na,nb] float64; metric VN_EVAL_BEV / VN_EVAL_3D
+ * (VN_EINVAL otherwise); na == 0 or nb == 0 is a no-op.  One thread per pair, no workspace, asynchronous.
+ *
+ * vn_eval_match: per frame b, the greedy matching of vn_rpn_predict's outputs (det_boxes [B,top_k,7] and det_scores
+ * [B,top_k] float32, det_counts [B] read ON THE DEVICE) against gt [B,max_gt,7] float64 with gt_counts [B] (device)
+ * and gt_flags [B,n_diff,max_gt] (0 valid, anything else ignored), for both metrics and every one of the n_diff
+ * difficulties: detections by descending score (ties: lower index); a detection takes, among the ground truths not
+ * taken yet with IoU > thr, the valid one with the largest IoU (ties: lowest index), else the ignored one with the
+ * largest IoU; a taken ground truth, valid or ignored, is gone for the later detections.
+ *   status     [B,2,n_diff,top_k] int8 : 1 TP (took a valid one), 0 FP, -1 ignored (took an ignored one), -2 slot
+ *                                        beyond det_counts[b];  axis 1: VN_EVAL_BEV, VN_EVAL_3D
+ *   matched_gt [B,2,n_diff,top_k] int32: index of the taken ground truth, -1 none
+ *   iou_out    [B,2,top_k,max_gt] float64 or NULL: the frame's IoU tables (0 beyond the counts)
+ *   workspace  vn_eval_match_workspace_bytes(B, top_k, max_gt) bytes; afterwards its first B*top_k int32 hold the
+ *              order in which each frame's detections were walked (-1 beyond the count)
+ * One workgroup per frame, one launch, no host synchronisation.  Limits: 1 <= top_k <= VN_EVAL_MAX_TOPK, 1 <= max_gt
+ * <= VN_TARGETS_MAX_GT, 1 <= n_diff <= VN_EVAL_MAX_DIFF.  VN_EINVAL for a size outside them, a NaN threshold, a null
+ * pointer (iou_out excepted) or a workspace smaller than asked for; B == 0 is a no-op (0).  Counts outside
+ * [0, top_k] / [0, max_gt] are clamped on the device. */
+#define VN_EVAL_MAX_TOPK 32
+#define VN_EVAL_MAX_DIFF 8
+#define VN_EVAL_BEV 0
+#define VN_EVAL_3D 1
+int vn_box_iou_rotated(const double *a, int32_t na, const double *b, int32_t nb, int32_t metric, double *out,
+                       vnStream stream);
+size_t vn_eval_match_workspace_bytes(int32_t B, int32_t top_k, int32_t max_gt);
+int vn_eval_match(const float *det_boxes, const float *det_scores, const int32_t *det_counts, const double *gt,
+                  const int32_t *gt_counts, const uint8_t *gt_flags, int32_t B, int32_t top_k, int32_t max_gt,
+                  int32_t n_diff, double thr_bev, double thr_3d, int8_t *status, int32_t *matched_gt, double *iou_out,
+                  void *workspace, size_t workspace_bytes, vnStream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,264 @@
+"""Float64 NumPy / plain-Python restatement of the detection-scoring protocol — the reference
+tests/test_eval_host.py and tests/test_gpu_detection_eval.py hold voxelnet_amd/evaluate.py and csrc/eval.hip against, in
+the role tests/augment_ref.py plays for the augmentation.  It shares no code with evaluate.py for the IoU, the flags, the
+matching or the AP; only the label-line -> lidar-box conversion is the project's (targets.label_to_gt_box_3d).
+
+Box = (x, y, z, h, w, l, r), lidar frame: footprint corners (+-l/2, +-w/2) turned by r about (x, y); vertical extent
+[z, z + h]."""
+import math
+
+import numpy as np
+
+from voxelnet_amd.targets import CLASS_CFG, label_to_gt_box_3d
+
+DIFFS = ("all", "easy", "moderate", "hard")
+THRES = {"Car": 0.7, "Pedestrian": 0.5, "Cyclist": 0.5}
+
+
+# ---------------------------------------------------------------------------------------------------------- IoU
+def _corners(l, w, r, cx, cy):
+    c, s = math.cos(r), math.sin(r)
+    return [(sx * l / 2 * c - sy * w / 2 * s + cx, sx * l / 2 * s + sy * w / 2 * c + cy)
+            for sx, sy in ((1, 1), (-1, 1), (-1, -1), (1, -1))]          # counter-clockwise
+
+
+def _clip(poly, e0, e1):
+    """Sutherland-Hodgman: the part of `poly` on the left of the directed line e0 -> e1"""
+    dx, dy = e1[0] - e0[0], e1[1] - e0[1]
+    out = []
+    for i, cur in enumerate(poly):
+        prev = poly[i - 1]
+        dp = dx * (prev[1] - e0[1]) - dy * (prev[0] - e0[0])
+        dc = dx * (cur[1] - e0[1]) - dy * (cur[0] - e0[0])
+        if (dp >= 0) != (dc >= 0):
+            t = dp / (dp - dc)
+            out.append((prev[0] + (cur[0] - prev[0]) * t, prev[1] + (cur[1] - prev[1]) * t))
+        if dc >= 0:
+            out.append(cur)
+    return out
+
+
+def bev_intersection(a, b):
+    """area of the intersection of the two footprints; A's centre is the origin of the computation"""
+    pa = _corners(a[5], a[4], a[6], 0.0, 0.0)
+    pb = _corners(b[5], b[4], b[6], b[0] - a[0], b[1] - a[1])
+    poly = pa
+    for k in range(4):
+        poly = _clip(poly, pb[k], pb[(k + 1) % 4])
+        if not poly:
+            return 0.0
+    s = 0.0
+    for i, p in enumerate(poly):
+        q = poly[(i + 1) % len(poly)]
+        s += p[0] * q[1] - q[0] * p[1]
+    return 0.5 * abs(s)
+
+
+def iou_pair(a, b):
+    """-> (iou_bev, iou_3d) of two boxes; 0, never NaN, for a non-finite field, a non-positive w / l / h or a
+    denominator <= 0"""
+    a, b = [float(v) for v in a], [float(v) for v in b]
+    if not all(math.isfinite(v) for v in a + b) or min(a[3], a[4], a[5], b[3], b[4], b[5]) <= 0:
+        return 0.0, 0.0
+    inter = bev_intersection(a, b)
+    area_a, area_b = a[4] * a[5], b[4] * b[5]
+    den = area_a + area_b - inter
+    bev = inter / den if den > 0 else 0.0
+    zo = max(0.0, min(a[2] + a[3], b[2] + b[3]) - max(a[2], b[2]))
+    inter3 = inter * zo
+    den3 = a[3] * area_a + b[3] * area_b - inter3
+    return bev, (inter3 / den3 if den3 > 0 else 0.0)
+
+
+def iou_matrix(a, b, metric):
+    """a (na,7), b (nb,7) -> (na,nb) float64; metric 'bev' or '3d'"""
+    k = {"bev": 0, "3d": 1}[metric]
+    out = np.zeros((len(a), len(b)), dtype=np.float64)
+    for i in range(len(a)):
+        for j in range(len(b)):
+            out[i, j] = iou_pair(a[i], b[j])[k]
+    return out
+
+
+# ------------------------------------------------------------------------------------------ ground truths, flags
+_FILTER = {"easy": (40.0, 0, 0.15), "moderate": (25.0, 1, 0.30), "hard": (25.0, 2, 0.50)}
+
+
+def frame_ground_truth(lines, cls_name="Car", diffs=DIFFS):
+    """one frame's label lines -> (boxes (G,7) float64 lidar, flags (len(diffs),G) bool: True = IGNORED).  Lines of
+    cls_name are candidates (ignored where they fail the difficulty's filter), lines of another accepted class (Van for
+    Car) are ignored everywhere, the rest is dropped."""
+    boxes, flags = [], []
+    for line in lines:
+        f = line.split()
+        name = f[0]
+        if name == cls_name:
+            trunc, occ, height = float(f[1]), float(f[2]), float(f[7]) - float(f[5])
+            row = []
+            for d in diffs:
+                if d == "all":
+                    row.append(False)
+                else:
+                    hmin, omax, tmax = _FILTER[d]
+                    row.append(not (height >= hmin and occ <= omax and trunc <= tmax))
+        elif name in CLASS_CFG[cls_name]["accept"]:
+            row = [True] * len(diffs)
+        else:
+            continue
+        boxes.append(label_to_gt_box_3d([[line]], "", "lidar")[0][0])
+        flags.append(row)
+    return (np.array(boxes, dtype=np.float64).reshape(-1, 7),
+            np.array(flags, dtype=bool).reshape(-1, len(diffs)).T.copy())
+
+
+# ---------------------------------------------------------------------------------------------------- matching
+def match_frame(iou, scores, ignored, thr):
+    """iou (n_det, n_gt), scores (n_det,), ignored (n_gt,) bool -> (status (n_det,) 1 TP / 0 FP / -1 ignored,
+    matched (n_det,) ground-truth index or -1).  Plain loops."""
+    n_det, n_gt = iou.shape
+    order = sorted(range(n_det), key=lambda d: (-float(scores[d]), d))
+    taken = [False] * n_gt
+    status, matched = [0] * n_det, [-1] * n_det
+    for d in order:
+        best_valid, best_ign = -1, -1
+        for g in range(n_gt):
+            if taken[g] or not iou[d, g] > thr:
+                continue
+            if ignored[g]:
+                if best_ign < 0 or iou[d, g] > iou[d, best_ign]:
+                    best_ign = g
+            elif best_valid < 0 or iou[d, g] > iou[d, best_valid]:
+                best_valid = g
+        if best_valid >= 0:
+            status[d], matched[d], taken[best_valid] = 1, best_valid, True
+        elif best_ign >= 0:
+            status[d], matched[d], taken[best_ign] = -1, best_ign, True
+    return np.array(status, dtype=np.int64), np.array(matched, dtype=np.int64)
+
+
+def evaluate_frame(det_boxes, det_scores, lines, cls_name="Car", diffs=DIFFS, thr=None):
+    """-> dict: iou {'bev','3d'} (n_det,n_gt), status / matched {metric: (len(diffs), n_det)}, flags, boxes"""
+    thr = THRES[cls_name] if thr is None else thr
+    gt, flags = frame_ground_truth(lines, cls_name, diffs)
+    out = {"boxes": gt, "flags": flags, "iou": {}, "status": {}, "matched": {}}
+    det = np.asarray(det_boxes, dtype=np.float64).reshape(-1, 7)
+    both = np.zeros((2, len(det), len(gt)), dtype=np.float64)
+    for i in range(len(det)):
+        for j in range(len(gt)):
+            both[:, i, j] = iou_pair(det[i], gt[j])
+    for m, metric in enumerate(("bev", "3d")):
+        iou = both[m]
+        st = np.zeros((len(diffs), len(det_scores)), dtype=np.int64)
+        mg = np.zeros((len(diffs), len(det_scores)), dtype=np.int64)
+        for k in range(len(diffs)):
+            st[k], mg[k] = match_frame(iou, det_scores, flags[k], thr)
+        out["iou"][metric], out["status"][metric], out["matched"][metric] = iou, st, mg
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------- AP
+def average_precision(scores, status, n_valid_gt, recall_points=40):
+    """pooled (score, status) in (frame, index) order -> AP (R40: mean over r = 1/40..40/40; R11: r = 0, 0.1 .. 1 of the
+    largest precision at a recall >= r); NaN without a valid ground truth"""
+    if n_valid_gt == 0:
+        return float("nan")
+    pairs = [(float(s), int(t)) for s, t in zip(scores, status) if int(t) != -1]
+    pairs.sort(key=lambda p: -p[0])          # (stable)
+    tp = fp = 0
+    curve = []          # (recall, precision) after each detection
+    for _, t in pairs:
+        if t == 1:
+            tp += 1
+        else:
+            fp += 1
+        curve.append((tp / n_valid_gt, tp / (tp + fp)))
+    if recall_points == 40:
+        rs = [k / 40 for k in range(1, 41)]
+    else:
+        rs = [k / 10 for k in range(0, 11)]
+    total = 0.0
+    for r in rs:
+        total += max([p for rec, p in curve if rec >= r], default=0.0)
+    return total / len(rs)
+
+
+class RefEvaluator:
+    """frame-by-frame accumulation with the functions above"""
+
+    def __init__(self, cls_name="Car", diffs=DIFFS, thr=None, recall_points=40):
+        self.cls_name, self.diffs, self.thr, self.recall_points = cls_name, tuple(diffs), thr, recall_points
+        self.scores = []
+        self.status = {m: [[] for _ in self.diffs] for m in ("bev", "3d")}
+        self.n_gt = [0] * len(self.diffs)
+
+    def add_frame(self, det_boxes, det_scores, lines):
+        r = evaluate_frame(det_boxes, det_scores, lines, self.cls_name, self.diffs, self.thr)
+        self.scores += [float(s) for s in det_scores]
+        for m in ("bev", "3d"):
+            for k in range(len(self.diffs)):
+                self.status[m][k] += [int(v) for v in r["status"][m][k]]
+        for k in range(len(self.diffs)):
+            self.n_gt[k] += int((~r["flags"][k]).sum())
+        return r
+
+    def compute(self):
+        out = {"n_gt": {d: self.n_gt[k] for k, d in enumerate(self.diffs)}, "n_det": len(self.scores)}
+        for m in ("bev", "3d"):
+            out[m] = {d: average_precision(self.scores, self.status[m][k], self.n_gt[k], self.recall_points)
+                      for k, d in enumerate(self.diffs)}
+        return out
+
+
+# ---------------------------------------------------------------------------------------------- scene generator
+_T_VELO_2_CAM = np.array([[7.49916597e-03, -9.99971248e-01, -8.65110297e-04, -6.71807577e-03],
+                          [1.18652889e-02, 9.54520517e-04, -9.99910318e-01, -7.33152811e-02],
+                          [9.99882833e-01, 7.49141178e-03, 1.18719929e-02, -2.78557062e-01],
+                          [0, 0, 0, 1]])
+_R_RECT_0 = np.array([[0.99992475, 0.00975976, -0.00734152, 0], [-0.0097913, 0.99994262, -0.00430371, 0],
+                      [0.00729911, 0.0043753, 0.99996319, 0], [0, 0, 0, 1]])
+
+
+def label_line(name, box, trunc=0.0, occ=0, height=50.0):
+    """a KITTI label line of the lidar box with the difficulty fields given (2D box: y1 = 100, y2 = 100 + height)"""
+    x, y, z, h, w, l, r = (float(v) for v in box)
+    p = _R_RECT_0 @ (_T_VELO_2_CAM @ np.array([x, y, z, 1.0]))
+    return (f"{name} {trunc:.2f} {int(occ)} 0.00 300.00 100.00 400.00 {100.0 + height:.2f} {h:.2f} {w:.2f} {l:.2f} "
+            f"{p[0]:.2f} {p[1]:.2f} {p[2]:.2f} {-r - np.pi / 2:.2f}")
+
+
+def make_frame(rng, top_k=20):
+    """-> (det_boxes (n,7) float32, det_scores (n,) float32 distinct in [0.96, 1), label lines)"""
+    n_gt = int(rng.integers(0, 13))
+    lines = []
+    for _ in range(n_gt):
+        box = [rng.uniform(5, 65), rng.uniform(-35, 35), rng.uniform(-2, -1), rng.uniform(1.4, 1.8), rng.uniform(1.5, 1.8),
+               rng.uniform(3.4, 4.5), rng.uniform(-np.pi / 2, np.pi / 2)]
+        # difficulty fields: every one of the four difficulties sees another set of valid ground truths
+        lines.append(label_line("Car", box, trunc=float(rng.choice([0.0, 0.1, 0.25, 0.4, 0.7])), occ=int(rng.integers(0, 4)),
+                                height=float(rng.uniform(15, 80))))
+    gt = label_to_gt_box_3d([lines], "Car", "lidar")[0]          # the boxes as the two-decimal label text gives them back
+    dets = []
+    for g in gt:
+        for _ in range(int(rng.choice([0, 1, 2], p=[0.2, 0.6, 0.2]))):
+            d = g.copy()
+            d[0:2] += rng.normal(0, 0.25, 2)
+            d[2] += rng.normal(0, 0.1)
+            d[6] += rng.normal(0, 0.1)
+            d[3:6] *= rng.uniform(0.93, 1.07, 3)
+            dets.append(d)
+    for _ in range(int(rng.integers(0, 5))):          # false positives of anchor size
+        dets.append(np.array([rng.uniform(5, 65), rng.uniform(-35, 35), -1.78, 1.56, 1.6, 3.9, rng.choice([0.0, np.pi / 2])]))
+    if dets:
+        dets = [dets[i] for i in rng.permutation(len(dets))][:top_k]
+    boxes = np.array(dets, dtype=np.float64).reshape(-1, 7).astype(np.float32)
+    n = boxes.shape[0]
+    # distinct float32 scores in [0.96, 1): distinct multiples of 2^-20 above 0.96
+    ticks = rng.choice(40000, size=n, replace=False)
+    scores = (np.float32(0.96) + ticks.astype(np.float32) * np.float32(2.0 ** -20)).astype(np.float32)
+    assert len(set(scores.tolist())) == n and (scores < 1).all()
+    return boxes, scores, lines
+
+
+def make_scene(seed, n_frames=64, top_k=20):
+    rng = np.random.default_rng(seed)
+    return [make_frame(rng, top_k) for _ in range(n_frames)]

@@ -105,6 +105,8 @@ class VnAugmentBox(ctypes.Structure):   # vnAugmentBox (vn_augment_points): one 
 
 VN_AUGMENT_BOXES, VN_AUGMENT_ROTATE, VN_AUGMENT_SCALE = 0, 1, 2       # vn_augment_points' `mode`
 VN_AUGMENT_MAX_BOXES = 128
+VN_EVAL_BEV, VN_EVAL_3D = 0, 1       # vn_box_iou_rotated's `metric`; axis 1 of vn_eval_match's outputs
+VN_EVAL_MAX_TOPK, VN_EVAL_MAX_DIFF = 32, 8
 
 
 # name -> (restype, argtypes); mirrors include/voxelnet_hip.h one to one
@@ -235,6 +237,10 @@ SIGNATURES = {
     "vn_rpn_predict_workspace_bytes": (c_sz, [c_i32, c_i32]),
     "vn_rpn_predict": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, ctypes.c_double, c_i32, ctypes.c_double, c_vp, c_vp, c_vp,
                                c_vp, c_sz, c_vp]),
+    "vn_box_iou_rotated": (c_i32, [c_vp, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp]),
+    "vn_eval_match_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32]),
+    "vn_eval_match": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, ctypes.c_double, ctypes.c_double,
+                              c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "vn_clip_sgd_workspace_bytes": (c_sz, [c_i32]),
     "vn_clip_sgd": (c_i32, [c_vp, c_i32, c_f32, c_f32, c_i32, c_vp, c_sz, c_vp, c_vp]),
 }

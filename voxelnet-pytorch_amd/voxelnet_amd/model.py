@@ -1029,18 +1029,44 @@ class RPN3D(nn.Module):
         if summary or visual:
             raise NotImplementedError("the summary / visual branches of RPN3D.predict draw with OpenCV (model.py:396-439): "
                                       "outside the accelerated path")
-        from .predict import BoxDecoder
-        dec = self.__dict__.get("_decoder")
-        if dec is None or dec.device != probs.device:
-            dec = BoxDecoder(self.cls_name, probs.device)
-            self.__dict__["_decoder"] = dec
-            self.anchors = dec.anchors
-        ret_box_3d, ret_score = dec(probs, deltas)
+        ret_box_3d, ret_score = self._box_decoder(probs.device)(probs, deltas)
         out = []
         for boxes_3d, scores in zip(ret_box_3d, ret_score):
             out.append(np.concatenate([np.tile(self.cls_name, len(boxes_3d))[:, np.newaxis], boxes_3d,
                                        scores[:, np.newaxis]], axis=-1))
         return data[0], out
+
+    def _box_decoder(self, device):
+        from .predict import BoxDecoder
+        dec = self.__dict__.get("_decoder")
+        if dec is None or dec.device != device:
+            dec = BoxDecoder(self.cls_name, device)
+            self.__dict__["_decoder"] = dec
+            self.anchors = dec.anchors
+        return dec
+
+    def evaluate(self, batches, device, evaluator=None, decoder=None):
+        """The validation loop a user would otherwise write around `predict`: every batch tuple of `batches` (the
+        7-tuples forward takes; x[1] = label lines) goes through an eval-mode, no_grad forward, BoxDecoder.decode_device
+        and evaluator.update — the maps, the decoded boxes and the matching stay on the device, nothing is waited for
+        until the caller asks the returned evaluator to compute().  evaluator: an evaluate.DetectionEvaluator (default:
+        a new one for this class); decoder: a predict.BoxDecoder (default: the module's own, full anchor grid).  The
+        module is back in the mode it was in afterwards."""
+        from .evaluate import DetectionEvaluator
+        device = torch.device(device)
+        if evaluator is None:
+            evaluator = DetectionEvaluator(self.cls_name, device)
+        dec = self._box_decoder(device) if decoder is None else decoder
+        was_training = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                for x in batches:
+                    prob, delta = self.detect(_parts_to(x[2], device), _parts_to(x[4], device))
+                    evaluator.update(*dec.decode_device(prob, delta, top_k=evaluator.top_k), x[1])
+        finally:
+            self.train(was_training)
+        return evaluator
 
     def _named_params(self):
         """list(self.named_parameters()), cached (the Parameter objects are stable; see _flat_params)"""

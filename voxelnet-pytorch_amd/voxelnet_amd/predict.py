@@ -24,8 +24,11 @@ class BoxDecoder:
         self.n_anchors = self._anchors_dev.shape[0]
         self.anchor_h = float(CLASS_CFG[cls_name]["h"])
 
-    def __call__(self, probs, deltas, score_thres=SCORE_THRES, nms_thres=NMS_THRES, top_k=NMS_POST_TOPK):
-        """probs (B,2,h,w), deltas (B,14,h,w) fp32 device tensors -> ([boxes (n_i,7) f32 numpy], [scores (n_i,) f32 numpy])"""
+    def decode_device(self, probs, deltas, score_thres=SCORE_THRES, nms_thres=NMS_THRES, top_k=NMS_POST_TOPK):
+        """probs (B,2,h,w), deltas (B,14,h,w) fp32 device tensors -> (boxes (B,top_k,7) f32, scores (B,top_k) f32, counts (B,)
+        int32) ON THE DEVICE, enqueued on the current stream without any host synchronisation: per sample the first
+        counts[b] rows are the kept detections in descending score, the rest is zero.  What evaluate.DetectionEvaluator
+        consumes."""
         if not (probs.is_cuda and deltas.is_cuda):
             raise _lib.VoxelnetHipError("predict: probs / deltas must be HIP tensors (no CPU path)")
         probs, deltas = probs.detach().float().contiguous(), deltas.detach().float().contiguous()
@@ -42,6 +45,12 @@ class BoxDecoder:
             _lib.call("vn_rpn_predict", probs.data_ptr(), deltas.data_ptr(), self._anchors_dev.data_ptr(), B, N,
                       float(score_thres), float(nms_thres), int(top_k), self.anchor_h, boxes.data_ptr(), scores.data_ptr(),
                       counts.data_ptr(), ws.data_ptr(), nbytes, _lib.raw_stream())
+        return boxes, scores, counts
+
+    def __call__(self, probs, deltas, score_thres=SCORE_THRES, nms_thres=NMS_THRES, top_k=NMS_POST_TOPK):
+        """probs (B,2,h,w), deltas (B,14,h,w) fp32 device tensors -> ([boxes (n_i,7) f32 numpy], [scores (n_i,) f32 numpy])"""
+        boxes, scores, counts = self.decode_device(probs, deltas, score_thres, nms_thres, top_k)
+        B = boxes.shape[0]
         cnt = counts.cpu().numpy()
         bh, sh = boxes.cpu().numpy(), scores.cpu().numpy()
         return [bh[b, :cnt[b]].copy() for b in range(B)], [sh[b, :cnt[b]].copy() for b in range(B)]
