@@ -888,6 +888,56 @@ int vn_eval_match(const float *det_boxes, const float *det_scores, const int32_t
                   int32_t n_diff, double thr_bev, double thr_3d, int8_t *status, int32_t *matched_gt, double *iou_out,
                   void *workspace, size_t workspace_bytes, vnStream stream);
 
+/* ---- detection tail for evaluation (csrc/detect.hip; rules: DESIGN.md section 1c) ---------------------------
+ * Extends the inference tail above (filter_boxes model.py:28-57, deltas_to_boxes_3d utils.py:476-489, utils.nms
+ * utils.py:492-553), which lets only the NMS_POST_TOPK = 20 best candidates enter a stand-up-rectangle NMS
+ * (utils.py:510), to the three steps an average precision needs: a pre-NMS top-K in the thousands, a greedy NMS on
+ * stand-up rectangles or on the ROTATED footprints, a post-NMS cap.  vn_rpn_predict keeps the reference's behaviour.
+ *
+ * vn_rpn_select_decode (model.py:34, utils.py:476-489, 509-510): probs, deltas, anchors as for vn_rpn_predict.  Per
+ * sample, of the M candidates with p >= score_thres (a NaN score is never one) the min(M, pre_top_k) largest by the
+ * key (score, flat index) — equal scores: the LARGER flat index first, -0.0 == +0.0 — in descending key order:
+ *   sel_boxes  [B,pre_top_k,7] float32: box j = flat delta elements 7j..7j+6 on anchor j, float64 arithmetic with a
+ *                                       float32 expf, stored as float32 (exactly vn_rpn_predict's decoding)
+ *   sel_scores [B,pre_top_k] float32, sel_idx [B,pre_top_k] int32 (flat index j), sel_counts [B] int32
+ * Rows beyond sel_counts[b] are left untouched.  The keys are unique: the result does not depend on the order in
+ * which the filter's atomics hand out slots.  Limits: 1 <= pre_top_k <= VN_DETECT_MAX_PRE, B * n_anchors < 2^28.
+ *
+ * vn_box_nms (utils.py:519-551 as an operation of its own): boxes [B,K,7] float32, row order = priority order;
+ * counts [B] int32 read ON THE DEVICE (above K: K, below 0: 0).  Walk the rows in order; a row that is not suppressed
+ * is kept; a kept row i suppresses every later row j with !(IoU(i,j) <= nms_thres); the walk stops once post_top_k
+ * rows are kept.  keep_idx [B,post_top_k] int32 (row numbers, -1 beyond the count), keep_counts [B] int32.
+ *   VN_NMS_STANDUP: vn_rpn_predict's arithmetic — float32 corners, float64 stand-up rectangles, areas without "+1";
+ *                   a NaN IoU suppresses.
+ *   VN_NMS_ROTATED: the BEV IoU of the detection scoring above (a float32 box is widened exactly; never NaN).  A row
+ *                   with a non-finite field or h, w or l <= 0 is never kept and suppresses nothing.
+ * Limits: 1 <= K <= VN_DETECT_MAX_PRE, 1 <= post_top_k <= VN_PREDICT_MAX_TOPK, nms_thres finite.
+ *
+ * vn_rpn_detect: vn_rpn_select_decode, vn_box_nms on its rows, and a gather of the kept rows into vn_rpn_predict's
+ * output format: boxes [B,post_top_k,7], scores [B,post_top_k], counts [B]; rows beyond the count are not written.
+ * Equal to the composition of the two operations exactly; with VN_NMS_STANDUP and pre_top_k == post_top_k
+ * bit-identical to vn_rpn_predict; deterministic from run to run.
+ *
+ * All three: asynchronous on `stream`, no host synchronisation, one workgroup per sample after the filter pass.
+ * VN_EINVAL for a size outside the limits, an unknown mode, a non-finite nms_thres or a null pointer (the workspace
+ * queries return 0 for such sizes); VN_EWORKSPACE for a workspace smaller than the query's answer. */
+#define VN_NMS_STANDUP 0
+#define VN_NMS_ROTATED 1
+#define VN_DETECT_MAX_PRE 4096
+size_t vn_rpn_select_decode_workspace_bytes(int32_t B, int32_t n_anchors, int32_t pre_top_k);
+int vn_rpn_select_decode(const float *probs, const float *deltas, const double *anchors, int32_t B, int32_t n_anchors,
+                         float score_thres, int32_t pre_top_k, double anchor_h, float *sel_boxes, float *sel_scores,
+                         int32_t *sel_idx, int32_t *sel_counts, void *workspace, size_t workspace_bytes, vnStream stream);
+size_t vn_box_nms_workspace_bytes(int32_t B, int32_t K);
+int vn_box_nms(const float *boxes, const int32_t *counts, int32_t B, int32_t K, int32_t mode, double nms_thres,
+               int32_t post_top_k, int32_t *keep_idx, int32_t *keep_counts, void *workspace, size_t workspace_bytes,
+               vnStream stream);
+size_t vn_rpn_detect_workspace_bytes(int32_t B, int32_t n_anchors, int32_t pre_top_k);
+int vn_rpn_detect(const float *probs, const float *deltas, const double *anchors, int32_t B, int32_t n_anchors,
+                  float score_thres, int32_t pre_top_k, int32_t mode, double nms_thres, int32_t post_top_k,
+                  double anchor_h, float *boxes, float *scores, int32_t *counts, void *workspace, size_t workspace_bytes,
+                  vnStream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,6 +29,7 @@
 //            (valid before ignored, IoU descending, index ascending) — a total order, so the result does not depend
 //            on the lane order of the reduction.
 // No host synchronisation: the detection counts are read on the device.
+// The pair function (box_iou_pair and its helpers) lives in common.h: detect.hip's rotated NMS calls it too.
 #include "common.h"
 
 namespace {
@@ -37,104 +38,10 @@ constexpr int EV_THREADS = 256;
 constexpr int EV_MAX_TOPK = VN_EVAL_MAX_TOPK;
 constexpr int EV_MAX_GT = VN_TARGETS_MAX_GT;
 constexpr int EV_MAX_DIFF = VN_EVAL_MAX_DIFF;
-constexpr int EV_NV = 8;          // vertices of a rectangle clipped by a rectangle
 
 static_assert(EV_MAX_TOPK <= VN_WAVE, "a lane per detection when the wave ranks the scores");
 static_assert(EV_MAX_GT <= 2 * VN_WAVE, "two ground truths per lane");
 static_assert(2 * EV_MAX_TOPK * EV_MAX_GT * sizeof(double) <= 65536, "both IoU tables fit the 64 KB of LDS a launch gets by default");
-
-__device__ __forceinline__ void poly_push(double (&px)[EV_NV], double (&py)[EV_NV], int &n, double x, double y) {
-#pragma unroll
-    for (int j = 0; j < EV_NV; ++j) {
-        const bool here = (j == n);
-        px[j] = here ? x : px[j];
-        py[j] = here ? y : py[j];
-    }
-    ++n;
-}
-
-// keep the part of the polygon on the left of the directed line through (ex, ey) with direction (dx, dy)
-__device__ __forceinline__ void clip_halfplane(const double (&ix)[EV_NV], const double (&iy)[EV_NV], int n, double ex, double ey,
-                                               double dx, double dy, double (&ox)[EV_NV], double (&oy)[EV_NV], int &m) {
-    m = 0;
-#pragma unroll
-    for (int j = 0; j < EV_NV; ++j) { ox[j] = 0.0; oy[j] = 0.0; }
-    double px = ix[0], py = iy[0];          // the last vertex: the walk starts on the edge last -> first
-#pragma unroll
-    for (int j = 1; j < EV_NV; ++j) {
-        const bool last = (j == n - 1);
-        px = last ? ix[j] : px;
-        py = last ? iy[j] : py;
-    }
-    double dp = dx * (py - ey) - dy * (px - ex);
-#pragma unroll
-    for (int i = 0; i < EV_NV; ++i) {
-        if (i < n) {
-            const double cx = ix[i], cy = iy[i];
-            const double dc = dx * (cy - ey) - dy * (cx - ex);
-            if ((dp >= 0.0) != (dc >= 0.0)) {
-                const double t = dp / (dp - dc);
-                poly_push(ox, oy, m, px + (cx - px) * t, py + (cy - py) * t);
-            }
-            if (dc >= 0.0) poly_push(ox, oy, m, cx, cy);
-            px = cx; py = cy; dp = dc;
-        }
-    }
-}
-
-__device__ __forceinline__ bool box_ok(const double (&q)[7]) {
-    bool ok = true;
-#pragma unroll
-    for (int k = 0; k < 7; ++k) ok = ok && isfinite(q[k]);
-    return ok && q[3] > 0.0 && q[4] > 0.0 && q[5] > 0.0;
-}
-
-// the ONE pair function: vn_box_iou_rotated and vn_eval_match both call it
-__device__ __forceinline__ void box_iou_pair(const double (&a)[7], const double (&b)[7], double &iou_bev, double &iou_3d) {
-    iou_bev = 0.0;
-    iou_3d = 0.0;
-    if (!(box_ok(a) && box_ok(b))) return;
-    const double ca = cos(a[6]), sa = sin(a[6]), cb = cos(b[6]), sb = sin(b[6]);
-    const double la = a[5] / 2, wa = a[4] / 2, lb = b[5] / 2, wb = b[4] / 2;
-    const double ox = b[0] - a[0], oy = b[1] - a[1];          // B's centre seen from A's
-    // counter-clockwise corners (+,+), (-,+), (-,-), (+,-) of the local (l, w) frame, turned by r
-    const double sx[4] = {1.0, -1.0, -1.0, 1.0}, sy[4] = {1.0, 1.0, -1.0, -1.0};
-    double p0x[EV_NV], p0y[EV_NV], p1x[EV_NV], p1y[EV_NV], bx[4], by[4];
-#pragma unroll
-    for (int k = 0; k < EV_NV; ++k) { p0x[k] = 0.0; p0y[k] = 0.0; }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const double ax = sx[k] * la, ay = sy[k] * wa;
-        p0x[k] = ax * ca - ay * sa;
-        p0y[k] = ax * sa + ay * ca;
-        const double qx = sx[k] * lb, qy = sy[k] * wb;
-        bx[k] = (qx * cb - qy * sb) + ox;
-        by[k] = (qx * sb + qy * cb) + oy;
-    }
-    int n = 4, m = 0;
-    clip_halfplane(p0x, p0y, n, bx[0], by[0], bx[1] - bx[0], by[1] - by[0], p1x, p1y, m);
-    clip_halfplane(p1x, p1y, m, bx[1], by[1], bx[2] - bx[1], by[2] - by[1], p0x, p0y, n);
-    clip_halfplane(p0x, p0y, n, bx[2], by[2], bx[3] - bx[2], by[3] - by[2], p1x, p1y, m);
-    clip_halfplane(p1x, p1y, m, bx[3], by[3], bx[0] - bx[3], by[0] - by[3], p0x, p0y, n);
-    double s = 0.0;
-#pragma unroll
-    for (int i = 0; i < EV_NV; ++i) {
-        if (i < n) {
-            const bool wrap = (i + 1 >= n);          // the closing edge: last -> first
-            const double nx = wrap ? p0x[0] : p0x[(i + 1) % EV_NV];
-            const double ny = wrap ? p0y[0] : p0y[(i + 1) % EV_NV];
-            s += p0x[i] * ny - nx * p0y[i];
-        }
-    }
-    const double inter = 0.5 * fabs(s);
-    const double area_a = a[4] * a[5], area_b = b[4] * b[5];
-    const double den2 = area_a + area_b - inter;
-    iou_bev = den2 > 0.0 ? inter / den2 : 0.0;
-    const double zo = fmax(0.0, fmin(a[2] + a[3], b[2] + b[3]) - fmax(a[2], b[2]));
-    const double inter3 = inter * zo;
-    const double den3 = a[3] * area_a + b[3] * area_b - inter3;
-    iou_3d = den3 > 0.0 ? inter3 / den3 : 0.0;
-}
 
 __global__ void __launch_bounds__(EV_THREADS) k_box_iou_rotated(const double *__restrict__ a, int na, const double *__restrict__ b,
                                                                 int nb, int metric, double *__restrict__ out) {

@@ -107,6 +107,8 @@ VN_AUGMENT_BOXES, VN_AUGMENT_ROTATE, VN_AUGMENT_SCALE = 0, 1, 2       # vn_augme
 VN_AUGMENT_MAX_BOXES = 128
 VN_EVAL_BEV, VN_EVAL_3D = 0, 1       # vn_box_iou_rotated's `metric`; axis 1 of vn_eval_match's outputs
 VN_EVAL_MAX_TOPK, VN_EVAL_MAX_DIFF = 32, 8
+VN_NMS_STANDUP, VN_NMS_ROTATED = 0, 1       # vn_box_nms' / vn_rpn_detect's `mode`
+VN_DETECT_MAX_PRE, VN_PREDICT_MAX_TOPK = 4096, 64
 
 
 # name -> (restype, argtypes); mirrors include/voxelnet_hip.h one to one
@@ -241,6 +243,14 @@ SIGNATURES = {
     "vn_eval_match_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32]),
     "vn_eval_match": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, ctypes.c_double, ctypes.c_double,
                               c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "vn_rpn_select_decode_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32]),
+    "vn_rpn_select_decode": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, c_i32, ctypes.c_double, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz,
+                                     c_vp]),
+    "vn_box_nms_workspace_bytes": (c_sz, [c_i32, c_i32]),
+    "vn_box_nms": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, ctypes.c_double, c_i32, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "vn_rpn_detect_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32]),
+    "vn_rpn_detect": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, c_i32, c_i32, ctypes.c_double, c_i32, ctypes.c_double, c_vp, c_vp,
+                              c_vp, c_vp, c_sz, c_vp]),
     "vn_clip_sgd_workspace_bytes": (c_sz, [c_i32]),
     "vn_clip_sgd": (c_i32, [c_vp, c_i32, c_f32, c_f32, c_i32, c_vp, c_sz, c_vp, c_vp]),
 }

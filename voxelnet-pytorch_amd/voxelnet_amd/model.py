@@ -1045,25 +1045,30 @@ class RPN3D(nn.Module):
             self.anchors = dec.anchors
         return dec
 
-    def evaluate(self, batches, device, evaluator=None, decoder=None):
+    def evaluate(self, batches, device, evaluator=None, decoder=None, decode=None):
         """The validation loop a user would otherwise write around `predict`: every batch tuple of `batches` (the
         7-tuples forward takes; x[1] = label lines) goes through an eval-mode, no_grad forward, BoxDecoder.decode_device
         and evaluator.update — the maps, the decoded boxes and the matching stay on the device, nothing is waited for
         until the caller asks the returned evaluator to compute().  evaluator: an evaluate.DetectionEvaluator (default:
-        a new one for this class); decoder: a predict.BoxDecoder (default: the module's own, full anchor grid).  The
-        module is back in the mode it was in afterwards."""
+        a new one for this class); decoder: a predict.BoxDecoder (default: the module's own, full anchor grid); decode: a dict of
+        BoxDecoder.decode_device keyword arguments (e.g. predict.EVAL_DECODE: a pre-NMS top-K and the rotated NMS; None:
+        the reference's tail); the post-NMS cap is always evaluator.top_k.  The module is back in the mode it was in
+        afterwards."""
         from .evaluate import DetectionEvaluator
         device = torch.device(device)
         if evaluator is None:
             evaluator = DetectionEvaluator(self.cls_name, device)
         dec = self._box_decoder(device) if decoder is None else decoder
+        kw = dict(decode or {})
+        if "top_k" in kw:
+            raise ValueError("evaluate: the post-NMS cap is evaluator.top_k; `decode` may not set top_k")
         was_training = self.training
         self.eval()
         try:
             with torch.no_grad():
                 for x in batches:
                     prob, delta = self.detect(_parts_to(x[2], device), _parts_to(x[4], device))
-                    evaluator.update(*dec.decode_device(prob, delta, top_k=evaluator.top_k), x[1])
+                    evaluator.update(*dec.decode_device(prob, delta, top_k=evaluator.top_k, **kw), x[1])
         finally:
             self.train(was_training)
         return evaluator

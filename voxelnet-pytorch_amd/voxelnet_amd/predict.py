@@ -1,7 +1,12 @@
 """Inference tail of the reference's `RPN3D.predict` (voxelnet/model.py:364-395) on the device: box decoding
 (utils.deltas_to_boxes_3d, utils.py:476-489), score filter, stand-up rectangles and NMS (model.filter_boxes,
 model.py:28-57; utils.nms, utils.py:492-553) through `vn_rpn_predict` (csrc/predict.hip).  The probability and delta
-maps never leave HBM; only the <= NMS_POST_TOPK kept boxes per sample come back.  No CPU fallback."""
+maps never leave HBM; only the <= NMS_POST_TOPK kept boxes per sample come back.  No CPU fallback.
+
+For evaluation the same tail with the three steps an average precision needs (csrc/detect.hip): a
+pre-NMS top-K in the thousands, a greedy NMS on stand-up rectangles or on the rotated footprints, a post-NMS cap —
+`decode_device(..., nms=, pre_nms_top_k=)` through `vn_rpn_detect`, and its two halves on their own:
+`BoxDecoder.candidates_device` (`vn_rpn_select_decode`) and `nms_device` (`vn_box_nms`)."""
 import ctypes
 
 import numpy as np
@@ -11,6 +16,48 @@ from . import _lib
 from .targets import CLASS_CFG, generate_anchors
 
 SCORE_THRES, NMS_THRES, NMS_POST_TOPK = 0.96, 0.1, 20          # config.py:95-98 (cfg.RPN)
+NMS_MODES = {"standup": _lib.VN_NMS_STANDUP, "rotated": _lib.VN_NMS_ROTATED}
+# A starting point for RPN3D.evaluate(decode=...), NOT tuned: there is no trained checkpoint here to tune it on.
+EVAL_DECODE = dict(score_thres=0.1, nms="rotated", nms_thres=0.1, pre_nms_top_k=1024)
+
+
+def _nms_mode(nms):
+    if nms not in NMS_MODES:
+        raise ValueError(f"nms must be one of {sorted(NMS_MODES)}, not {nms!r}")
+    return NMS_MODES[nms]
+
+
+def _check_range(name, v, hi):
+    if not (isinstance(v, (int, np.integer)) and 1 <= v <= hi):
+        raise ValueError(f"{name} must be an integer in [1, {hi}], not {v!r}")
+    return int(v)
+
+
+def nms_device(boxes, counts, mode="rotated", nms_thres=NMS_THRES, top_k=NMS_POST_TOPK):
+    """Greedy suppression as an operation of its own (vn_box_nms): boxes (B,K,7) f32 device tensor whose row order is the
+    priority order, counts (B,) int32 device tensor (read on the device; above K means K) -> (keep_idx (B,top_k) int32, the
+    kept row numbers in walk order, -1 past the count; keep_counts (B,) int32), on the device, no host synchronisation.
+    mode "standup": vn_rpn_predict's rule; "rotated": the BEV IoU of evaluate.box_iou_rotated, rows with a non-finite
+    field or h, w, l <= 0 are never kept."""
+    if not (boxes.is_cuda and counts.is_cuda):
+        raise _lib.VoxelnetHipError("nms_device: boxes / counts must be HIP tensors (no CPU path)")
+    m = _nms_mode(mode)
+    if boxes.dim() != 3 or boxes.shape[2] != 7 or counts.shape != (boxes.shape[0],) or boxes.shape[0] < 1:
+        raise ValueError(f"boxes {tuple(boxes.shape)} / counts {tuple(counts.shape)}: want (B,K,7) and (B,)")
+    B, K = boxes.shape[0], _check_range("K", boxes.shape[1], _lib.VN_DETECT_MAX_PRE)
+    top_k = _check_range("top_k", top_k, _lib.VN_PREDICT_MAX_TOPK)
+    if not np.isfinite(nms_thres):
+        raise ValueError("nms_thres must be finite")
+    boxes, counts = boxes.detach().float().contiguous(), counts.to(torch.int32).contiguous()
+    dev = boxes.device
+    keep = torch.empty((B, top_k), dtype=torch.int32, device=dev)
+    kc = torch.empty(B, dtype=torch.int32, device=dev)
+    nbytes = _lib.load().vn_box_nms_workspace_bytes(B, K)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    with _lib.on_device(dev):
+        _lib.call("vn_box_nms", boxes.data_ptr(), counts.data_ptr(), B, K, m, float(nms_thres), top_k, keep.data_ptr(),
+                  kc.data_ptr(), ws.data_ptr(), nbytes, _lib.raw_stream())
+    return keep, kc
 
 
 class BoxDecoder:
@@ -24,32 +71,77 @@ class BoxDecoder:
         self.n_anchors = self._anchors_dev.shape[0]
         self.anchor_h = float(CLASS_CFG[cls_name]["h"])
 
-    def decode_device(self, probs, deltas, score_thres=SCORE_THRES, nms_thres=NMS_THRES, top_k=NMS_POST_TOPK):
+    def _maps(self, probs, deltas, what):
+        if not (probs.is_cuda and deltas.is_cuda):
+            raise _lib.VoxelnetHipError(f"{what}: probs / deltas must be HIP tensors (no CPU path)")
+        probs, deltas = probs.detach().float().contiguous(), deltas.detach().float().contiguous()
+        N = self.n_anchors
+        if probs[0].numel() != N or deltas[0].numel() != 7 * N:
+            raise ValueError(f"maps of {probs[0].numel()} / {deltas[0].numel()} elements do not match {N} anchors")
+        return probs, deltas
+
+    def decode_device(self, probs, deltas, score_thres=SCORE_THRES, nms_thres=NMS_THRES, top_k=NMS_POST_TOPK, nms="standup",
+                      pre_nms_top_k=None):
         """probs (B,2,h,w), deltas (B,14,h,w) fp32 device tensors -> (boxes (B,top_k,7) f32, scores (B,top_k) f32, counts (B,)
         int32) ON THE DEVICE, enqueued on the current stream without any host synchronisation: per sample the first
         counts[b] rows are the kept detections in descending score, the rest is zero.  What evaluate.DetectionEvaluator
-        consumes."""
-        if not (probs.is_cuda and deltas.is_cuda):
-            raise _lib.VoxelnetHipError("predict: probs / deltas must be HIP tensors (no CPU path)")
-        probs, deltas = probs.detach().float().contiguous(), deltas.detach().float().contiguous()
+        consumes.
+        nms="standup", pre_nms_top_k=None is the reference's tail (vn_rpn_predict: the top_k best candidates enter a
+        stand-up-rectangle NMS).  Anything else goes through vn_rpn_detect: the pre_nms_top_k (default top_k) best
+        candidates enter the NMS, on stand-up rectangles or, nms="rotated", on the rotated footprints; top_k caps what
+        it keeps."""
+        mode = _nms_mode(nms)
+        probs, deltas = self._maps(probs, deltas, "predict")
         B, N = probs.shape[0], self.n_anchors
-        if probs[0].numel() != N or deltas[0].numel() != 7 * N:
-            raise ValueError(f"maps of {probs[0].numel()} / {deltas[0].numel()} elements do not match {N} anchors")
         dev = probs.device
+        if pre_nms_top_k is not None or mode != _lib.VN_NMS_STANDUP:
+            top_k = _check_range("top_k", top_k, _lib.VN_PREDICT_MAX_TOPK)
+            pre = _check_range("pre_nms_top_k", top_k if pre_nms_top_k is None else pre_nms_top_k, _lib.VN_DETECT_MAX_PRE)
+            if not np.isfinite(nms_thres):
+                raise ValueError("nms_thres must be finite")
         boxes = torch.zeros((B, top_k, 7), dtype=torch.float32, device=dev)
         scores = torch.zeros((B, top_k), dtype=torch.float32, device=dev)
         counts = torch.zeros(B, dtype=torch.int32, device=dev)
-        nbytes = _lib.load().vn_rpn_predict_workspace_bytes(B, N)
+        if pre_nms_top_k is None and mode == _lib.VN_NMS_STANDUP:
+            nbytes = _lib.load().vn_rpn_predict_workspace_bytes(B, N)
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            with _lib.on_device(dev):
+                _lib.call("vn_rpn_predict", probs.data_ptr(), deltas.data_ptr(), self._anchors_dev.data_ptr(), B, N,
+                          float(score_thres), float(nms_thres), int(top_k), self.anchor_h, boxes.data_ptr(), scores.data_ptr(),
+                          counts.data_ptr(), ws.data_ptr(), nbytes, _lib.raw_stream())
+            return boxes, scores, counts
+        nbytes = _lib.load().vn_rpn_detect_workspace_bytes(B, N, pre)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         with _lib.on_device(dev):
-            _lib.call("vn_rpn_predict", probs.data_ptr(), deltas.data_ptr(), self._anchors_dev.data_ptr(), B, N,
-                      float(score_thres), float(nms_thres), int(top_k), self.anchor_h, boxes.data_ptr(), scores.data_ptr(),
-                      counts.data_ptr(), ws.data_ptr(), nbytes, _lib.raw_stream())
+            _lib.call("vn_rpn_detect", probs.data_ptr(), deltas.data_ptr(), self._anchors_dev.data_ptr(), B, N, float(score_thres),
+                      pre, mode, float(nms_thres), top_k, self.anchor_h, boxes.data_ptr(), scores.data_ptr(), counts.data_ptr(),
+                      ws.data_ptr(), nbytes, _lib.raw_stream())
         return boxes, scores, counts
 
-    def __call__(self, probs, deltas, score_thres=SCORE_THRES, nms_thres=NMS_THRES, top_k=NMS_POST_TOPK):
+    def candidates_device(self, probs, deltas, score_thres, pre_nms_top_k):
+        """The first half of the tail on its own (vn_rpn_select_decode): per sample the min(M, pre_nms_top_k) best of the M
+        candidates with p >= score_thres, decoded, in descending (score, flat index) order -> (boxes (B,pre,7) f32, scores
+        (B,pre) f32, flat anchor indices (B,pre) int32, counts (B,) int32) on the device; rows past the count are zero."""
+        probs, deltas = self._maps(probs, deltas, "candidates")
+        pre = _check_range("pre_nms_top_k", pre_nms_top_k, _lib.VN_DETECT_MAX_PRE)
+        B, N = probs.shape[0], self.n_anchors
+        dev = probs.device
+        boxes = torch.zeros((B, pre, 7), dtype=torch.float32, device=dev)
+        scores = torch.zeros((B, pre), dtype=torch.float32, device=dev)
+        idx = torch.zeros((B, pre), dtype=torch.int32, device=dev)
+        counts = torch.zeros(B, dtype=torch.int32, device=dev)
+        nbytes = _lib.load().vn_rpn_select_decode_workspace_bytes(B, N, pre)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        with _lib.on_device(dev):
+            _lib.call("vn_rpn_select_decode", probs.data_ptr(), deltas.data_ptr(), self._anchors_dev.data_ptr(), B, N,
+                      float(score_thres), pre, self.anchor_h, boxes.data_ptr(), scores.data_ptr(), idx.data_ptr(), counts.data_ptr(),
+                      ws.data_ptr(), nbytes, _lib.raw_stream())
+        return boxes, scores, idx, counts
+
+    def __call__(self, probs, deltas, score_thres=SCORE_THRES, nms_thres=NMS_THRES, top_k=NMS_POST_TOPK, nms="standup",
+                 pre_nms_top_k=None):
         """probs (B,2,h,w), deltas (B,14,h,w) fp32 device tensors -> ([boxes (n_i,7) f32 numpy], [scores (n_i,) f32 numpy])"""
-        boxes, scores, counts = self.decode_device(probs, deltas, score_thres, nms_thres, top_k)
+        boxes, scores, counts = self.decode_device(probs, deltas, score_thres, nms_thres, top_k, nms, pre_nms_top_k)
         B = boxes.shape[0]
         cnt = counts.cpu().numpy()
         bh, sh = boxes.cpu().numpy(), scores.cpu().numpy()
