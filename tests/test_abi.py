@@ -323,21 +323,42 @@ def test_every_production_plan_id_has_a_case():
     benchmarked layer lands on a kernel no stage test compares with its float64 oracle fails here, on the CPU.
     middle_layer.0 is exempt: its forward is the rulebook (test_gpu_bf16_parity.test_bf16_rulebook_first_layer), its
     weight and data gradients run over the active-site list, checked through the executor
-    (test_gpu_native_chain.test_bf16_native_gradients_vs_exact_chain_on_the_native_forward, every config)."""
+    (test_gpu_native_chain.test_bf16_native_gradients_vs_exact_chain_on_the_native_forward, every config).
+    The same for operands of VN_F32 and VN_F32X3 (the fp32 and fp32x3 modes; tests/test_gpu_fp32_parity.py runs the same
+    rows): conv ids as in bf16, weight-gradient ids 22 / 44 (no three-tap and no patch form outside bf16)."""
     from test_gpu_bf16_parity import CASES, make_spec, plan_ids
-    from voxelnet_amd import _lib
-    covered = set()
-    for case in CASES:
-        spec = make_spec(case)
-        for stage, i in zip(("forward", "data gradient", "weight gradient"), case[10]):
-            covered.add((_kind(spec), stage, i))
-    missing = []
-    for plan, (B, D, H, W, stride) in sorted(BENCH_PLANS.items()):
-        for name, spec, dims in _layer_inputs(B, D, H, W, stride):
-            if name == "middle_layer.0":
-                continue
-            ids = plan_ids(_lib, spec, B, dims)
-            for stage, i in zip(("forward", "data gradient", "weight gradient"), ids):
-                if (_kind(spec), stage, i) not in covered:
-                    missing.append((plan, name, stage, i))
-    assert missing == [], f"production kernel ids without a test_gpu_bf16_parity.CASES row: {missing}"
+    from test_gpu_fp32_parity import expected_ids
+    from voxelnet_amd import _lib, engine as E
+    for dtype in (_lib.VN_BF16, _lib.VN_F32, E.VN_F32X3):
+        covered = set()
+        for case in CASES:
+            spec = make_spec(case)
+            for stage, i in zip(("forward", "data gradient", "weight gradient"), expected_ids(case, dtype)):
+                covered.add((_kind(spec), stage, i))
+        missing = []
+        for plan, (B, D, H, W, stride) in sorted(BENCH_PLANS.items()):
+            for name, spec, dims in _layer_inputs(B, D, H, W, stride):
+                if name == "middle_layer.0":
+                    continue
+                ids = plan_ids(_lib, spec, B, dims, dtype)
+                for stage, i in zip(("forward", "data gradient", "weight gradient"), ids):
+                    if (_kind(spec), stage, i) not in covered:
+                        missing.append((plan, name, stage, i))
+        assert missing == [], f"production kernel ids (operand dtype {dtype}) without a test_gpu_bf16_parity.CASES row: {missing}"
+
+
+def test_fp32_rows_select_the_production_kernels_on_the_host():
+    """every row of CASES, operands VN_F32 and VN_F32X3: the test shape and the production shape it stands for give the same
+    (forward, data-gradient, weight-gradient) ids, and these are the expected ones (host only; the GPU test asserts it
+    again in front of the launches)"""
+    from test_gpu_bf16_parity import CASES, make_spec, plan_ids
+    from test_gpu_fp32_parity import expected_ids
+    from voxelnet_amd import _lib, engine as E
+    for dtype in (_lib.VN_F32, E.VN_F32X3):
+        for case in CASES:
+            spec = make_spec(case)
+            dim = case[2]
+            (B, sp), (Bp, spp) = case[8], case[9]
+            ids = plan_ids(_lib, spec, B, (1,) + tuple(sp) if dim == 2 else tuple(sp), dtype)
+            ids_prod = plan_ids(_lib, spec, Bp, (1,) + tuple(spp) if dim == 2 else tuple(spp), dtype)
+            assert ids == ids_prod == expected_ids(case, dtype), (case[0], dtype, ids, ids_prod)

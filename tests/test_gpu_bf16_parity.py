@@ -118,20 +118,22 @@ def dense_geom(_lib, dtype, B, src_dims, row_dims, Cs, Cr, k, mul, tmul, pad, di
     return g
 
 
-def plan_ids(_lib, spec, B, in_dims):
-    """(forward, data-gradient, weight-gradient) kernel ids the library picks for this layer at this size"""
+def plan_ids(_lib, spec, B, in_dims, dtype=None):
+    """(forward, data-gradient, weight-gradient) kernel ids the library picks for this layer at this size, for operands of
+    `dtype` (default VN_BF16; VN_F32 / VN_F32X3: tests/test_gpu_fp32_parity.py)"""
     lib = _lib.load()
+    dt = _lib.VN_BF16 if dtype is None else dtype
     od = spec.out_dims(in_dims)
     neg = tuple(-p for p in spec.pad)
     one, mone = (1, 1, 1), (-1, -1, -1)
     if spec.transposed:
-        gf = dense_geom(_lib, _lib.VN_BF16, B, in_dims, od, spec.cin, spec.cout, spec.k, one, mone, neg, spec.stride)
-        gd = dense_geom(_lib, _lib.VN_BF16, B, od, in_dims, spec.cout, spec.cin, spec.k, spec.stride, one, spec.pad, one)
-        gw = dense_geom(_lib, _lib.VN_BF16, B, od, in_dims, spec.cout, spec.cin, spec.k, spec.stride, one, spec.pad, one)
+        gf = dense_geom(_lib, dt, B, in_dims, od, spec.cin, spec.cout, spec.k, one, mone, neg, spec.stride)
+        gd = dense_geom(_lib, dt, B, od, in_dims, spec.cout, spec.cin, spec.k, spec.stride, one, spec.pad, one)
+        gw = dense_geom(_lib, dt, B, od, in_dims, spec.cout, spec.cin, spec.k, spec.stride, one, spec.pad, one)
     else:
-        gf = dense_geom(_lib, _lib.VN_BF16, B, in_dims, od, spec.cin, spec.cout, spec.k, spec.stride, one, spec.pad, one)
-        gd = dense_geom(_lib, _lib.VN_BF16, B, od, in_dims, spec.cout, spec.cin, spec.k, one, mone, neg, spec.stride)
-        gw = dense_geom(_lib, _lib.VN_BF16, B, in_dims, od, spec.cin, spec.cout, spec.k, spec.stride, one, spec.pad, one)
+        gf = dense_geom(_lib, dt, B, in_dims, od, spec.cin, spec.cout, spec.k, spec.stride, one, spec.pad, one)
+        gd = dense_geom(_lib, dt, B, od, in_dims, spec.cout, spec.cin, spec.k, one, mone, neg, spec.stride)
+        gw = dense_geom(_lib, dt, B, in_dims, od, spec.cin, spec.cout, spec.k, spec.stride, one, spec.pad, one)
     return (lib.vn_conv_plan_id(ctypes.byref(gf)), lib.vn_conv_plan_id(ctypes.byref(gd)),
             lib.vn_conv_wgrad_plan_id(ctypes.byref(gw), 0, 0))
 
@@ -360,11 +362,22 @@ def test_bf16_heads_and_loss_grad_rows():
                     "heads db")
 
 
-def test_bf16_rulebook_first_layer():
-    """middle_layer.0 (model.py:207) as production runs it in bf16: voxel rows x packed weights as one GEMM, then the
-    rulebook gather-sum per active site (no dense grid), against conv3d of the scattered grid in float64 on the same
-    bf16 operands; its backward (flagged BatchNorm apply, row-list weight / data gradient) through the executor is
-    covered by test_bf16_step_vs_fp32_step and the fp32 full-frame tests."""
+def relu_like(shape, seed, channel_axis):
+    """fp32 operands that are NOT bf16-representable (every lo part of an fp32x3 split is live) and look like real
+    activations: relu(N(0,1)) * s_c with s_c log-uniform in [1e-2, 10] per channel (tests/test_gpu_fp32_parity.py)"""
+    rng = np.random.default_rng(seed)
+    v = np.maximum(rng.standard_normal(shape), 0.0)
+    sc = np.exp(rng.uniform(np.log(1e-2), np.log(10.0), size=shape[channel_axis]))
+    bshape = [1] * len(shape)
+    bshape[channel_axis] = shape[channel_axis]
+    return torch.from_numpy((v * sc.reshape(bshape)).astype(np.float32))
+
+
+def run_rulebook_first_layer(mode):
+    """middle_layer.0 as the executor runs it (csrc/runtime.hip net_prepare + vn_net_forward, layer 0) in `mode`
+    ("bf16": bf16 voxel rows and weights, bf16 y; "fp32" / "fp32x3" with engine.X3 set by the caller: fp32 operands that
+    are not bf16-representable, the P GEMM with VN_F32 / VN_F32X3 operands, y in fp32) -> the kernel's y and statistics
+    slab and the float64 oracle (conv3d of the scattered grid) on the same operands"""
     from voxelnet_amd import _lib, engine as E
     from voxelnet_amd.net import layer_table
     dev = torch.device(DEV)
@@ -375,22 +388,29 @@ def test_bf16_rulebook_first_layer():
     cells = rng.choice(B * D * H * W, size=K, replace=False)
     cells.sort()
     coord = torch.from_numpy(np.stack([cells // (D * H * W), (cells // (H * W)) % D, (cells // W) % H, cells % W], 1).astype(np.int64))
-    vw = bf16r(seeded((K, 128), 8102))
-    w = bf16r(tr._fill((64, 128, 3, 3, 3), 8103, 1.0 / np.sqrt(128 * 27)))
+    if mode == "bf16":
+        vw = bf16r(seeded((K, 128), 8102))
+        w = bf16r(tr._fill((64, 128, 3, 3, 3), 8103, 1.0 / np.sqrt(128 * 27)))
+    else:
+        vw = relu_like((K, 128), 8102, 1)
+        w = tr._fill((64, 128, 3, 3, 3), 8103, 1.0 / np.sqrt(128 * 27))
     bias = tr._fill((64,), 8104, 0.1)
     od = spec.out_dims((D, H, W))
     dense = torch.zeros((B, D, H, W, 128), dtype=torch.float64)
     dense[coord[:, 0], coord[:, 1], coord[:, 2], coord[:, 3]] = vw.double()
-    y64 = F.conv3d(dense.permute(0, 4, 1, 2, 3), w.double(), bias.double(), spec.stride, spec.pad)
+    dense = dense.permute(0, 4, 1, 2, 3)
+    y64 = F.conv3d(dense, w.double(), bias.double(), spec.stride, spec.pad)
     # --- the executor's call sequence (csrc/runtime.hip net_prepare + vn_net_forward, layer 0)
-    coord_d, vw_d = coord.to(dev), vw.to(dev).bfloat16()
-    wp = E.pack_weight(w.to(dev), spec, 0, "bf16")
-    y = E.Rows(torch.empty((B,) + od + (64,), dtype=torch.bfloat16, device=dev), 64)
+    vdt = _lib.VN_BF16 if mode == "bf16" else _lib.VN_F32
+    odt = E.VN_F32X3 if (mode != "bf16" and E.X3["on"]) else vdt        # operand dtype of the P GEMM
+    coord_d, vw_d = coord.to(dev), vw.to(dev).to(E.plain_dtype_of(mode))
+    wp = E.pack_weight(w.to(dev), spec, 0, mode)
+    y = E.Rows(torch.empty((B,) + od + (64,), dtype=E.plain_dtype_of(mode), device=dev), 64)
     M = y.M
     bias_d = bias.to(dev)
-    _lib.call("vn_fill_rows", y.ptr(), _lib.VN_BF16, M, 64, 64, bias_d.data_ptr(), E.stream())
+    _lib.call("vn_fill_rows", y.ptr(), vdt, M, 64, 64, bias_d.data_ptr(), E.stream())
     g = _lib.VnConv()
-    g.dtype = _lib.VN_BF16
+    g.dtype = odt
     g.B = B
     g.Ds, g.Hs, g.Ws = D, H, W
     g.Dr, g.Hr, g.Wr = od
@@ -413,7 +433,7 @@ def test_bf16_rulebook_first_layer():
     _lib.call("vn_voxel_index_grid", coord_d.data_ptr(), K, B, D, H, W, igrid.data_ptr(), E.stream())
     rbP = torch.empty((K, 27 * 64), dtype=torch.float32, device=dev)
     q = _lib.VnConv()
-    q.dtype = _lib.VN_BF16
+    q.dtype = odt
     q.B = 1
     q.Ds = q.Hs = 1; q.Ws = K
     q.Dr = q.Hr = 1; q.Wr = K
@@ -424,20 +444,37 @@ def test_bf16_rulebook_first_layer():
     q.divD = q.divH = q.divW = 1
     q.src_sB = q.src_sD = q.src_sH = K * 128; q.src_sW = 128
     q.out_sB = q.out_sD = q.out_sH = K * 27 * 64; q.out_sW = 27 * 64
+    gemm_plan = lib.vn_conv_plan_id(ctypes.byref(q))
     _lib.call("vn_conv_gather_gemm", vw_d.data_ptr(), wp.data_ptr(), None, rbP.data_ptr(), _lib.VN_F32, ctypes.byref(q), 0,
               None, E.stream())
     srows = lib.vn_rulebook_slab_rows(cap)
     slab = torch.empty((srows, 2, 64), dtype=torch.float32, device=dev)
     _lib.call("vn_rulebook_combine", rbP.data_ptr(), igrid.data_ptr(), alist.data_ptr(), cap, acount.data_ptr(),
-              ctypes.byref(g), bias_d.data_ptr(), y.ptr(), _lib.VN_BF16, slab.data_ptr(), E.stream())
-    ref = y64.permute(0, 2, 3, 4, 1).reshape(y.t.shape).numpy()
-    e = assert_rounded(y.t, ref, "rulebook y")
-    # fused statistics: sum / sum of squares of (y - bias) over the active rows == over all rows
-    s = slab.double().sum(0).cpu()
-    yc = (y64 - bias.double().view(1, 64, 1, 1, 1))
+              ctypes.byref(g), bias_d.data_ptr(), y.ptr(), vdt, slab.data_ptr(), E.stream())
+    torch.cuda.synchronize()
+    return {"y": y, "y64": y64, "bias": bias, "slab": slab, "dense": dense, "vw": vw, "w": w, "active": int(acount[0]), "M": M,
+            "gemm_plan": gemm_plan}
+
+
+def assert_rulebook_slab(r):
+    """the rulebook's fused statistics: sum / sum of squares of (y - bias) over the active rows == over all rows"""
+    s = r["slab"].double().sum(0).cpu()
+    yc = (r["y64"] - r["bias"].double().view(1, 64, 1, 1, 1))
     assert_fp32_sum(s[0].float(), yc.sum(dim=(0, 2, 3, 4)).numpy(), yc.abs().sum(dim=(0, 2, 3, 4)).numpy(), "rulebook sum")
     assert_fp32_sum(s[1].float(), (yc * yc).sum(dim=(0, 2, 3, 4)).numpy(), (yc * yc).sum(dim=(0, 2, 3, 4)).numpy(), "rulebook sumsq")
-    print("rulebook first layer: y max err / max %.1e, rel-L2 %.1e, active sites %d of %d" % (e[0], e[1], int(acount[0]), M))
+
+
+def test_bf16_rulebook_first_layer():
+    """middle_layer.0 (model.py:207) as production runs it in bf16: voxel rows x packed weights as one GEMM, then the
+    rulebook gather-sum per active site (no dense grid), against conv3d of the scattered grid in float64 on the same
+    bf16 operands; its backward (flagged BatchNorm apply, row-list weight / data gradient) through the executor is
+    covered by test_bf16_step_vs_fp32_step and the fp32 full-frame tests."""
+    r = run_rulebook_first_layer("bf16")
+    y = r["y"]
+    ref = r["y64"].permute(0, 2, 3, 4, 1).reshape(y.t.shape).numpy()
+    e = assert_rounded(y.t, ref, "rulebook y")
+    assert_rulebook_slab(r)
+    print("rulebook first layer: y max err / max %.1e, rel-L2 %.1e, active sites %d of %d" % (e[0], e[1], r["active"], r["M"]))
 
 
 def test_bf16_step_vs_fp32_step():
