@@ -403,6 +403,44 @@ int vn_augment_points(const float *points, int64_t n, int32_t mode, const vnAugm
                       double s, float scale, float *out, vnStream stream);
 
 /* ------------------------------------------------------------------------
+ * Ground-truth database sampling ("GT-paste") — the per-point half (csrc/gtsample.hip): cut labelled objects with their
+ * points out of the training frames, paste a few into every training frame where they collide with nothing.  The
+ * reference has no counterpart; the draw and the collision test are O(boxes) host work (voxelnet_amd/gtsample.py).
+ * points (n,4) fp32 [x,y,z,reflectance], 16-byte aligned; boxes = DEVICE table of 0 <= n_boxes <= VN_GT_MAX_BOXES
+ * entries (16-byte aligned).  An entry comes from a lidar box (x, y, z, h, w, l, r): z0 = z, z1 = z + h, hl = l / 2,
+ * hw = w / 2, c = cos(r), s = sin(r) — the HOST's cos / sin.
+ *   inside, for a point (px, py, pz) widened exactly to float64, in float64 exactly as written, no contraction:
+ *     dx = px - x;  dy = py - y;  u = dx*c + dy*s;  v = -(dx*s) + dy*c
+ *     inside  <=>  |u| <= hl  and  |v| <= hw  and  pz >= z0  and  pz <= z1      (inclusive; a NaN anywhere fails)
+ *   There is no fp32 prefilter: every decision is the float64 one.
+ * vn_points_in_boxes: out_index[i] (n int32) = the lowest table index whose box holds point i, else -1; out_counts[j]
+ *   (n_boxes int32, may be NULL) = the number of points inside box j — a point inside two boxes counts for both; integer
+ *   adds only, so the counts are deterministic.  n == 0 is a no-op apart from the zeroed counts.  No workspace.
+ * vn_gt_paste: a scene row is kept when none of its x, y, z is NaN (the padding rows of vn_fov_crop go) and it is inside
+ *   no box.  out_points (cap rows, cap >= n + m, else VN_EINVAL): rows [0, k) = the kept scene rows in input order,
+ *   reflectance copied; rows [k, k + m) = obj_points (m,4) in order, verbatim; rows [k + m, cap) = NaN points, which every
+ *   range test downstream drops, so the voxelizer runs on all cap rows without the count being read back; *out_count
+ *   (device int32) = k + m.  out_points must not overlap either input (VN_EINVAL).  n, m and n_boxes may each be 0.
+ *   Misaligned pointers: VN_EUNSUPPORTED; a workspace below vn_gt_paste_workspace_bytes(n): VN_EWORKSPACE.
+ *   Three launches (flags + per-workgroup counts, one-workgroup scan, compaction + append + NaN fill); no workgroup
+ *   waits on another one.
+ * Asynchronous.
+ * ---------------------------------------------------------------------- */
+#define VN_GT_MAX_BOXES 128
+typedef struct vnGtBox {
+    double x, y;          /* footprint centre */
+    double z0, z1;        /* bottom and top: z, z + h */
+    double hl, hw;        /* half length (along the heading), half width */
+    double c, s;          /* cos(r), sin(r) */
+} vnGtBox;                /* 64 bytes */
+int vn_points_in_boxes(const float *points, int64_t n, const vnGtBox *boxes, int32_t n_boxes, int32_t *out_index,
+                       int32_t *out_counts, vnStream stream);
+size_t vn_gt_paste_workspace_bytes(int64_t n);
+int vn_gt_paste(const float *points, int64_t n, const vnGtBox *boxes, int32_t n_boxes, const float *obj_points, int64_t m,
+                float *out_points, int64_t cap, int32_t *out_count, void *workspace, size_t workspace_bytes,
+                vnStream stream);
+
+/* ------------------------------------------------------------------------
  * Native step executor — MiddleConvNet.forward (model.py:257-281) and its backward as ONE call
  * each (csrc/runtime.hip): layer table, launch geometry and workspace arena live in C++, so the
  * ~450 launches of a step cost microseconds of host time instead of a Python round trip each.

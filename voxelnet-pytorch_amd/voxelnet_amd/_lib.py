@@ -105,6 +105,13 @@ class VnAugmentBox(ctypes.Structure):   # vnAugmentBox (vn_augment_points): one 
 
 VN_AUGMENT_BOXES, VN_AUGMENT_ROTATE, VN_AUGMENT_SCALE = 0, 1, 2       # vn_augment_points' `mode`
 VN_AUGMENT_MAX_BOXES = 128
+
+
+class VnGtBox(ctypes.Structure):   # vnGtBox (vn_points_in_boxes, vn_gt_paste): one entry of the device box table, 64 bytes
+    _fields_ = [(n, ctypes.c_double) for n in ("x", "y", "z0", "z1", "hl", "hw", "c", "s")]
+
+
+VN_GT_MAX_BOXES = 128
 VN_EVAL_BEV, VN_EVAL_3D = 0, 1       # vn_box_iou_rotated's `metric`; axis 1 of vn_eval_match's outputs
 VN_EVAL_MAX_TOPK, VN_EVAL_MAX_DIFF = 32, 8
 VN_NMS_STANDUP, VN_NMS_ROTATED = 0, 1       # vn_box_nms' / vn_rpn_detect's `mode`
@@ -131,6 +138,9 @@ SIGNATURES = {
     "vn_fov_crop_workspace_bytes": (c_sz, [c_i64]),
     "vn_fov_crop": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "vn_augment_points": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i32, ctypes.c_double, ctypes.c_double, c_f32, c_vp, c_vp]),
+    "vn_points_in_boxes": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_vp, c_vp, c_vp]),
+    "vn_gt_paste_workspace_bytes": (c_sz, [c_i64]),
+    "vn_gt_paste": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_sz, c_vp]),
     "vn_comm_rccl_version": (c_i32, []),
     "vn_comm_unique_id": (c_i32, [c_vp]),
     "vn_comm_create": (c_i32, [_P(c_vp), c_vp, c_i32, c_i32]),

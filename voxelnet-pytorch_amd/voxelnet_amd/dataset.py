@@ -14,7 +14,13 @@ Data augmentation (dataset.py:122-219, `pcl_augmentation`: per-box perturbation,
 stage of this pipeline, not of the dataset: copy -> [field-of-view crop] -> augment -> voxelize.  `DeviceCollate(...,
 augment=True)` / `DeviceBatcher(..., augment=True)` draw the parameters per sample on the host (augment.py, after the
 sample's shuffle), move the points on the device (csrc/augment.hip) and hand the model the moved label lines.  The
-dataset itself runs in DataLoader workers, which must not touch the GPU: `KITTIDataset(augment=True)` still raises."""
+dataset itself runs in DataLoader workers, which must not touch the GPU: `KITTIDataset(augment=True)` still raises.
+
+Ground-truth database sampling (gtsample.py; SECOND's "GT-paste", no counterpart in the reference) is the stage in front
+of the augmentation: copy -> [field-of-view crop] -> paste -> augment -> voxelize.  `DeviceCollate(..., gt_sampler=s)` /
+`DeviceBatcher(..., gt_sampler=s)` draw the pasted objects per sample on the host (after the sample's shuffle, before the
+augmentation's draw, which then runs on the enlarged labels), paste their points on the device (csrc/gtsample.hip) and
+hand the model labels + the pasted objects' lines."""
 import glob
 import os
 
@@ -71,7 +77,7 @@ class DeviceCollate:
     GPU (not in a DataLoader worker)."""
 
     def __init__(self, device="cuda:0", target="Car", shuffle_points=True, fov_calib_dir=None, image_shape=(375, 1242),
-                 augment=False):
+                 augment=False, gt_sampler=None):
         """augment: the reference's pcl_augmentation (dataset.py:122-219) per sample — drawn from np.random after the
         sample's shuffle, applied to the (cropped) cloud on the device in front of the voxelizer; the batch's `label`
         element then holds the MOVED label lines (augment.augment_labels), its raw-lidar element the host cloud as shuffled.
@@ -79,7 +85,12 @@ class DeviceCollate:
         (the reference does this offline, preprocess_data.py:42-154, and trains on the rewritten .bin files):
         `<fov_calib_dir>/<tag>.txt` is the sample's KITTI object calibration file, the image size is the sample's image's
         (or image_shape when images are not loaded).  The crop keeps the input order, so shuffling the raw cloud first
-        still hands the voxelizer a uniformly shuffled cropped cloud."""
+        still hands the voxelizer a uniformly shuffled cropped cloud.
+        gt_sampler: a gtsample.GTSampler — per sample, after the shuffle and before the augmentation's draw,
+        `gt_sampler.draw(labels, tag)` picks database objects that collide with nothing in the frame; their points are
+        pasted into the (cropped) cloud on the device in front of the augmentation (the scene points inside their boxes
+        go) and the batch's `label` element holds labels + their lines (moved by the augmentation when it is on).  None:
+        nothing is drawn, nothing is launched."""
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise _lib.VoxelnetHipError("DeviceCollate needs a HIP device (no CPU path)")
@@ -87,6 +98,7 @@ class DeviceCollate:
         self.shuffle_points = shuffle_points
         self.fov_calib_dir, self.image_shape = fov_calib_dir, tuple(image_shape)
         self.augment = bool(augment)
+        self.gt_sampler = gt_sampler
         self.stream = pipeline_stream(self.device)      # (shared with the target generator: see voxelize.pipeline_stream)
 
     def launch(self, parts):
@@ -94,12 +106,22 @@ class DeviceCollate:
         handles = []
         if self.augment:
             from . import augment as A
+        if self.gt_sampler is not None:
+            from . import gtsample as G
+        if self.augment or self.gt_sampler is not None:
             parts = list(parts)
         with torch.cuda.stream(self.stream):
             for b, p in enumerate(parts):
                 pcl = p[2]
                 if self.shuffle_points:
                     np.random.shuffle(pcl)                                     # utils.py:35, in place like the reference
+                pasted = None
+                if self.gt_sampler is not None:
+                    pasted = self.gt_sampler.draw(p[3], p[0])                  # host: O(boxes); no points yet
+                    if pasted.lines:
+                        p = parts[b] = (p[0], p[1], p[2], list(p[3]) + pasted.lines, *p[4:])
+                    else:
+                        pasted = None                                          # nothing accepted: no launch, the cloud passes
                 if self.augment:
                     params = A.draw_augmentation(p[3])                         # dataset.py:122-219, host: O(boxes)
                     parts[b] = (p[0], p[1], p[2], A.augment_labels(p[3], params), *p[4:])
@@ -112,6 +134,11 @@ class DeviceCollate:
                     # padded form: no 4-byte read-back per sample (it would stall the host behind everything queued
                     # on this stream); the rows past the device-side count are NaN points, which the voxelizer drops
                     pts, _ = fov_crop_device(pts, P, Tr, R, rows, cols, padded=True)
+                if pasted is not None:
+                    # behind the copy / the crop on this stream; the NaN rows of the padded crop go, NaN rows come out, so
+                    # the count is not read back either; `keep` = the staged table and object points
+                    pts, keep = G.enqueue_gt_paste(pts, pasted)
+                    host = (host, keep)
                 if self.augment:
                     # in place, behind the copy / the crop on this stream; `keep` = the staged box table, referenced
                     # by the handle until the batch is consumed, like `host`
@@ -159,9 +186,9 @@ class DeviceBatcher:
     voxelized on the pipeline's own stream."""
 
     def __init__(self, loader, device="cuda:0", target="Car", shuffle_points=True, fov_calib_dir=None, image_shape=(375, 1242),
-                 augment=False):
+                 augment=False, gt_sampler=None):
         self.loader = loader
-        self.collate = DeviceCollate(device, target, shuffle_points, fov_calib_dir, image_shape, augment)
+        self.collate = DeviceCollate(device, target, shuffle_points, fov_calib_dir, image_shape, augment, gt_sampler=gt_sampler)
 
     def __len__(self):
         return len(self.loader)

@@ -1,0 +1,268 @@
+"""Ground-truth database sampling ("GT-paste", SECOND) as a stage of the input pipeline — the reference has no
+counterpart.  Labelled objects are cut with their points out of the training frames once
+(`GTDatabase`); every training frame then receives a few of them where they collide with nothing (`GTSampler`).  Split
+where the work splits:
+
+  host   (this module, O(boxes) NumPy): the draw, the collision test (`augment.footprints_overlap`), the table, the
+         appended label lines
+  device (csrc/gtsample.hip): the point-in-rotated-box test over N points x up to 128 boxes (`vn_points_in_boxes`) and
+         the paste — drop the scene points inside the pasted boxes, keep the rest in order, append the objects' points,
+         pad with NaN points (`vn_gt_paste`) — on the pipeline's stream between the field-of-view crop and the
+         augmentation.  There is no CPU path for the points.
+
+Table entry (vnGtBox, 64 bytes of float64) of a lidar box (x, y, z, h, w, l, r) in the convention of targets.py:
+    x, y, z0 = z, z1 = z + h, hl = l / 2, hw = w / 2, c = cos(r), s = sin(r)            (NumPy's cos / sin, on the host)
+Inside, for a float32 point widened exactly to float64, evaluated as written without contraction:
+    dx = px - x;  dy = py - y;  u = dx*c + dy*s;  v = -(dx*s) + dy*c
+    inside  <=>  |u| <= hl  and  |v| <= hw  and  pz >= z0  and  pz <= z1                  (inclusive; a NaN anywhere fails)
+
+Objects are pasted at their source position: all frames share the lidar frame.  Stated divergences from SECOND: no
+ground-plane alignment of a pasted object, no check that it is visible from the sensor, the mean calibration as
+everywhere in targets.py, and pasted points come after all scene points (in a voxel shared with surviving scene points
+the scene points win the T slots)."""
+import os
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+
+from . import _lib
+from .augment import footprints_overlap
+from .targets import label_to_gt_box_3d
+
+MAX_BOXES = _lib.VN_GT_MAX_BOXES
+# one entry of the device box table: vnGtBox (include/voxelnet_hip.h), 64 bytes
+BOX_DTYPE = np.dtype([(n, "<f8") for n in ("x", "y", "z0", "z1", "hl", "hw", "c", "s")])
+assert BOX_DTYPE.itemsize == 64
+
+
+def box_table(boxes):
+    """(G,7) float64 lidar boxes (x, y, z, h, w, l, r) -> (G,) BOX_DTYPE table"""
+    b = np.asarray(boxes, dtype=np.float64).reshape(-1, 7)
+    t = np.zeros(b.shape[0], dtype=BOX_DTYPE)
+    t["x"], t["y"] = b[:, 0], b[:, 1]
+    t["z0"], t["z1"] = b[:, 2], b[:, 2] + b[:, 3]
+    t["hl"], t["hw"] = b[:, 5] / 2, b[:, 4] / 2
+    t["c"], t["s"] = np.cos(b[:, 6]), np.sin(b[:, 6])
+    return t
+
+
+def _check_points(points, what):
+    if not (torch.is_tensor(points) and points.is_cuda and points.dtype == torch.float32 and points.dim() == 2
+            and points.shape[1] == 4 and points.is_contiguous()):
+        raise _lib.VoxelnetHipError(f"{what} needs a contiguous (N,4) float32 HIP tensor (there is no CPU path)")
+
+
+def _stage_table(table, dev, what):
+    """-> (device pointer or None, entries, tensors to keep referenced): pinned staging + an asynchronous copy on the
+    current stream, as augment.enqueue_augment_points stages its table"""
+    table = np.ascontiguousarray(table, dtype=BOX_DTYPE).reshape(-1)
+    g = int(table.shape[0])
+    if g > MAX_BOXES:
+        raise _lib.VoxelnetHipError(f"{g} table entries; {what} takes at most {MAX_BOXES}")
+    if g == 0:
+        return None, 0, ()
+    host = torch.from_numpy(table.view(np.uint8)).pin_memory()
+    dev_table = host.to(dev, non_blocking=True)
+    return dev_table.data_ptr(), g, (host, dev_table)
+
+
+def points_in_boxes_device(points, table, counts=True):
+    """points: contiguous (N,4) float32 HIP tensor; table: (G <= 128,) BOX_DTYPE (box_table).  -> (index (N,) int32: the
+    lowest table entry whose box holds the point, else -1; counts (G,) int32: points inside each box, a point inside two
+    boxes counted for both — None with counts=False), device tensors, enqueued on the current stream."""
+    _check_points(points, "points_in_boxes_device")
+    dev, n = points.device, points.shape[0]
+    with _lib.on_device(dev):
+        ptr, g, keep = _stage_table(table, dev, "vn_points_in_boxes")
+        index = torch.empty(n, dtype=torch.int32, device=dev)
+        cnt = torch.empty(g, dtype=torch.int32, device=dev) if counts else None
+        _lib.call("vn_points_in_boxes", points.data_ptr(), n, ptr, g, index.data_ptr(),
+                  cnt.data_ptr() if counts and g else None, _lib.raw_stream())
+    return index, cnt
+
+
+@dataclass
+class GTEntry:
+    """one database object: its class, the tag of the frame it was cut from, its (7,) float64 lidar box, its (P,4)
+    float32 points in the source cloud's order and its source label line, verbatim"""
+    cls: str
+    tag: str
+    box: np.ndarray
+    points: np.ndarray
+    line: str
+
+
+class GTDatabase:
+    def __init__(self, entries=()):
+        self.entries = list(entries)
+
+    def __len__(self):
+        return len(self.entries)
+
+    def __getitem__(self, i):
+        return self.entries[i]
+
+    @classmethod
+    def build(cls, frames, device="cuda:0", classes=("Car",)):
+        """frames: iterable of (tag, cloud, label lines); the cloud — (N,4) float32, a NumPy array or a HIP tensor — is
+        the one the model trains on (for raw sweeps: the cloud after fov_crop_device).  Every line whose type is exactly
+        one of `classes` gives one entry: box = label_to_gt_box_3d([[line]], "", "lidar")[0][0], points = the cloud's
+        rows inside that box in cloud order (overlapping boxes each keep their points; entries with 0 points are
+        stored).  One vn_points_in_boxes launch per frame; a box that shares points with another one is cut with a
+        launch of its own."""
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise _lib.VoxelnetHipError("GTDatabase.build needs a HIP device (there is no CPU path for the points)")
+        classes = tuple(classes)
+        entries = []
+        for tag, cloud, labels in frames:
+            lines = [line for line in labels if line.split() and line.split()[0] in classes]
+            if not lines:
+                continue
+            if len(lines) > MAX_BOXES:
+                raise _lib.VoxelnetHipError(f"{len(lines)} objects in frame {tag}; vn_points_in_boxes takes at most {MAX_BOXES}")
+            boxes = np.stack([label_to_gt_box_3d([[line]], "", "lidar")[0][0] for line in lines])
+            if torch.is_tensor(cloud):
+                pts = cloud.to(device).contiguous()
+            else:
+                pts = torch.from_numpy(np.array(cloud, dtype=np.float32)).to(device)
+            table = box_table(boxes)
+            index, counts = points_in_boxes_device(pts, table)
+            host, index, counts = pts.cpu().numpy(), index.cpu().numpy(), counts.cpu().numpy()
+            for j, line in enumerate(lines):
+                mask = index == j
+                if int(mask.sum()) != int(counts[j]):          # some of its points also lie in an earlier box
+                    mask = points_in_boxes_device(pts, table[j:j + 1], counts=False)[0].cpu().numpy() == 0
+                entries.append(GTEntry(line.split()[0], str(tag), boxes[j].copy(), host[mask].copy(), line))
+        return cls(entries)
+
+    @classmethod
+    def build_from_dataset(cls, dataset, device="cuda:0", classes=("Car",), fov_calib_dir=None, image_shape=(375, 1242)):
+        """every sample (tag, img, pcl, labels, _) of a KITTIDataset-like dataset; fov_calib_dir: raw sweeps — each cloud
+        is cropped to the camera field of view on the device first, as DeviceCollate(fov_calib_dir=...) does"""
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise _lib.VoxelnetHipError("GTDatabase.build_from_dataset needs a HIP device (there is no CPU path for the points)")
+
+        def frames():
+            for i in range(len(dataset)):
+                tag, img, pcl, labels = dataset[i][:4]
+                pts = torch.from_numpy(np.ascontiguousarray(pcl[:, :4], dtype=np.float32)).to(device)
+                if fov_calib_dir is not None:
+                    from .fov import fov_crop_device, load_calib
+                    P, Tr, R = load_calib(os.path.join(fov_calib_dir, str(tag) + ".txt"))
+                    rows, cols = img.shape[:2] if img is not None else tuple(image_shape)
+                    pts = fov_crop_device(pts, P, Tr, R, rows, cols)
+                yield tag, pts, labels
+        return cls.build(frames(), device, classes)
+
+    def save(self, path):
+        """one .npz: concatenated points, offsets, boxes, class / tag / line arrays"""
+        pts = [e.points for e in self.entries]
+        offsets = np.zeros(len(pts) + 1, dtype=np.int64)
+        offsets[1:] = np.cumsum([p.shape[0] for p in pts])
+        with open(path, "wb") as fh:
+            np.savez(fh, points=np.concatenate(pts + [np.zeros((0, 4), np.float32)]).astype(np.float32, copy=False),
+                     offsets=offsets, boxes=np.array([e.box for e in self.entries], dtype=np.float64).reshape(-1, 7),
+                     cls=np.array([e.cls for e in self.entries], dtype=np.str_),
+                     tag=np.array([e.tag for e in self.entries], dtype=np.str_),
+                     line=np.array([e.line for e in self.entries], dtype=np.str_))
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path, allow_pickle=False) as z:
+            pts, off, boxes = z["points"], z["offsets"], z["boxes"]
+            return cls([GTEntry(str(c), str(t), boxes[i].copy(), pts[off[i]:off[i + 1]].copy(), str(line))
+                        for i, (c, t, line) in enumerate(zip(z["cls"], z["tag"], z["line"]))])
+
+
+@dataclass
+class GTSampleParams:
+    """one frame's draw, in acceptance order: `table` (G,) BOX_DTYPE, `points` (M,4) float32 = the accepted objects'
+    points concatenated, `boxes` (G,7) float64, `lines` = their stored label lines (the frame's labels become
+    labels + lines)"""
+    table: np.ndarray
+    points: np.ndarray
+    boxes: np.ndarray
+    lines: list
+
+
+class GTSampler:
+    def __init__(self, db, per_class=None, min_points=5):
+        """per_class: {class: the number of objects of that class a frame is filled up to}, drawn in its order"""
+        self.db = db
+        self.per_class = dict(per_class if per_class is not None else {"Car": 15})
+        self.min_points = int(min_points)
+        self._pools = {c: [i for i, e in enumerate(db.entries) if e.cls == c and e.points.shape[0] >= self.min_points]
+                       for c in self.per_class}
+
+    def draw(self, labels, tag):
+        """labels: the frame's label lines; tag: the frame's (its own objects are never drawn).  From the global
+        np.random state, per class in per_class order: want = max(0, per_class[cls] - #lines of that type); pool = the
+        class's entries with >= min_points points and another tag, in database order; when want == 0 or the pool is
+        empty NO random number is consumed, else exactly one np.random.permutation(len(pool)), whose first `want` are
+        the candidates.  A candidate is accepted when its footprint overlaps no box of the frame (every line, DontCare
+        included) and no candidate accepted earlier, of any class; at most 128 in total.  -> GTSampleParams"""
+        existing = label_to_gt_box_3d([labels], "", "lidar")[0]
+        entries, tag, taken = self.db.entries, str(tag), []
+        for c, target in self.per_class.items():
+            want = max(0, int(target) - sum(1 for line in labels if line.split() and line.split()[0] == c))
+            pool = [i for i in self._pools[c] if entries[i].tag != tag]
+            if want == 0 or not pool:
+                continue
+            for j in np.random.permutation(len(pool))[:want]:
+                if len(taken) >= MAX_BOXES:
+                    break
+                cand = entries[pool[j]]
+                if any(footprints_overlap(cand.box, b) for b in existing) or \
+                        any(footprints_overlap(cand.box, t.box) for t in taken):
+                    continue
+                taken.append(cand)
+        boxes = np.array([e.box for e in taken], dtype=np.float64).reshape(-1, 7)
+        points = np.concatenate([e.points for e in taken] + [np.zeros((0, 4), np.float32)]).astype(np.float32, copy=False)
+        return GTSampleParams(box_table(boxes), points, boxes, [e.line for e in taken])
+
+
+def _paste(points, params, cap):
+    _check_points(points, "gt_paste_device")
+    dev, n = points.device, points.shape[0]
+    obj_host = np.array(params.points, dtype=np.float32).reshape(-1, 4)          # (a copy: the staging needs a writable array)
+    m = int(obj_host.shape[0])
+    cap = n + m if cap is None else int(cap)
+    keep = (points,)
+    with _lib.on_device(dev):
+        ptr, g, staged = _stage_table(params.table, dev, "vn_gt_paste")
+        keep += staged
+        obj_ptr = None
+        if m:
+            host = torch.from_numpy(obj_host).pin_memory()
+            obj = host.to(dev, non_blocking=True)
+            obj_ptr = obj.data_ptr()
+            keep += (host, obj)
+        out = torch.empty((max(cap, 1), 4), dtype=torch.float32, device=dev)
+        count = torch.empty(1, dtype=torch.int32, device=dev)
+        nbytes = _lib.load().vn_gt_paste_workspace_bytes(n)
+        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+        _lib.call("vn_gt_paste", points.data_ptr(), n, ptr, g, obj_ptr, m, out.data_ptr(), cap, count.data_ptr(),
+                  ws.data_ptr(), ws.numel(), _lib.raw_stream())
+    return out[:max(cap, 0)], count, keep + (count, ws)
+
+
+def enqueue_gt_paste(points, params, cap=None):
+    """-> (out: the capacity-sized (cap = N + M by default, 4) buffer — kept scene rows in order, the objects' points,
+    NaN points —, tensors the queued work reads: keep them referenced until the stream has run it).  No host
+    synchronisation: the voxelizer drops the NaN rows like any out-of-range point."""
+    out, _, keep = _paste(points, params, cap)
+    return out, keep
+
+
+def gt_paste_device(points, params, padded=False, cap=None):
+    """points: contiguous (N,4) float32 HIP tensor -> the pasted cloud: the scene rows that are not NaN points and lie in
+    none of params' boxes, in input order, then params.points (a view of the capacity-sized buffer sliced to the count:
+    one device->host read of 4 bytes).  padded=True: no host synchronisation — (the whole buffer, whose rows past the
+    count are NaN points; the count as a device int32 tensor).  Raises VoxelnetHipError for anything but a HIP tensor."""
+    out, count, _ = _paste(points, params, cap)
+    if padded:
+        return out, count
+    return out[:int(count.item())]
