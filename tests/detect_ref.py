@@ -105,9 +105,10 @@ def nms(boxes, mode, nms_thres, post_top_k, cache=None):
     return keep, gap
 
 
-def detect(probs, deltas, anchors, score_thres, pre_top_k, mode, nms_thres, post_top_k):
-    """one sample's maps -> (boxes (k,7) float32, scores (k,) float32): select, decode, nms, gather"""
+def detect(probs, deltas, anchors, score_thres, pre_top_k, mode, nms_thres, post_top_k, cls_name="Car"):
+    """one sample's maps -> (boxes (k,7) float32, scores (k,) float32): select, decode (with the class's anchor height),
+    nms, gather"""
     idx = select(probs, score_thres, pre_top_k)
-    boxes = decode(deltas, anchors, idx)
+    boxes = decode(deltas, anchors, idx, cls_name)
     keep, _ = nms(boxes, mode, nms_thres, post_top_k)
     return boxes[keep], np.asarray(probs, dtype=np.float32).reshape(-1)[idx][keep]

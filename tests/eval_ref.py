@@ -226,28 +226,47 @@ def label_line(name, box, trunc=0.0, occ=0, height=50.0):
             f"{p[0]:.2f} {p[1]:.2f} {p[2]:.2f} {-r - np.pi / 2:.2f}")
 
 
-def make_frame(rng, top_k=20):
-    """-> (det_boxes (n,7) float32, det_scores (n,) float32 distinct in [0.96, 1), label lines)"""
+# what a scene of a class is drawn from: centre ranges (5 m inside the class's range), ground-truth sizes, the sigma of a
+# detection's centre jitter, the false positives' (z, h, w, l) = the class's anchor.  Car: the literals the Car scenes have
+# always used.
+_SCENE = {"Car": dict(x=(5, 65), y=(-35, 35), h=(1.4, 1.8), w=(1.5, 1.8), l=(3.4, 4.5), jitter=0.25, fp=(-1.78, 1.56, 1.6, 3.9))}
+OTHER_NAMES = ("Car", "Van", "Cyclist", "Pedestrian", "Person_sitting", "DontCare")
+
+
+def _scene_cfg(cls_name):
+    if cls_name not in _SCENE:
+        c = CLASS_CFG[cls_name]
+        _SCENE[cls_name] = dict(x=(c["x"][0] + 5, c["x"][1] - 5), y=(c["y"][0] + 5, c["y"][1] - 5),
+                                h=(0.9 * c["h"], 1.1 * c["h"]), w=(0.9 * c["w"], 1.1 * c["w"]), l=(0.9 * c["l"], 1.1 * c["l"]),
+                                jitter=0.1 * c["w"], fp=(c["z"], c["h"], c["w"], c["l"]))
+    return _SCENE[cls_name]
+
+
+def make_frame(rng, top_k=20, cls_name="Car", others=False):
+    """-> (det_boxes (n,7) float32, det_scores (n,) float32 distinct in [0.96, 1), label lines) of class `cls_name`: its
+    ranges, its box sizes, false positives of its anchor size.  others: label lines of OTHER classes (OTHER_NAMES) are mixed
+    in, each on top of a detection or a ground truth, so that a line wrongly taken for the class changes the result."""
+    s = _scene_cfg(cls_name)
     n_gt = int(rng.integers(0, 13))
     lines = []
     for _ in range(n_gt):
-        box = [rng.uniform(5, 65), rng.uniform(-35, 35), rng.uniform(-2, -1), rng.uniform(1.4, 1.8), rng.uniform(1.5, 1.8),
-               rng.uniform(3.4, 4.5), rng.uniform(-np.pi / 2, np.pi / 2)]
+        box = [rng.uniform(*s["x"]), rng.uniform(*s["y"]), rng.uniform(-2, -1), rng.uniform(*s["h"]), rng.uniform(*s["w"]),
+               rng.uniform(*s["l"]), rng.uniform(-np.pi / 2, np.pi / 2)]
         # difficulty fields: every one of the four difficulties sees another set of valid ground truths
-        lines.append(label_line("Car", box, trunc=float(rng.choice([0.0, 0.1, 0.25, 0.4, 0.7])), occ=int(rng.integers(0, 4)),
+        lines.append(label_line(cls_name, box, trunc=float(rng.choice([0.0, 0.1, 0.25, 0.4, 0.7])), occ=int(rng.integers(0, 4)),
                                 height=float(rng.uniform(15, 80))))
-    gt = label_to_gt_box_3d([lines], "Car", "lidar")[0]          # the boxes as the two-decimal label text gives them back
+    gt = label_to_gt_box_3d([lines], cls_name, "lidar")[0]          # the boxes as the two-decimal label text gives them back
     dets = []
     for g in gt:
         for _ in range(int(rng.choice([0, 1, 2], p=[0.2, 0.6, 0.2]))):
             d = g.copy()
-            d[0:2] += rng.normal(0, 0.25, 2)
+            d[0:2] += rng.normal(0, s["jitter"], 2)
             d[2] += rng.normal(0, 0.1)
             d[6] += rng.normal(0, 0.1)
             d[3:6] *= rng.uniform(0.93, 1.07, 3)
             dets.append(d)
     for _ in range(int(rng.integers(0, 5))):          # false positives of anchor size
-        dets.append(np.array([rng.uniform(5, 65), rng.uniform(-35, 35), -1.78, 1.56, 1.6, 3.9, rng.choice([0.0, np.pi / 2])]))
+        dets.append(np.array([rng.uniform(*s["x"]), rng.uniform(*s["y"]), *s["fp"], rng.choice([0.0, np.pi / 2])]))
     if dets:
         dets = [dets[i] for i in rng.permutation(len(dets))][:top_k]
     boxes = np.array(dets, dtype=np.float64).reshape(-1, 7).astype(np.float32)
@@ -256,9 +275,17 @@ def make_frame(rng, top_k=20):
     ticks = rng.choice(40000, size=n, replace=False)
     scores = (np.float32(0.96) + ticks.astype(np.float32) * np.float32(2.0 ** -20)).astype(np.float32)
     assert len(set(scores.tolist())) == n and (scores < 1).all()
+    if others:
+        accept = CLASS_CFG[cls_name]["accept"]
+        spots = [b.astype(np.float64) for b in boxes] + [g for g in gt]
+        for name in OTHER_NAMES:
+            if name in accept or not spots or rng.random() < 0.4:
+                continue
+            box = spots[int(rng.integers(0, len(spots)))]
+            lines.insert(int(rng.integers(0, len(lines) + 1)), label_line(name, box, occ=int(rng.integers(0, 3))))
     return boxes, scores, lines
 
 
-def make_scene(seed, n_frames=64, top_k=20):
+def make_scene(seed, n_frames=64, top_k=20, cls_name="Car", others=False):
     rng = np.random.default_rng(seed)
-    return [make_frame(rng, top_k) for _ in range(n_frames)]
+    return [make_frame(rng, top_k, cls_name, others) for _ in range(n_frames)]

@@ -12,7 +12,12 @@ vn_rpn_predict: bit-equal.
 
 Stand-up mode and NaN fields: csrc/predict.hip's fminf / fmaxf drop a NaN corner (the rectangle comes out empty, IoU 0),
 NumPy's min / max keep it (IoU NaN).  vn_box_nms restates the kernel verbatim, so the hand-made stand-up frames use
-infinite and zero-width rows (on which both agree: a NaN IoU suppresses), and rows with a NaN field in rotated mode."""
+infinite and zero-width rows (on which both agree: a NaN IoU suppresses), and rows with a NaN field in rotated mode.
+
+Scene "ped": the full Pedestrian anchor grid (N = 24,000 = 93 * 256 + 192) with tests/label_cases.py's clustered maps and
+BoxDecoder("Pedestrian"): anchors of 0.6 x 0.8 and the class's anchor height 1.73 in the decoded z (a decoder with Car's 1.56
+fails the selection test: the two differ by far more than the decode bar, asserted there).  The reference for that class is
+the Car-pinned restatement with the class's constants."""
 import functools
 
 import numpy as np
@@ -20,16 +25,19 @@ import pytest
 import torch
 
 import detect_ref as D
+import label_cases as L
 from oracle import targets as ot
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 MARGIN = 1e-7
 MODES = {"standup": D.STANDUP, "rotated": D.ROTATED}
-# scene -> (slice of generate_anchors("Car"), score_thres, pre_top_k)
+# scene -> (slice of the class's generate_anchors, score_thres, pre_top_k)
 SCENES = {"dense": ((slice(0, 24), slice(0, 20)), 0.25, 512),
           "spread": ((slice(None, None, 4), slice(None, None, 4)), 0.70, 1024),
-          "wide": ((slice(None, None, 2), slice(None, None, 2)), 0.70, 4096)}
+          "wide": ((slice(None, None, 2), slice(None, None, 2)), 0.70, 4096),
+          "ped": ((slice(None), slice(None)), 0.50, 512)}
+SCENE_CLASS = {"ped": "Pedestrian"}          # every other scene: "Car"
 SEEDS = (5, 6)
 
 
@@ -44,19 +52,21 @@ def _u32(a):
 @functools.lru_cache(maxsize=None)
 def _anchors(scene):
     sl = SCENES[scene][0]
-    return np.ascontiguousarray(ot.generate_anchors("Car")[sl[0], sl[1]])
+    return np.ascontiguousarray(ot.generate_anchors(SCENE_CLASS.get(scene, "Car"))[sl[0], sl[1]])
 
 
 @functools.lru_cache(maxsize=None)
 def _decoder(scene):
     from voxelnet_amd.predict import BoxDecoder
-    return BoxDecoder("Car", DEV, anchors=None if scene == "full" else _anchors(scene))
+    return BoxDecoder(SCENE_CLASS.get(scene, "Car"), DEV, anchors=None if scene in ("full", "ped") else _anchors(scene))
 
 
 @functools.lru_cache(maxsize=None)
 def _maps(scene, seed):
     """tests/test_gpu_predict.py's random maps on the scene's anchors: B = 2"""
     h, w = (200, 176) if scene == "full" else _anchors(scene).shape[:2]
+    if scene == "ped":          # clustered candidates: 96 neighbouring anchors at 0.96.., the rest below 0.9
+        return L.clustered_maps((h, w), seed)
     rng = np.random.default_rng(seed)
     probs = rng.random((2, 2, h, w)).astype(np.float32)
     deltas = (rng.standard_normal((2, 14, h, w)) * 0.3).astype(np.float32)
@@ -72,7 +82,7 @@ def _candidates(scene, seed):
     return tuple(t.cpu().numpy() for t in out)
 
 
-def _check_selection(probs, deltas, anchors, thres, pre, got):
+def _check_selection(probs, deltas, anchors, thres, pre, got, cls_name="Car"):
     boxes, scores, idx, counts = got
     B = probs.shape[0]
     assert boxes.shape == (B, pre, 7) and scores.shape == (B, pre) and idx.shape == (B, pre) and counts.shape == (B,)
@@ -82,7 +92,7 @@ def _check_selection(probs, deltas, anchors, thres, pre, got):
         assert counts[b] == n, (b, counts[b], n)
         assert np.array_equal(idx[b, :n], want), b
         assert np.array_equal(_u32(scores[b, :n]), _u32(probs[b].reshape(-1)[want])), b
-        np.testing.assert_allclose(boxes[b, :n], D.decode(deltas[b], anchors, want), rtol=2.4e-7, atol=1e-6)
+        np.testing.assert_allclose(boxes[b, :n], D.decode(deltas[b], anchors, want, cls_name), rtol=2.4e-7, atol=1e-6)
         assert (boxes[b, n:] == 0).all() and (scores[b, n:] == 0).all() and (idx[b, n:] == 0).all()          # untouched rows
     return counts
 
@@ -93,9 +103,17 @@ def _check_selection(probs, deltas, anchors, thres, pre, got):
 def test_selection_matches_reference(scene, seed):
     probs, deltas = _maps(scene, seed)
     _, thres, pre = SCENES[scene]
-    counts = _check_selection(probs, deltas, _anchors(scene), thres, pre, _candidates(scene, seed))
+    cls = SCENE_CLASS.get(scene, "Car")
+    counts = _check_selection(probs, deltas, _anchors(scene), thres, pre, _candidates(scene, seed), cls)
     n_cand = (probs.reshape(2, -1) >= np.float32(thres)).sum(axis=1)
     assert (counts == pre).all() and (n_cand > pre).all()          # the cut really truncates
+    if cls != "Car":
+        # the class's anchor height is in the decoded z: with Car's 1.56 the same rows lie far outside the decode bar
+        assert _decoder(scene).anchor_h == ot.CLASSES[cls]["h"] == 1.73 and _anchors(scene).shape == (100, 120, 2, 7)
+        for b in range(2):
+            want = D.select(probs[b], thres, pre)
+            z, z_car = (D.decode(deltas[b], _anchors(scene), want, c)[:, 2].astype(np.float64) for c in (cls, "Car"))
+            assert (np.abs(z - z_car) > 100 * (1e-6 + 2.4e-7 * np.abs(z))).mean() > 0.9
 
 
 def test_selection_pool_larger_than_the_candidates_and_empty():
@@ -181,7 +199,10 @@ def test_box_nms_matches_reference(scene, seed, mode):
     for thr in (0.1, 0.5):
         for post in (64, 20):
             kept = _check_nms(boxes, counts, mode, thr, post, caches)
-            if scene != "dense":
+            if scene == "ped":                       # the clustered candidates lead the pool: the walk suppresses among them
+                lead = [len(D.nms(boxes[b, :96], MODES[mode], thr, 96, caches[b])[0]) for b in range(2)]
+                assert all(k < 96 for k in lead) and all(k >= 1 for k in kept)
+            elif scene != "dense":
                 assert kept == [post, post]          # spread and wide hit the cap
             elif thr == 0.1 and post == 64:
                 assert all(k < 64 for k in kept)     # dense at 0.1: the whole pool is walked

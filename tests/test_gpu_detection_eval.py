@@ -372,6 +372,44 @@ def test_average_precision_r11_and_other_thresholds():
             assert abs(got[m][d] - want[m][d]) <= 1e-12
 
 
+@functools.lru_cache(maxsize=None)
+def _class_scene(cls):
+    """16 frames of the class (its ranges, box sizes, anchor-sized false positives) with label lines of OTHER classes
+    mixed in on top of detections and ground truths -> (scene, the reference's result, the reference's result with the
+    other classes' lines taken out, per-frame IoU tables).  The reference is tests/eval_ref.py with the class's 0.5."""
+    scene = R.make_scene(1, n_frames=16, cls_name=cls, others=True)
+    ref, own = R.RefEvaluator(cls), R.RefEvaluator(cls)
+    frames, n_other = [], 0
+    for det, scores, lines in scene:
+        r = ref.add_frame(det, scores, lines)
+        mine = [l for l in lines if l.split()[0] == cls]
+        n_other += len(lines) - len(mine)
+        own.add_frame(det, scores, mine)
+        frames.append({"iou": np.stack([r["iou"]["bev"], r["iou"]["3d"]])})
+    assert n_other >= 16
+    return scene, ref.compute(), own.compute(), frames
+
+
+@pytest.mark.parametrize("batch", [2, 7])
+@pytest.mark.parametrize("cls", ["Pedestrian", "Cyclist"])
+def test_average_precision_other_classes(cls, batch):
+    """DetectionEvaluator(cls) with its default threshold (IOU_THRES: 0.5) against RefEvaluator(cls); the Car, Van,
+    Person_sitting, DontCare, ... lines in the labels are dropped: the result is the one without them"""
+    from voxelnet_amd.evaluate import IOU_THRES, DetectionEvaluator
+    scene, ref, ref_own, frames = _class_scene(cls)
+    assert IOU_THRES[cls] == R.THRES[cls] == 0.5 and len(scene) == 16
+    closest = _assert_margin(frames, (0.5,))
+    ev = DetectionEvaluator(cls, DEV)
+    assert ev.iou_thres == (0.5, 0.5)
+    _feed(ev, scene, batch, True)
+    got = ev.compute()
+    print(f"AP {cls} batch {batch}: closest IoU to 0.5 {closest:.2e}; " + ", ".join(
+        f"{m}/{d} {got[m][d]:.6f}" for m in ("bev", "3d") for d in R.DIFFS) + f"; n_gt {got['n_gt']}, n_det {got['n_det']}")
+    _assert_same_result(got, ref)
+    _assert_same_result(got, ref_own)
+    assert all(0 < got[m][d] < 1 for m in ("bev", "3d") for d in R.DIFFS)
+
+
 # ------------------------------------------------------------------------------- decode_device, RPN3D.evaluate
 @pytest.mark.parametrize("which", ["fixture maps", (5, False), (6, True)])
 def test_decode_device_is_call_without_the_copies(which):

@@ -1015,9 +1015,13 @@ class RPN3D(nn.Module):
         gen = self.__dict__.get("_targets")
         if gen is None or gen.device != torch.device(device):
             gen = TargetGenerator(self.cls_name, device)
-            if tuple(gen.shape) != tuple(self.rpn_output_shape):
+            # the maps the network EMITS, not rpn_output_shape: for Pedestrian / Cyclist that attribute repeats the anchor
+            # grid (100 x 120, as the reference has it) while block 1 does not stride and the maps are 200 x 240
+            g, s = grid_config(self.cls_name), self.middle_rpn._block1_stride
+            emitted = (g.H // s, g.W // s)
+            if tuple(gen.shape) != emitted:
                 # (the reference has the same mismatch for Pedestrian / Cyclist: its loss cannot run)
-                raise _lib.VoxelnetHipError(f"anchor grid {tuple(gen.shape)} != RPN output {tuple(self.rpn_output_shape)}")
+                raise _lib.VoxelnetHipError(f"anchor grid {tuple(gen.shape)} != RPN output {emitted}")
             self.__dict__["_targets"] = gen
             self.anchors = gen.anchors
         return gen
