@@ -858,6 +858,46 @@ size_t vn_clip_sgd_workspace_bytes(int32_t n_chunks);
 int vn_clip_sgd(const vnParamChunk *chunks, int32_t n_chunks, float max_norm, float lr, int32_t scale_grads,
                 void *workspace, size_t workspace_bytes, float *total_norm, vnStream stream);
 
+/* ---- optimizer tail with AdamW in SGD's place (voxelnet/train.py:153-154; what every successor trains with) ----
+ * torch.nn.utils.clip_grad_norm_(parameters, max_norm) followed by torch.optim.AdamW's update (torch/optim/adam.py
+ * _single_tensor_adam with decoupled_weight_decay, amsgrad = False, maximize = False), in two launches:
+ *   total = sqrt(sum |g|^2) over EVERY chunk, whatever its slot;  coef = min(1, max_norm / (total + 1e-6))  (NaN stays NaN)
+ *   per element, with the values of its chunk's slot:
+ *     g' = g * coef;  p *= 1 - lr * wd;  m += (g' - m) * (1 - beta1);  v = beta2 * v + (1 - beta2) * g'^2
+ *     p -= (lr / (1 - beta1^t)) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
+ * `chunks` is a DEVICE array built once for a fixed set of fp32 tensors: every (parameter, gradient, exp_avg, exp_avg_sq)
+ * quadruple cut into pieces of at most VN_OPT_CHUNK elements, each naming the hyperparameter slot it takes; the kernel
+ * clamps that index into [0, n_slots).  `hyper` is HOST memory, read during the call and not afterwards: lr, the betas
+ * and the step count can change from call to call (schedulers) without touching the device table.  The slot's five
+ * floats are widened to the double with the shortest decimal form that rounds to the float (0.999f means 0.999, not
+ * 0.99900001287...), 1 - beta, 1 - lr * wd and 1 - beta^t are taken in double, and the results go to the kernel by value.
+ * scale_grads != 0 also stores g' (what clip_grad_norm_ leaves behind); total_norm (device, may be NULL) receives the norm
+ * before clipping.  Sums as in vn_clip_sgd: fp32 per thread, one fp32 partial per chunk, added in double in one fixed
+ * order by every workgroup of the second launch — no atomics, bit-identical from run to run.
+ * VN_EINVAL (before any HIP call): a NULL chunks / hyper / workspace, n_chunks <= 0, max_norm <= 0 or NaN, n_slots outside
+ * 1..VN_OPT_MAX_SLOTS, a slot (of the first n_slots) with a beta outside [0,1), eps < 0, lr < 0, weight_decay < 0, step < 1
+ * or a NaN; VN_EWORKSPACE: workspace_bytes < vn_clip_adamw_workspace_bytes(n_chunks).  Asynchronous. */
+#define VN_OPT_MAX_SLOTS 8
+typedef struct vnAdamChunk {
+    float *param;
+    float *grad;
+    float *exp_avg;
+    float *exp_avg_sq;
+    int32_t n;          /* elements in this piece, 1..VN_OPT_CHUNK */
+    int32_t slot;       /* index into vnAdamHyper.slot */
+} vnAdamChunk;
+typedef struct vnAdamSlot {
+    float lr, beta1, beta2, eps, weight_decay;
+    int32_t step;       /* t >= 1: the step being taken */
+} vnAdamSlot;
+typedef struct vnAdamHyper {
+    int32_t n_slots;
+    vnAdamSlot slot[VN_OPT_MAX_SLOTS];
+} vnAdamHyper;
+size_t vn_clip_adamw_workspace_bytes(int32_t n_chunks);
+int vn_clip_adamw(const vnAdamChunk *chunks, int32_t n_chunks, const vnAdamHyper *hyper, float max_norm,
+                  int32_t scale_grads, void *workspace, size_t workspace_bytes, float *total_norm, vnStream stream);
+
 /* ---- RPN training targets (voxelnet/utils.py:376-473 generate_targets, :344-373 bbox_iou, :213-227
  * anchor_to_standup_box2d; called by RPN3D.forward, voxelnet/model.py:309) -------------------------------
  * Per sample b: gt_count[b] ground-truth boxes in lidar coordinates, gt [B,max_gt,7] = (x,y,z,h,w,l,r) float64 and

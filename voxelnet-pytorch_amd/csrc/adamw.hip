@@ -1,0 +1,196 @@
+// Optimizer tail of the train step with AdamW in SGD's place (train.py:153-154 is clip_grad_norm_(parameters, 5) +
+// SGD.step(); SECOND, PointPillars and what followed train with Adam / AdamW): clip_grad_norm_(parameters, max_norm)
+// followed by torch.optim.AdamW's single-tensor update (torch/optim/adam.py, _single_tensor_adam with decoupled weight
+// decay, amsgrad = False, maximize = False), as TWO launches over a chunk table like vn_clip_sgd (optim.hip) instead of
+// torch's multi-tensor launches over the 104 parameter tensors.
+//   total = sqrt(sum_i |g_i|^2);  coef = min(1, max_norm / (total + 1e-6));  g' = g * coef
+//   p *= 1 - lr * wd;  m += (g' - m) * (1 - beta1);  v = beta2 * v + (1 - beta2) * g'^2
+//   p -= (lr / (1 - beta1^t)) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
+// Every chunk names one of at most VN_OPT_MAX_SLOTS hyperparameter slots (parameter group x step count); the slots'
+// scalars are worked out in double on the host at every call and travel in the kernel arguments, so a scheduler's new lr
+// or beta1 costs no device table rebuild and no copy.  HBM-bound: 4 B read per element in the first pass, 28 B (g, p, m, v
+// read; p, m, v written; +4 when the scaled gradients are written back) in the second.
+// Sums as in optim.hip: fp32 per thread -> one fp32 partial per chunk -> every workgroup of the second kernel adds the
+// partials in double in the same fixed order (deterministic, no atomics, no third launch).
+#include "common.h"
+
+#include <charconv>
+#include <cmath>
+
+namespace {
+
+constexpr int ADAM_THREADS = 256;
+
+struct AdamSlotK {          // one slot as the kernel wants it
+    float neg_step_size;    // -lr / (1 - beta1^t)
+    float decay;            // 1 - lr * wd
+    float omb1;             // 1 - beta1
+    float beta2, omb2;      // beta2, 1 - beta2
+    float inv_bc2_sqrt;     // 1 / (float)sqrt(1 - beta2^t), the reciprocal taken in float as torch's division by a scalar does
+    float eps;
+};
+struct AdamArgs {
+    AdamSlotK slot[VN_OPT_MAX_SLOTS];
+    int n_slots;
+};
+
+__device__ __forceinline__ bool aligned16(const void *a, const void *b, const void *c, const void *d) {
+    return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) |
+             reinterpret_cast<uintptr_t>(d)) & 15) == 0;
+}
+
+__global__ void __launch_bounds__(ADAM_THREADS) k_adam_sumsq(const vnAdamChunk *__restrict__ chunks, float *__restrict__ partial) {
+    const vnAdamChunk c = chunks[blockIdx.x];
+    const float *__restrict__ g = c.grad;
+    float s = 0.f;
+    if ((reinterpret_cast<uintptr_t>(g) & 15) == 0) {
+        const int n4 = c.n >> 2;
+        for (int i = threadIdx.x; i < n4; i += ADAM_THREADS) {
+            const float4 v = reinterpret_cast<const float4 *>(g)[i];
+            s += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
+        }
+        for (int i = (n4 << 2) + threadIdx.x; i < c.n; i += ADAM_THREADS) s += g[i] * g[i];
+    } else {
+        for (int i = threadIdx.x; i < c.n; i += ADAM_THREADS) s += g[i] * g[i];
+    }
+    __shared__ float red[ADAM_THREADS / 64];
+    s = vn_wave_sum(s);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float t = 0.f;
+        for (int w = 0; w < ADAM_THREADS / 64; ++w) t += red[w];
+        partial[blockIdx.x] = t;
+    }
+}
+
+// one element: g is scaled in place (the caller stores it when scale_grads is set).  The roundings are those of torch's
+// device kernels for the same update, one kernel per line there: mul_ | lerp_ (a + w * (b - a), contracted; the other
+// form from weight 0.5 on) | mul_, addcmul_ (a + alpha * b * c, the last product contracted into the sum) | sqrt, a
+// division by a scalar done as a product with its float reciprocal, add_ | addcdiv_ (a + alpha * (b / c), contracted).  The
+// build has contraction off (Makefile), hence the explicit fmaf.  Measured against torch on the MI355X: exp_avg comes out
+// equal bit for bit (unclipped gradients), exp_avg_sq and p still differ in the last bit for a part of the elements
+// (DESIGN.md section 1d); what this buys is the whole detector's second step, whose gradient norm equals the torch tail's
+// bit for bit with this form and was 1.9e-4 off with the uncontracted one.
+__device__ __forceinline__ void adam_element(float &p, float &g, float &m, float &v, float coef, const AdamSlotK &h) {
+    g *= coef;
+    p *= h.decay;
+    const float d = g - m;
+    m = h.omb1 < 0.5f ? fmaf(h.omb1, d, m) : fmaf(-d, 1.f - h.omb1, g);
+    v = fmaf(h.omb2 * g, g, h.beta2 * v);
+    const float denom = sqrtf(v) * h.inv_bc2_sqrt + h.eps;
+    p = fmaf(h.neg_step_size, m / denom, p);
+}
+
+__global__ void __launch_bounds__(ADAM_THREADS) k_adam_update(const vnAdamChunk *__restrict__ chunks, int n_chunks,
+                                                              const float *__restrict__ partial, float max_norm,
+                                                              const AdamArgs args, int scale_grads,
+                                                              float *__restrict__ total_norm) {
+    // every workgroup recomputes the (same) total from the partials: n_chunks * 4 B from L2
+    double s = 0.0;
+    for (int i = threadIdx.x; i < n_chunks; i += ADAM_THREADS) s += (double)partial[i];
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    __shared__ double red[ADAM_THREADS / 64];
+    __shared__ float coef_s;
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = 0.0;
+        for (int w = 0; w < ADAM_THREADS / 64; ++w) t += red[w];
+        const float total = (float)sqrt(t);
+        const float coef = max_norm / (total + 1e-6f);         // torch.nn.utils.clip_grad_norm_
+        coef_s = coef < 1.f ? coef : 1.f;                        // clamp(max=1.0); NaN stays NaN as in torch
+        if (coef != coef) coef_s = coef;
+        if (blockIdx.x == 0 && total_norm) *total_norm = total;
+    }
+    __syncthreads();
+    const float coef = coef_s;
+    const vnAdamChunk c = chunks[blockIdx.x];
+    // the slot index is device data: clamped, never trusted
+    const int si = c.slot < 0 ? 0 : (c.slot >= args.n_slots ? args.n_slots - 1 : c.slot);
+    const AdamSlotK h = args.slot[si];
+    float *__restrict__ p = c.param;
+    float *__restrict__ g = c.grad;
+    float *__restrict__ m = c.exp_avg;
+    float *__restrict__ v = c.exp_avg_sq;
+    int done = 0;
+    if (aligned16(p, g, m, v)) {
+        const int n4 = c.n >> 2;
+        for (int i = threadIdx.x; i < n4; i += ADAM_THREADS) {
+            float4 gv = reinterpret_cast<const float4 *>(g)[i];
+            float4 pv = reinterpret_cast<float4 *>(p)[i];
+            float4 mv = reinterpret_cast<float4 *>(m)[i];
+            float4 vv = reinterpret_cast<float4 *>(v)[i];
+            adam_element(pv.x, gv.x, mv.x, vv.x, coef, h);
+            adam_element(pv.y, gv.y, mv.y, vv.y, coef, h);
+            adam_element(pv.z, gv.z, mv.z, vv.z, coef, h);
+            adam_element(pv.w, gv.w, mv.w, vv.w, coef, h);
+            reinterpret_cast<float4 *>(p)[i] = pv;
+            reinterpret_cast<float4 *>(m)[i] = mv;
+            reinterpret_cast<float4 *>(v)[i] = vv;
+            if (scale_grads) reinterpret_cast<float4 *>(g)[i] = gv;
+        }
+        done = n4 << 2;
+    }
+    // the chunk's tail, or all of it when a pointer is off a 16-byte boundary (a tensor inside a flat buffer)
+    for (int i = done + threadIdx.x; i < c.n; i += ADAM_THREADS) {
+        float gv = g[i], pv = p[i], mv = m[i], vv = v[i];
+        adam_element(pv, gv, mv, vv, coef, h);
+        p[i] = pv;
+        m[i] = mv;
+        v[i] = vv;
+        if (scale_grads) g[i] = gv;
+    }
+}
+
+// The ABI carries the hyperparameters as floats; the caller meant a decimal (0.9, 0.999, 1e-8).  (double)0.999f is
+// 0.99900001287..., whose 1 - beta2 is off by 1.3e-5 of itself — far above the rounding of the update.  The shortest
+// decimal form that rounds to the float (std::to_chars) read back as a double gives 0.999 again; a value that needs all
+// of a double's digits loses at most half a float ulp, as any float would.
+double widen(float x) {
+    char buf[32];
+    const std::to_chars_result r = std::to_chars(buf, buf + sizeof(buf), x);
+    double d = (double)x;
+    if (r.ec == std::errc()) std::from_chars(buf, r.ptr, d);
+    return d;
+}
+
+}  // namespace
+
+extern "C" size_t vn_clip_adamw_workspace_bytes(int32_t n_chunks) {
+    if (n_chunks <= 0) return 0;
+    return vn_align(sizeof(float) * (size_t)n_chunks);
+}
+
+extern "C" int vn_clip_adamw(const vnAdamChunk *chunks, int32_t n_chunks, const vnAdamHyper *hyper, float max_norm,
+                             int32_t scale_grads, void *workspace, size_t workspace_bytes, float *total_norm,
+                             vnStream stream) {
+    VN_CHECK_ARG(chunks && hyper && workspace && n_chunks > 0 && max_norm > 0.f);
+    VN_CHECK_ARG(hyper->n_slots >= 1 && hyper->n_slots <= VN_OPT_MAX_SLOTS);
+    AdamArgs args = {};
+    args.n_slots = hyper->n_slots;
+    for (int i = 0; i < hyper->n_slots; ++i) {
+        const vnAdamSlot &s = hyper->slot[i];
+        // (written so that a NaN fails every test)
+        VN_CHECK_ARG(s.beta1 >= 0.f && s.beta1 < 1.f && s.beta2 >= 0.f && s.beta2 < 1.f);
+        VN_CHECK_ARG(s.eps >= 0.f && s.lr >= 0.f && s.weight_decay >= 0.f && s.step >= 1);
+        const double lr = widen(s.lr), b1 = widen(s.beta1), b2 = widen(s.beta2), wd = widen(s.weight_decay);
+        const double bc1 = 1.0 - std::pow(b1, (double)s.step), bc2 = 1.0 - std::pow(b2, (double)s.step);
+        AdamSlotK &k = args.slot[i];
+        k.neg_step_size = (float)(-(lr / bc1));
+        k.decay = (float)(1.0 - lr * wd);
+        k.omb1 = (float)(1.0 - b1);
+        k.beta2 = (float)b2;
+        k.omb2 = (float)(1.0 - b2);
+        k.inv_bc2_sqrt = 1.f / (float)std::sqrt(bc2);
+        k.eps = s.eps;
+    }
+    if (workspace_bytes < vn_clip_adamw_workspace_bytes(n_chunks)) return VN_EWORKSPACE;
+    hipStream_t st = vn_stream(stream);
+    float *partial = static_cast<float *>(workspace);
+    k_adam_sumsq<<<n_chunks, ADAM_THREADS, 0, st>>>(chunks, partial);
+    VN_LAUNCH_STATUS();
+    k_adam_update<<<n_chunks, ADAM_THREADS, 0, st>>>(chunks, n_chunks, partial, max_norm, args, scale_grads, total_norm);
+    VN_LAUNCH_STATUS();
+    return VN_OK;
+}

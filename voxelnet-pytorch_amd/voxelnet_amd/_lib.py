@@ -84,6 +84,21 @@ class VnParamChunk(ctypes.Structure):
     _fields_ = [("param", c_vp), ("grad", c_vp), ("n", c_i32), ("reserved", c_i32)]
 
 
+VN_OPT_MAX_SLOTS = 8
+
+
+class VnAdamChunk(ctypes.Structure):   # vnAdamChunk (vn_clip_adamw): one row of the device chunk table, 40 bytes
+    _fields_ = [("param", c_vp), ("grad", c_vp), ("exp_avg", c_vp), ("exp_avg_sq", c_vp), ("n", c_i32), ("slot", c_i32)]
+
+
+class VnAdamSlot(ctypes.Structure):
+    _fields_ = [("lr", c_f32), ("beta1", c_f32), ("beta2", c_f32), ("eps", c_f32), ("weight_decay", c_f32), ("step", c_i32)]
+
+
+class VnAdamHyper(ctypes.Structure):   # vnAdamHyper: HOST memory, read during the call
+    _fields_ = [("n_slots", c_i32), ("slot", VnAdamSlot * VN_OPT_MAX_SLOTS)]
+
+
 class VnStep(ctypes.Structure):       # vnStep (vn_net_step): field for field
     _fields_ = [("feature", c_vp), ("coord", c_vp), ("K", c_i64), ("T", c_i32), ("bn_momentum", c_f32), ("bn_eps", c_f32),
                 ("vfe", VnVfeWeights), ("vfe_grads", VnVfeGrads), ("vfe_ws", c_vp), ("vfe_ws_bytes", c_sz),
@@ -263,6 +278,8 @@ SIGNATURES = {
                               c_vp, c_vp, c_sz, c_vp]),
     "vn_clip_sgd_workspace_bytes": (c_sz, [c_i32]),
     "vn_clip_sgd": (c_i32, [c_vp, c_i32, c_f32, c_f32, c_i32, c_vp, c_sz, c_vp, c_vp]),
+    "vn_clip_adamw_workspace_bytes": (c_sz, [c_i32]),
+    "vn_clip_adamw": (c_i32, [c_vp, c_i32, _P(VnAdamHyper), c_f32, c_i32, c_vp, c_sz, c_vp, c_vp]),
 }
 
 _lib = None

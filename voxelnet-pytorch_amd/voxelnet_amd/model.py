@@ -1190,13 +1190,13 @@ class RPN3D(nn.Module):
         return sc
 
     def _step_fused_ok(self, mode, optimizer):
-        from .optim import ClipSGD
+        from .optim import ClipAdamW, ClipSGD
         red = self.grad_reducer
         return (self._native_ok(mode) and self.training and self.direct_grads and self.overlap_wgrad and self.sparse_first_layer
                 and torch.is_grad_enabled() and self.target_fn is None and E.SECTIONS is None
                 and not (int(self.grad_storage) & 16)
                 and (red is None or (red.comm_stream is not None and HEADS_W in _grad_views(self)))
-                and (optimizer is None or isinstance(optimizer, ClipSGD)))
+                and (optimizer is None or isinstance(optimizer, (ClipSGD, ClipAdamW))))
 
     def train_step(self, x, device, optimizer=None, targets=None):
         """One training step — `out = model(x, device); out[2].backward(); clip_grad_norm_; optimizer.step()`
@@ -1205,9 +1205,11 @@ class RPN3D(nn.Module):
         the engine's hand-over to its device thread, ~15 tensor allocations, ~12 ctypes calls).
         Returns the tuple forward() returns (tensors without an autograd graph: the backward has already run); the
         parameters' .grad are set as backward() leaves them.  optimizer: a ClipSGD (its update runs inside the call when no
-        gradient reducer is attached, after the reducer's exchange otherwise) or None (no update).
+        gradient reducer is attached, after the reducer's exchange otherwise), a ClipAdamW (the call runs without a parameter
+        update and optimizer.step() follows on the same stream, after the reducer's exchange) or None (no update).
         Whatever the fused call does not cover — per-layer orchestration, eval mode, target_fn, gradient accumulation, a
         reducer without a communication stream, bench.py's per-section timer — takes the separate calls, same results."""
+        from .optim import ClipSGD
         mode = _mode()
         fused = self._step_fused_ok(mode, optimizer)
         plist = self._flat_params() if fused else None
@@ -1297,7 +1299,8 @@ class RPN3D(nn.Module):
                 grads = (views, [views[n] for n, _ in self._named_params_in_flat_order()])
                 self.__dict__["_mg_cache"] = grads
             out_grads = grads[1]
-            inside = optimizer is not None and red is None and optimizer._step_table(plist, out_grads)
+            # (only ClipSGD's update is part of vnStep; a ClipAdamW steps after the call)
+            inside = isinstance(optimizer, ClipSGD) and red is None and optimizer._step_table(plist, out_grads)
             if inside:
                 a.chunks, a.n_chunks = optimizer._table.data_ptr(), optimizer._n_chunks
                 a.max_norm, a.lr, a.scale_grads = optimizer.max_norm, optimizer.lr, int(optimizer.scale_grads)
