@@ -569,7 +569,7 @@ int vn_net_backward(vnNet *net, const vnNetConfig *cfg, const vnLayerParams *lay
  *   side:  [wait stream]  counters += 1 | vn_net_prepare phase 1 | heads' parameters -> heads_w / heads_b | vn_net_prepare phase 2 |
  *          [wait targets_stream] vn_rpn_loss_norm | ... | [wait the pass] vn_rpn_loss_finalize -> loss5
  *   main:  vn_vfe_fwd (bf16 mode: vn_vfe_fwd_rows, whose last pass writes vw_rows too: no vn_cast_rows launch) |
- *          vn_net_forward | [wait the normalisers] vn_rpn_loss_fwd_bwd_rows (g_loss): ONE launch between the heads and their
+ *          vn_net_forward | [wait the normalisers] vn_rpn_loss_spec_fwd_bwd_rows (g_loss, loss_spec): ONE launch between the heads and their
  *          backward, which also leaves the heads' gradient rows in the arena (no vn_heads_bwd launch) |
  *          vn_net_backward(0..24, defer_join) | vn_vfe_bwd | [wait side] | vn_clip_sgd
  * Same arithmetic and same results as those calls (tests/test_gpu_step.py: bit-identical); what it saves is the host's
@@ -577,6 +577,15 @@ int vn_net_backward(vnNet *net, const vnNetConfig *cfg, const vnLayerParams *lay
  * heads_w / heads_b, d_prob / d_reg, the three workspaces) need only live until the step has run.
  * Requires cfg->sparse_first, cfg->training and a side stream (VN_EUNSUPPORTED / VN_EINVAL otherwise).
  * cfg->bucket_events is honoured (vn_net_wait_bucket after the call; pass n_chunks = 0 and update after the exchange). */
+/* the loss's objective: see "RPN loss" below (vn_rpn_loss_spec_*); all zero = the reference's */
+#define VN_LOSS_BCE 0
+#define VN_LOSS_FOCAL 1
+typedef struct {
+    int32_t cls_kind;     /* VN_LOSS_BCE = 0 (reference), VN_LOSS_FOCAL = 1 */
+    int32_t yaw_sin;
+    float focal_alpha;
+    float focal_gamma;
+} vnLossSpec;
 struct vnParamChunk;
 typedef struct {
     const float *feature;          /* (K,T,7) */
@@ -613,6 +622,7 @@ typedef struct {
     int64_t *const *bn_counters;   /* NULL, or a DEVICE array of n_bn_counters pointers: every BatchNorm's num_batches_tracked, */
     int32_t n_bn_counters;         /* += 1 each (nn.BatchNorm*.forward in train mode) — one launch on the side stream */
     vnStream stream, side_stream;
+    vnLossSpec loss_spec;          /* the objective of the loss pass (vn_rpn_loss_spec_fwd_bwd_rows); all zero: the reference's */
 } vnStep;
 int vn_net_step(vnNet *net, const vnNetConfig *cfg, const vnStep *step);
 
@@ -839,6 +849,44 @@ int vn_rpn_loss_fwd_bwd_rows(const float *prob, const float *delta, const float 
                              const float *targets, int32_t B, int32_t H, int32_t W, float alpha, float beta, float sigma,
                              void *workspace, size_t workspace_bytes, const float *g_loss, float *d_prob, float *d_delta,
                              void *d_rows, vnDtype d_dtype, int64_t d_stride, int32_t split, vnStream stream);
+
+/* The objective of the pass as a parameter.  A zeroed spec, or NULL, is the reference's objective above and
+ * the vn_rpn_loss_spec_* calls are then the calls they are named after, bit for bit.  Per anchor of a site in sample b, with
+ * P_b = max(1, sum pos[b]), eps = 1e-6, fa = focal_alpha, g = focal_gamma:
+ *   cls_kind = VN_LOSS_FOCAL (sigmoid focal loss; BOTH terms over the positives' count, the negatives' count is not used):
+ *     cls_pos = fa     * pos * (1-p)^g * (-log(p + eps))     / P_b
+ *     cls_neg = (1-fa) * neg *   p^g   * (-log(1 - p + eps)) / P_b
+ *   yaw_sin = 1 (with either classification objective): the yaw channel's difference goes through the sine,
+ *     diff_6 = pos * sin(delta_6 - tgt_6)      instead of      diff_6 = pos * (delta_6 - tgt_6)
+ *     (a box and the same box turned by pi cost the same; the heading's sign is then not supervised)
+ *   reg_j = smooth_L1(diff_j) / P_b,  j = 0..6, the reference's smooth_L1 (loss.py:3-13) unchanged
+ *   out5  = [alpha*S_pos + beta*S_neg + S_reg, alpha*S_pos + beta*S_neg, S_reg, S_pos, S_neg]
+ * d_prob is the exact derivative of these expressions (the eps where they stand), d_delta_6 carries cos(delta_6 - tgt_6),
+ * the head row is d_prob * p * (1 - p) as before.  p = 0 and p = 1 give finite sums and gradients.
+ * focal_gamma must be 0 or >= 1 (0, 1 and 2 are computed by multiplication, other exponents by powf) and focal_alpha in
+ * [0,1]: VN_EINVAL otherwise, before anything is launched (the two fields are not read when cls_kind = VN_LOSS_BCE).
+ * vn_rpn_loss_spec_check is that test on its own (host only).  vn_rpn_loss_norm, vn_rpn_loss_finalize and
+ * vn_rpn_loss_workspace_bytes serve every objective. */
+/* (vnLossSpec itself is defined in front of vnStep, whose last member it is) */
+int vn_rpn_loss_spec_check(const vnLossSpec *spec);
+int vn_rpn_loss_spec_fwd(const float *prob, const float *delta, const float *pos, const float *neg,
+                         const float *targets, int32_t B, int32_t H, int32_t W, float alpha, float beta, float sigma,
+                         void *workspace, size_t workspace_bytes, float *out5, vnStream stream, const vnLossSpec *spec);
+int vn_rpn_loss_spec_bwd(const float *prob, const float *delta, const float *pos, const float *neg,
+                         const float *targets, int32_t B, int32_t H, int32_t W, float alpha, float beta, float sigma,
+                         const void *workspace, const float *g_loss, const float *g_cls, const float *g_reg,
+                         const float *g_cls_pos, const float *g_cls_neg, float *d_prob, float *d_delta,
+                         vnStream stream, const vnLossSpec *spec);
+int vn_rpn_loss_spec_fwd_bwd(const float *prob, const float *delta, const float *pos, const float *neg,
+                             const float *targets, int32_t B, int32_t H, int32_t W, float alpha, float beta, float sigma,
+                             void *workspace, size_t workspace_bytes, const float *g_loss, const float *g_cls,
+                             const float *g_reg, const float *g_cls_pos, const float *g_cls_neg, float *d_prob,
+                             float *d_delta, vnStream stream, const vnLossSpec *spec);
+int vn_rpn_loss_spec_fwd_bwd_rows(const float *prob, const float *delta, const float *pos, const float *neg,
+                                  const float *targets, int32_t B, int32_t H, int32_t W, float alpha, float beta, float sigma,
+                                  void *workspace, size_t workspace_bytes, const float *g_loss, float *d_prob, float *d_delta,
+                                  void *d_rows, vnDtype d_dtype, int64_t d_stride, int32_t split, vnStream stream,
+                                  const vnLossSpec *spec);
 
 /* ---- optimizer tail (voxelnet/train.py:153-154 with the optimizer of train.py:130-132) ---------------------
  * torch.nn.utils.clip_grad_norm_(parameters, max_norm) followed by SGD(lr) without momentum / weight decay:

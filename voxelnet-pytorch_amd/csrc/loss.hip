@@ -8,6 +8,9 @@
 // Layouts: prob (B,2,h,w), delta (B,14,h,w) fp32 NCHW (the module's outputs); pos/neg (B,h,w,2), targets (B,h,w,14)
 // fp32 channels-last (utils.generate_targets' arrays, model.py:309).  HBM-bound: ~0.1 KB per site, 70,400 sites.
 // Sums: per-thread fp32 -> per-workgroup slab rows -> one workgroup reduces the slab in double (deterministic).
+// The objective is a compile-time parameter of the pass (vnLossSpec): the reference's, above, or
+//   cls_pos = fa * pos * (1-p)^g * (-log(p + 1e-6)) / P_b ;  cls_neg = (1-fa) * neg * p^g * (-log(1 - p + 1e-6)) / P_b
+// (sigmoid focal loss, BOTH terms over the positives' count), and, independently, sin(delta_6 - tgt_6) for the yaw channel.
 #include "common.h"
 
 namespace {
@@ -82,15 +85,39 @@ struct HeadRows {
     int f32, split;    // fp32 rows | bf16 rows (split: the lo parts at [16 + c], vn_heads_bwd's form)
 };
 
-template <int MODE>
+// The objective, fixed at compile time.  OBJ bit 0: sigmoid focal classification (else the reference's balanced
+// cross-entropy), bit 1: the yaw channel's difference goes through sin().  OBJ = 0 is the reference's pass: its geometry
+// argument is LossGeom itself and every `if (FOCAL)` / `if (YAW_SIN)` below is compiled out, so it is the kernel it was.
+struct LossGeomFocal : LossGeom {
+    float fa, gamma;
+};
+template <int OBJ> struct LossObj { using Geom = LossGeom; };
+template <> struct LossObj<1> { using Geom = LossGeomFocal; };
+template <> struct LossObj<3> { using Geom = LossGeomFocal; };
+
+// x^gamma and d/dx x^gamma for x in [0,1], gamma = 0 or >= 1 (the entry points refuse anything else).  0, 1 and 2 by
+// multiplication: exp2(gamma * log2 x) at x = 0 is 0 * inf = NaN when the exponent is 0 — gamma = 0, and x^(gamma-1) of the
+// derivative at gamma = 1.  Other exponents are > 0 on both: powf, with 0 at x <= 0.
+__device__ __forceinline__ float focal_pow(float x, float gamma, float *dx) {
+    if (gamma == 0.f) { *dx = 0.f; return 1.f; }
+    if (gamma == 1.f) { *dx = 1.f; return x; }
+    if (gamma == 2.f) { *dx = 2.f * x; return x * x; }
+    if (!(x > 0.f)) { *dx = 0.f; return 0.f; }
+    *dx = gamma * powf(x, gamma - 1.f);
+    return powf(x, gamma);
+}
+
+template <int MODE, int OBJ>
 __global__ void __launch_bounds__(LOSS_THREADS) k_loss(const float *__restrict__ prob, const float *__restrict__ reg,
                                                        const float *__restrict__ pos, const float *__restrict__ neg,
                                                        const float *__restrict__ tgt, const float *__restrict__ norm,
-                                                       LossGeom g, float *__restrict__ slab /* fwd: [blocks][3] */,
+                                                       typename LossObj<OBJ>::Geom g,
+                                                       float *__restrict__ slab /* fwd: [blocks][3] */,
                                                        LossGrads gout /* bwd: five device scalars, NULL = 0 */,
                                                        float *__restrict__ d_prob, float *__restrict__ d_reg, HeadRows hr) {
     VN_PRIO_MAIN();
     constexpr bool BWD = MODE != 0, FWD = MODE != 1;
+    constexpr bool FOCAL = (OBJ & 1) != 0, YAW_SIN = (OBJ & 2) != 0;
     const int64_t hw = (int64_t)g.H * g.W, sites = hw * g.B;
     const int64_t site = (int64_t)blockIdx.x * LOSS_THREADS + threadIdx.x;
     float s_pos = 0.f, s_neg = 0.f, s_reg = 0.f;
@@ -114,6 +141,22 @@ __global__ void __launch_bounds__(LOSS_THREADS) k_loss(const float *__restrict__
         for (int a = 0; a < 2; ++a) {
             const int64_t pi = ((int64_t)b * 2 + a) * hw + yx;
             const float p = prob[pi];
+            if constexpr (FOCAL) {
+                // both terms over P_b; the derivative is the forward's as written, the 1e-6 where they stand
+                const float q = 1.f - p, wp = g.fa * pa[a] * inv_p, wn = (1.f - g.fa) * na[a] * inv_p;
+                const float lp = -logf(p + 1e-6f), ln = -logf(q + 1e-6f);
+                float dqg, dpg;
+                const float qg = focal_pow(q, g.gamma, &dqg), pg = focal_pow(p, g.gamma, &dpg);
+                if (BWD) {
+                    const float dp = kp * wp * (-dqg * lp - qg / (p + 1e-6f)) + kn * wn * (dpg * ln + pg / (q + 1e-6f));
+                    d_prob[pi] = dp;
+                    row[a] = dp * p * (1.0f - p);
+                }
+                if (FWD) {
+                    s_pos += wp * qg * lp;
+                    s_neg += wn * pg * ln;
+                }
+            } else {
             if (BWD) {
                 const float dp = -kp * pa[a] * inv_p / (p + 1e-6f) + kn * na[a] * inv_n / (1.f - p + 1e-6f);
                 d_prob[pi] = dp;
@@ -123,15 +166,23 @@ __global__ void __launch_bounds__(LOSS_THREADS) k_loss(const float *__restrict__
                 s_pos += -pa[a] * logf(p + 1e-6f) * inv_p;
                 s_neg += -na[a] * logf(1.f - p + 1e-6f) * inv_n;
             }
+            }
 #pragma unroll
             for (int j = 0; j < 7; ++j) {
                 const int c = a * 7 + j;
                 const int64_t ri = ((int64_t)b * 14 + c) * hw + yx;
-                const float diff = reg[ri] * pa[a] - tgt[site * 14 + c] * pa[a];
+                float diff, ddiff = pa[a];       // ddiff: d diff / d delta
+                if (YAW_SIN && j == 6) {
+                    const float ang = reg[ri] - tgt[site * 14 + c];
+                    diff = pa[a] * sinf(ang);
+                    if (BWD) ddiff = pa[a] * cosf(ang);
+                } else {
+                    diff = reg[ri] * pa[a] - tgt[site * 14 + c] * pa[a];
+                }
                 float dd;
                 const float l = smooth_l1(diff, g.sigma2, &dd);
                 if (BWD) {
-                    const float dr = kr * dd * pa[a] * inv_p;
+                    const float dr = kr * dd * ddiff * inv_p;
                     d_reg[ri] = dr;
                     row[2 + c] = dr;
                 }
@@ -197,7 +248,50 @@ __global__ void __launch_bounds__(LOSS_THREADS) k_loss_finalize(const float *__r
 
 bool loss_args_ok(int32_t B, int32_t H, int32_t W) { return B > 0 && H > 0 && W > 0 && (int64_t)B * H * W < (1ll << 31); }
 
+// OBJ of a checked spec (NULL: the reference's objective)
+int loss_obj(const vnLossSpec *spec) { return spec ? (spec->cls_kind == VN_LOSS_FOCAL ? 1 : 0) | (spec->yaw_sin ? 2 : 0) : 0; }
+
+struct LossArgs {
+    const float *prob, *reg, *pos, *neg, *tgt, *norm;
+    float *slab;
+    LossGrads up;
+    float *d_prob, *d_reg;
+    HeadRows hr;
+};
+
+template <int MODE, int OBJ>
+void launch_loss_obj(int blocks, hipStream_t st, const LossGeom &g, const vnLossSpec *spec, const LossArgs &a) {
+    typename LossObj<OBJ>::Geom gg;
+    static_cast<LossGeom &>(gg) = g;
+    if constexpr (OBJ & 1) { gg.fa = spec->focal_alpha; gg.gamma = spec->focal_gamma; }
+    k_loss<MODE, OBJ><<<blocks, LOSS_THREADS, 0, st>>>(a.prob, a.reg, a.pos, a.neg, a.tgt, a.norm, gg, a.slab, a.up, a.d_prob, a.d_reg,
+                                                       a.hr);
+}
+
+// the objective is picked here, on the host: one instantiation per (pass, objective), no branch on it inside a kernel
+template <int MODE>
+void launch_loss(int blocks, hipStream_t st, const LossGeom &g, const vnLossSpec *spec, const LossArgs &a) {
+    switch (loss_obj(spec)) {
+        case 0: launch_loss_obj<MODE, 0>(blocks, st, g, spec, a); break;
+        case 1: launch_loss_obj<MODE, 1>(blocks, st, g, spec, a); break;
+        case 2: launch_loss_obj<MODE, 2>(blocks, st, g, spec, a); break;
+        default: launch_loss_obj<MODE, 3>(blocks, st, g, spec, a); break;
+    }
+}
+
 }  // namespace
+
+extern "C" int vn_rpn_loss_spec_check(const vnLossSpec *spec) {
+    if (!spec) return VN_OK;
+    VN_CHECK_ARG(spec->cls_kind == VN_LOSS_BCE || spec->cls_kind == VN_LOSS_FOCAL);
+    VN_CHECK_ARG(spec->yaw_sin == 0 || spec->yaw_sin == 1);
+    if (spec->cls_kind == VN_LOSS_FOCAL) {
+        const float fa = spec->focal_alpha, ga = spec->focal_gamma;
+        VN_CHECK_ARG(fa >= 0.f && fa <= 1.f);                             // (NaN fails both)
+        VN_CHECK_ARG((ga == 0.f || ga >= 1.f) && ga <= 3.0e38f);          // see focal_pow
+    }
+    return VN_OK;
+}
 
 extern "C" size_t vn_rpn_loss_workspace_bytes(int32_t B, int32_t H, int32_t W) {
     if (!loss_args_ok(B, H, W)) return 0;
@@ -206,10 +300,12 @@ extern "C" size_t vn_rpn_loss_workspace_bytes(int32_t B, int32_t H, int32_t W) {
     return vn_align(sizeof(float) * 2 * (size_t)B) + vn_align(slab > part ? slab : part);
 }
 
-extern "C" int vn_rpn_loss_fwd(const float *prob, const float *delta, const float *pos, const float *neg,
-                               const float *targets, int32_t B, int32_t H, int32_t W, float alpha, float beta, float sigma,
-                               void *workspace, size_t workspace_bytes, float *out5, vnStream stream) {
+extern "C" int vn_rpn_loss_spec_fwd(const float *prob, const float *delta, const float *pos, const float *neg,
+                                    const float *targets, int32_t B, int32_t H, int32_t W, float alpha, float beta, float sigma,
+                                    void *workspace, size_t workspace_bytes, float *out5, vnStream stream,
+                                    const vnLossSpec *spec) {
     VN_CHECK_ARG(prob && delta && pos && neg && targets && workspace && out5 && loss_args_ok(B, H, W) && sigma > 0.f);
+    VN_CHECK_ARG(vn_rpn_loss_spec_check(spec) == VN_OK);
     if (workspace_bytes < vn_rpn_loss_workspace_bytes(B, H, W)) return VN_EWORKSPACE;
     hipStream_t st = vn_stream(stream);
     float *norm = static_cast<float *>(workspace);
@@ -220,10 +316,34 @@ extern "C" int vn_rpn_loss_fwd(const float *prob, const float *delta, const floa
     k_loss_norm_final<<<B, 64, 0, st>>>(slab, norm, B);
     VN_LAUNCH_STATUS();
     const LossGeom g{B, H, W, alpha, beta, sigma * sigma};
-    k_loss<0><<<blocks, LOSS_THREADS, 0, st>>>(prob, delta, pos, neg, targets, norm, g, slab, LossGrads{}, nullptr, nullptr,
-                                               HeadRows{});
+    launch_loss<0>(blocks, st, g, spec, LossArgs{prob, delta, pos, neg, targets, norm, slab, LossGrads{}, nullptr, nullptr, HeadRows{}});
     VN_LAUNCH_STATUS();
     k_loss_finalize<<<1, LOSS_THREADS, 0, st>>>(slab, blocks, alpha, beta, out5);
+    VN_LAUNCH_STATUS();
+    return VN_OK;
+}
+
+extern "C" int vn_rpn_loss_fwd(const float *prob, const float *delta, const float *pos, const float *neg,
+                               const float *targets, int32_t B, int32_t H, int32_t W, float alpha, float beta, float sigma,
+                               void *workspace, size_t workspace_bytes, float *out5, vnStream stream) {
+    return vn_rpn_loss_spec_fwd(prob, delta, pos, neg, targets, B, H, W, alpha, beta, sigma, workspace, workspace_bytes, out5, stream,
+                                nullptr);
+}
+
+extern "C" int vn_rpn_loss_spec_bwd(const float *prob, const float *delta, const float *pos, const float *neg,
+                                    const float *targets, int32_t B, int32_t H, int32_t W, float alpha, float beta, float sigma,
+                                    const void *workspace, const float *g_loss, const float *g_cls, const float *g_reg,
+                                    const float *g_cls_pos, const float *g_cls_neg, float *d_prob, float *d_delta,
+                                    vnStream stream, const vnLossSpec *spec) {
+    VN_CHECK_ARG(prob && delta && pos && neg && targets && workspace && d_prob && d_delta && loss_args_ok(B, H, W) &&
+                 sigma > 0.f);
+    VN_CHECK_ARG(vn_rpn_loss_spec_check(spec) == VN_OK);
+    const float *norm = static_cast<const float *>(workspace);   // written by vn_rpn_loss_fwd
+    const int blocks = (int)vn_ceil_div((int64_t)B * H * W, LOSS_THREADS);
+    const LossGeom g{B, H, W, alpha, beta, sigma * sigma};
+    launch_loss<1>(blocks, vn_stream(stream), g, spec,
+                   LossArgs{prob, delta, pos, neg, targets, norm, nullptr, LossGrads{{g_loss, g_cls, g_reg, g_cls_pos, g_cls_neg}},
+                            d_prob, d_delta, HeadRows{}});
     VN_LAUNCH_STATUS();
     return VN_OK;
 }
@@ -233,16 +353,8 @@ extern "C" int vn_rpn_loss_bwd(const float *prob, const float *delta, const floa
                                const void *workspace, const float *g_loss, const float *g_cls, const float *g_reg,
                                const float *g_cls_pos, const float *g_cls_neg, float *d_prob, float *d_delta,
                                vnStream stream) {
-    VN_CHECK_ARG(prob && delta && pos && neg && targets && workspace && d_prob && d_delta && loss_args_ok(B, H, W) &&
-                 sigma > 0.f);
-    const float *norm = static_cast<const float *>(workspace);   // written by vn_rpn_loss_fwd
-    const int blocks = (int)vn_ceil_div((int64_t)B * H * W, LOSS_THREADS);
-    const LossGeom g{B, H, W, alpha, beta, sigma * sigma};
-    k_loss<1><<<blocks, LOSS_THREADS, 0, vn_stream(stream)>>>(prob, delta, pos, neg, targets, norm, g, nullptr,
-                                                                  LossGrads{{g_loss, g_cls, g_reg, g_cls_pos, g_cls_neg}},
-                                                                  d_prob, d_delta, HeadRows{});
-    VN_LAUNCH_STATUS();
-    return VN_OK;
+    return vn_rpn_loss_spec_bwd(prob, delta, pos, neg, targets, B, H, W, alpha, beta, sigma, workspace, g_loss, g_cls, g_reg,
+                                g_cls_pos, g_cls_neg, d_prob, d_delta, stream, nullptr);
 }
 
 // ---- the same loss in three pieces, for a caller that schedules them itself (vn_net_step): the normalisers depend on the
@@ -266,18 +378,27 @@ extern "C" int vn_rpn_loss_norm(const float *pos, const float *neg, int32_t B, i
 static int loss_fwd_bwd(const float *prob, const float *delta, const float *pos, const float *neg, const float *targets,
                         int32_t B, int32_t H, int32_t W, float alpha, float beta, float sigma, void *workspace,
                         size_t workspace_bytes, const LossGrads &up, float *d_prob, float *d_delta, const HeadRows &hr,
-                        vnStream stream) {
+                        vnStream stream, const vnLossSpec *spec) {
     VN_CHECK_ARG(prob && delta && pos && neg && targets && workspace && d_prob && d_delta && loss_args_ok(B, H, W) &&
                  sigma > 0.f);
+    VN_CHECK_ARG(vn_rpn_loss_spec_check(spec) == VN_OK);
     if (workspace_bytes < vn_rpn_loss_workspace_bytes(B, H, W)) return VN_EWORKSPACE;
     const float *norm = static_cast<const float *>(workspace);   // written by vn_rpn_loss_norm
     float *slab = reinterpret_cast<float *>(static_cast<char *>(workspace) + vn_align(sizeof(float) * 2 * (size_t)B));
     const int blocks = (int)vn_ceil_div((int64_t)B * H * W, LOSS_THREADS);
     const LossGeom g{B, H, W, alpha, beta, sigma * sigma};
-    k_loss<2><<<blocks, LOSS_THREADS, 0, vn_stream(stream)>>>(prob, delta, pos, neg, targets, norm, g, slab, up, d_prob, d_delta,
-                                                               hr);
+    launch_loss<2>(blocks, vn_stream(stream), g, spec, LossArgs{prob, delta, pos, neg, targets, norm, slab, up, d_prob, d_delta, hr});
     VN_LAUNCH_STATUS();
     return VN_OK;
+}
+
+extern "C" int vn_rpn_loss_spec_fwd_bwd(const float *prob, const float *delta, const float *pos, const float *neg,
+                                        const float *targets, int32_t B, int32_t H, int32_t W, float alpha, float beta,
+                                        float sigma, void *workspace, size_t workspace_bytes, const float *g_loss,
+                                        const float *g_cls, const float *g_reg, const float *g_cls_pos, const float *g_cls_neg,
+                                        float *d_prob, float *d_delta, vnStream stream, const vnLossSpec *spec) {
+    return loss_fwd_bwd(prob, delta, pos, neg, targets, B, H, W, alpha, beta, sigma, workspace, workspace_bytes,
+                        LossGrads{{g_loss, g_cls, g_reg, g_cls_pos, g_cls_neg}}, d_prob, d_delta, HeadRows{}, stream, spec);
 }
 
 extern "C" int vn_rpn_loss_fwd_bwd(const float *prob, const float *delta, const float *pos, const float *neg,
@@ -285,8 +406,20 @@ extern "C" int vn_rpn_loss_fwd_bwd(const float *prob, const float *delta, const 
                                    void *workspace, size_t workspace_bytes, const float *g_loss, const float *g_cls,
                                    const float *g_reg, const float *g_cls_pos, const float *g_cls_neg, float *d_prob,
                                    float *d_delta, vnStream stream) {
+    return vn_rpn_loss_spec_fwd_bwd(prob, delta, pos, neg, targets, B, H, W, alpha, beta, sigma, workspace, workspace_bytes, g_loss,
+                                    g_cls, g_reg, g_cls_pos, g_cls_neg, d_prob, d_delta, stream, nullptr);
+}
+
+extern "C" int vn_rpn_loss_spec_fwd_bwd_rows(const float *prob, const float *delta, const float *pos, const float *neg,
+                                             const float *targets, int32_t B, int32_t H, int32_t W, float alpha, float beta,
+                                             float sigma, void *workspace, size_t workspace_bytes, const float *g_loss,
+                                             float *d_prob, float *d_delta, void *d_rows, vnDtype d_dtype, int64_t d_stride,
+                                             int32_t split, vnStream stream, const vnLossSpec *spec) {
+    VN_CHECK_ARG(d_rows && d_stride >= (split ? 32 : 16));
+    VN_CHECK_ARG(d_dtype == VN_BF16 || (d_dtype == VN_F32 && !split));
     return loss_fwd_bwd(prob, delta, pos, neg, targets, B, H, W, alpha, beta, sigma, workspace, workspace_bytes,
-                        LossGrads{{g_loss, g_cls, g_reg, g_cls_pos, g_cls_neg}}, d_prob, d_delta, HeadRows{}, stream);
+                        LossGrads{{g_loss, nullptr, nullptr, nullptr, nullptr}}, d_prob, d_delta,
+                        HeadRows{d_rows, d_stride, d_dtype == VN_F32, split}, stream, spec);
 }
 
 extern "C" int vn_rpn_loss_fwd_bwd_rows(const float *prob, const float *delta, const float *pos, const float *neg,
@@ -294,11 +427,8 @@ extern "C" int vn_rpn_loss_fwd_bwd_rows(const float *prob, const float *delta, c
                                         float sigma, void *workspace, size_t workspace_bytes, const float *g_loss,
                                         float *d_prob, float *d_delta, void *d_rows, vnDtype d_dtype, int64_t d_stride,
                                         int32_t split, vnStream stream) {
-    VN_CHECK_ARG(d_rows && d_stride >= (split ? 32 : 16));
-    VN_CHECK_ARG(d_dtype == VN_BF16 || (d_dtype == VN_F32 && !split));
-    return loss_fwd_bwd(prob, delta, pos, neg, targets, B, H, W, alpha, beta, sigma, workspace, workspace_bytes,
-                        LossGrads{{g_loss, nullptr, nullptr, nullptr, nullptr}}, d_prob, d_delta,
-                        HeadRows{d_rows, d_stride, d_dtype == VN_F32, split}, stream);
+    return vn_rpn_loss_spec_fwd_bwd_rows(prob, delta, pos, neg, targets, B, H, W, alpha, beta, sigma, workspace, workspace_bytes,
+                                         g_loss, d_prob, d_delta, d_rows, d_dtype, d_stride, split, stream, nullptr);
 }
 
 extern "C" int vn_rpn_loss_finalize(const void *workspace, size_t workspace_bytes, int32_t B, int32_t H, int32_t W, float alpha,

@@ -1360,6 +1360,7 @@ extern "C" int vn_net_step(vnNet *net, const vnNetConfig *cfg, const vnStep *s) 
     VN_CHECK_ARG(s->n_chunks >= 0 && (s->n_chunks == 0 || (s->chunks && s->opt_ws)));
     VN_CHECK_ARG(s->side_stream && s->side_stream != s->stream);
     VN_CHECK_ARG(s->n_bn_counters >= 0 && s->n_bn_counters <= 64);
+    VN_CHECK_ARG(vn_rpn_loss_spec_check(&s->loss_spec) == VN_OK);
     if (!cfg->sparse_first || !cfg->training || (cfg->grad_storage & 16)) return VN_EUNSUPPORTED;
     if (cfg->mode == 0 ? s->vw_rows == (void *)s->voxelwise : s->vw_rows != (void *)s->voxelwise) return VN_EINVAL;
     hipStream_t hs = vn_stream(s->stream), ss = vn_stream(s->side_stream);
@@ -1406,9 +1407,9 @@ extern "C" int vn_net_step(vnNet *net, const vnNetConfig *cfg, const vnStep *s) 
         Plan P;
         if (!make_plan(&c, s->K, static_cast<char *>(s->ws), &P)) return VN_EUNSUPPORTED;
         if (s->ws_bytes < P.bytes) return VN_EWORKSPACE;
-        RT(vn_rpn_loss_fwd_bwd_rows(s->prob, s->reg, s->pos, s->neg, s->targets, cfg->B, hf, wf, s->alpha, s->beta, s->sigma,
-                                    s->loss_ws, s->loss_ws_bytes, s->g_loss, s->d_prob, s->d_reg, P.d_rows.ptr, (vnDtype)P.adt, 16, 0,
-                                    s->stream));
+        RT(vn_rpn_loss_spec_fwd_bwd_rows(s->prob, s->reg, s->pos, s->neg, s->targets, cfg->B, hf, wf, s->alpha, s->beta, s->sigma,
+                                         s->loss_ws, s->loss_ws_bytes, s->g_loss, s->d_prob, s->d_reg, P.d_rows.ptr, (vnDtype)P.adt, 16,
+                                         0, s->stream, &s->loss_spec));
         net->heads_rows_ready = P.d_rows.ptr;
     }
     ev = net->next_event();

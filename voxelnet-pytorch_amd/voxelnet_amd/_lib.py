@@ -99,6 +99,13 @@ class VnAdamHyper(ctypes.Structure):   # vnAdamHyper: HOST memory, read during t
     _fields_ = [("n_slots", c_i32), ("slot", VnAdamSlot * VN_OPT_MAX_SLOTS)]
 
 
+VN_LOSS_BCE, VN_LOSS_FOCAL = 0, 1       # vnLossSpec.cls_kind
+
+
+class VnLossSpec(ctypes.Structure):   # vnLossSpec (vn_rpn_loss_spec_*, vnStep.loss_spec): all zero = the reference's objective
+    _fields_ = [("cls_kind", c_i32), ("yaw_sin", c_i32), ("focal_alpha", c_f32), ("focal_gamma", c_f32)]
+
+
 class VnStep(ctypes.Structure):       # vnStep (vn_net_step): field for field
     _fields_ = [("feature", c_vp), ("coord", c_vp), ("K", c_i64), ("T", c_i32), ("bn_momentum", c_f32), ("bn_eps", c_f32),
                 ("vfe", VnVfeWeights), ("vfe_grads", VnVfeGrads), ("vfe_ws", c_vp), ("vfe_ws_bytes", c_sz),
@@ -110,7 +117,7 @@ class VnStep(ctypes.Structure):       # vnStep (vn_net_step): field for field
                 ("loss_ws", c_vp), ("loss_ws_bytes", c_sz), ("loss5", c_vp), ("g_loss", c_vp), ("chunks", c_vp),
                 ("n_chunks", c_i32), ("max_norm", c_f32), ("lr", c_f32), ("scale_grads", c_i32), ("opt_ws", c_vp),
                 ("opt_ws_bytes", c_sz), ("total_norm", c_vp), ("bn_counters", c_vp), ("n_bn_counters", c_i32), ("stream", c_vp),
-                ("side_stream", c_vp)]
+                ("side_stream", c_vp), ("loss_spec", VnLossSpec)]
 
 
 class VnAugmentBox(ctypes.Structure):   # vnAugmentBox (vn_augment_points): one entry of the device box table, 64 bytes
@@ -258,6 +265,15 @@ SIGNATURES = {
     "vn_rpn_loss_finalize": (c_i32, [c_vp, c_sz, c_i32, c_i32, c_i32, c_f32, c_f32, c_vp, c_vp]),
     "vn_rpn_loss_fwd_bwd_rows": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_f32, c_f32, c_f32, c_vp, c_sz, c_vp, c_vp,
                                          c_vp, c_vp, c_i32, c_i64, c_i32, c_vp]),
+    "vn_rpn_loss_spec_check": (c_i32, [_P(VnLossSpec)]),
+    "vn_rpn_loss_spec_fwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_f32, c_f32, c_f32, c_vp, c_sz, c_vp, c_vp,
+                                     _P(VnLossSpec)]),
+    "vn_rpn_loss_spec_bwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp,
+                                     c_vp, c_vp, c_vp, c_vp, c_vp, _P(VnLossSpec)]),
+    "vn_rpn_loss_spec_fwd_bwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_f32, c_f32, c_f32, c_vp, c_sz, c_vp,
+                                         c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, _P(VnLossSpec)]),
+    "vn_rpn_loss_spec_fwd_bwd_rows": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_f32, c_f32, c_f32, c_vp, c_sz,
+                                              c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_vp, _P(VnLossSpec)]),
     "vn_rpn_targets_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32]),
     "vn_rpn_targets": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, c_f32, ctypes.c_double, c_vp, c_vp, c_vp,
                                c_vp, c_sz, c_vp]),

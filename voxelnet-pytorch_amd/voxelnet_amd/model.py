@@ -878,12 +878,42 @@ def _detector_backward_native(ctx, d_prob, d_reg):
 _DetectorFn._backward_native = staticmethod(_detector_backward_native)
 
 
+_LOSS_SPECS = {}
+
+
+def loss_spec(cls_loss="bce", focal_alpha=0.25, focal_gamma=2.0, yaw_loss="diff"):
+    """-> _lib.VnLossSpec (include/voxelnet_hip.h), checked here on the host: ValueError for what the library
+    would answer with VN_EINVAL, before anything is launched.  ("bce", "diff") is all zero: the reference's objective.
+    The struct of a checked combination is kept and shared (nothing writes to it): a dictionary look-up per step."""
+    key = (cls_loss, focal_alpha, focal_gamma, yaw_loss)
+    try:
+        return _LOSS_SPECS[key]
+    except (KeyError, TypeError):
+        pass
+    if cls_loss not in ("bce", "focal"):
+        raise ValueError(f"cls_loss must be 'bce' or 'focal', not {cls_loss!r}")
+    if yaw_loss not in ("diff", "sin"):
+        raise ValueError(f"yaw_loss must be 'diff' or 'sin', not {yaw_loss!r}")
+    spec = _lib.VnLossSpec(0, int(yaw_loss == "sin"), 0.0, 0.0)
+    if cls_loss == "focal":
+        fa, ga = float(focal_alpha), float(focal_gamma)
+        if not 0.0 <= fa <= 1.0:
+            raise ValueError(f"focal_alpha must lie in [0, 1], not {focal_alpha!r}")
+        if not (ga == 0.0 or 1.0 <= ga < float("inf")):
+            raise ValueError(f"focal_gamma must be 0 or >= 1 (x^gamma and its derivative at x = 0), not {focal_gamma!r}")
+        spec.cls_kind, spec.focal_alpha, spec.focal_gamma = _lib.VN_LOSS_FOCAL, fa, ga
+    if _lib.load().vn_rpn_loss_spec_check(ctypes.byref(spec)) != 0:
+        raise ValueError(f"loss spec refused by the library: {cls_loss!r} {focal_alpha!r} {focal_gamma!r} {yaw_loss!r}")
+    _LOSS_SPECS[key] = spec
+    return spec
+
+
 class _LossFn(torch.autograd.Function):
     """model.py:309-352 as two fused passes over the anchor sites (csrc/loss.hip) -> tensor [loss, cls_loss,
-    reg_loss, cls_pos_loss_rec, cls_neg_loss_rec]"""
+    reg_loss, cls_pos_loss_rec, cls_neg_loss_rec].  spec: a _lib.VnLossSpec (loss_spec()), None = the reference's objective"""
 
     @staticmethod
-    def forward(ctx, prob, delta, pos, neg, tgt, alpha, beta, sigma):
+    def forward(ctx, prob, delta, pos, neg, tgt, alpha, beta, sigma, spec=None):
         _need_cuda(prob, delta, pos, neg, tgt)
         B, _, H, W = prob.shape
         if tuple(delta.shape) != (B, 14, H, W) or tuple(pos.shape) != (B, H, W, 2) or tuple(neg.shape) != (B, H, W, 2) \
@@ -896,23 +926,24 @@ class _LossFn(torch.autograd.Function):
             ws = torch.empty(ws_bytes, dtype=torch.uint8, device=prob.device)
             out = torch.empty(5, dtype=torch.float32, device=prob.device)
             with E.section("loss_fwd", 4.0 * B * H * W * 34):
-                _lib.call("vn_rpn_loss_fwd", prob.data_ptr(), delta.data_ptr(), pos.data_ptr(), neg.data_ptr(), tgt.data_ptr(),
-                          B, H, W, alpha, beta, sigma, ws.data_ptr(), ws_bytes, out.data_ptr(), E.stream())
-        ctx.saved = (prob, delta, pos, neg, tgt, ws, (B, H, W, alpha, beta, sigma))
+                _lib.call("vn_rpn_loss_spec_fwd", prob.data_ptr(), delta.data_ptr(), pos.data_ptr(), neg.data_ptr(), tgt.data_ptr(),
+                          B, H, W, alpha, beta, sigma, ws.data_ptr(), ws_bytes, out.data_ptr(), E.stream(),
+                          None if spec is None else ctypes.byref(spec))
+        ctx.saved = (prob, delta, pos, neg, tgt, ws, (B, H, W, alpha, beta, sigma), spec)
         ctx.set_materialize_grads(False)          # unused outputs arrive as None in backward, not as zero tensors
         return tuple(out[i] for i in range(5))    # five scalars (views of one buffer): loss, cls, reg, cls_pos, cls_neg
 
     @staticmethod
     def backward(ctx, *gs):
-        prob, delta, pos, neg, tgt, ws, (B, H, W, alpha, beta, sigma) = ctx.saved
+        prob, delta, pos, neg, tgt, ws, (B, H, W, alpha, beta, sigma), spec = ctx.saved
         gs = [None if g is None else g.contiguous().float() for g in gs]
         with _lib.on_device(prob.device):
             d_prob, d_delta = torch.empty_like(prob), torch.empty_like(delta)
             with E.section("loss_bwd", 4.0 * B * H * W * 50):
-                _lib.call("vn_rpn_loss_bwd", prob.data_ptr(), delta.data_ptr(), pos.data_ptr(), neg.data_ptr(), tgt.data_ptr(),
+                _lib.call("vn_rpn_loss_spec_bwd", prob.data_ptr(), delta.data_ptr(), pos.data_ptr(), neg.data_ptr(), tgt.data_ptr(),
                           B, H, W, alpha, beta, sigma, ws.data_ptr(), *[None if g is None else g.data_ptr() for g in gs],
-                          d_prob.data_ptr(), d_delta.data_ptr(), E.stream())
-        return d_prob, d_delta, None, None, None, None, None, None
+                          d_prob.data_ptr(), d_delta.data_ptr(), E.stream(), None if spec is None else ctypes.byref(spec))
+        return d_prob, d_delta, None, None, None, None, None, None, None     # (a trailing None too many is allowed)
 
 
 _STREAMS = {}
@@ -933,9 +964,16 @@ class RPN3D(nn.Module):
     csrc/targets.hip), unless `targets=(pos_equal_one, neg_equal_one, targets)` (channels-last arrays as
     utils.generate_targets returns them) is passed or `target_fn` is set."""
 
-    def __init__(self, cls_name="Car", alpha=ALPHA, beta=BETA, sigma=SIGMA):
+    # the loss's objective (DESIGN.md 1e).  Class-level defaults: a model pickled before these attributes existed loads
+    # without them in its __dict__ and still reads the reference's objective here.
+    cls_loss, focal_alpha, focal_gamma, yaw_loss = "bce", 0.25, 2.0, "diff"
+
+    def __init__(self, cls_name="Car", alpha=ALPHA, beta=BETA, sigma=SIGMA, *, cls_loss="bce", focal_alpha=0.25, focal_gamma=2.0,
+                 yaw_loss="diff"):
         super().__init__()
         self.cls_name, self.alpha, self.beta, self.sigma = cls_name, alpha, beta, sigma
+        loss_spec(cls_loss, focal_alpha, focal_gamma, yaw_loss)      # (ValueError here, not at the first step)
+        self.cls_loss, self.focal_alpha, self.focal_gamma, self.yaw_loss = cls_loss, focal_alpha, focal_gamma, yaw_loss
         self.feature_net = FeatureLearningNet(cls_name)
         self.middle_rpn = MiddleConvNet(cls_name)
         self.rpn_output_shape = self.middle_rpn.output_shape
@@ -1150,8 +1188,13 @@ class RPN3D(nn.Module):
     def _all_need_grad(self, flat):
         return all(p.requires_grad for p in flat)
 
+    def _loss_spec(self):
+        """the vnLossSpec of cls_loss / focal_alpha / focal_gamma / yaw_loss as they are now (they may be set after construction)"""
+        return loss_spec(self.cls_loss, self.focal_alpha, self.focal_gamma, self.yaw_loss)
+
     def loss(self, prob_out, delta_out, pos_equal_one, neg_equal_one, targets):
-        """model.py:310-352 -> (loss, cls_loss, reg_loss, cls_pos_loss_rec, cls_neg_loss_rec), fused (csrc/loss.hip)."""
+        """model.py:310-352 -> (loss, cls_loss, reg_loss, cls_pos_loss_rec, cls_neg_loss_rec), fused (csrc/loss.hip); with
+        cls_loss="focal" / yaw_loss="sin" the objective of DESIGN.md 1e, same five outputs."""
         dev = prob_out.device
 
         def f32(a):
@@ -1159,7 +1202,7 @@ class RPN3D(nn.Module):
                 return a
             return (a if torch.is_tensor(a) else torch.from_numpy(np.asarray(a))).to(dev).float().contiguous()
         return _LossFn.apply(prob_out, delta_out, f32(pos_equal_one), f32(neg_equal_one), f32(targets),
-                             float(self.alpha), float(self.beta), float(self.sigma))
+                             float(self.alpha), float(self.beta), float(self.sigma), self._loss_spec())
 
     # ---- one library call per train step (vn_net_step) ------------------------------------------------------------------
     def _step_scratch(self, dev, K, T, B, mode, hf, wf):
@@ -1211,6 +1254,7 @@ class RPN3D(nn.Module):
         reducer without a communication stream, bench.py's per-section timer — takes the separate calls, same results."""
         from .optim import ClipSGD
         mode = _mode()
+        spec = self._loss_spec()            # (checked before anything is launched)
         fused = self._step_fused_ok(mode, optimizer)
         plist = self._flat_params() if fused else None
         if fused and (not self._all_need_grad(plist) or any(p.grad is not None for p in plist)):
@@ -1293,6 +1337,7 @@ class RPN3D(nn.Module):
             a.pos, a.neg, a.targets = pos.data_ptr(), neg.data_ptr(), tgt.data_ptr()
             a.targets_stream = ts.cuda_stream if ts is not None else None
             a.alpha, a.beta, a.sigma = float(self.alpha), float(self.beta), float(self.sigma)
+            a.loss_spec = spec
             a.loss_ws, a.loss_ws_bytes, a.loss5, a.g_loss = sc["loss_ws"].data_ptr(), sc["loss_ws_bytes"], loss5.data_ptr(), sc["one"].data_ptr()
             grads = self.__dict__.get("_mg_cache")
             if grads is None or grads[0] is not views:
