@@ -441,6 +441,31 @@ int vn_gt_paste(const float *points, int64_t n, const vnGtBox *boxes, int32_t n_
                 vnStream stream);
 
 /* ------------------------------------------------------------------------
+ * Point shuffle on the device — the reference's np.random.shuffle(point_cloud) in front of the voxelizer
+ * (voxelnet/utils.py:35), which decides which <= T points of a crowded voxel survive, as a row gather right behind the
+ * host->device copy (csrc/shuffle.hip; the draws are voxelnet_amd/shuffle.py).  points / out: (n,4) fp32
+ * [x,y,z,reflectance], 16-byte aligned.  In both calls output row i is a BIT copy of input row p(i), moved as one 16-byte
+ * word: NaN payloads, -0.0 and the reflectance survive.
+ *   vn_permute_points: p(i) = index[i]; index = DEVICE table of n int32.  With the table np.random.shuffle made of
+ *     arange(n) — the same Mersenne-Twister draws as the shuffle of the (n,C) cloud itself — out is the reference's
+ *     shuffled cloud bit for bit.  An index outside [0, n) writes a NaN point (four 0x7FC00000 words) to that row and
+ *     reads nothing: no table makes the kernel read outside points.
+ *   vn_shuffle_points: p = a keyed bijection of [0, n), evaluated per thread; keys = SIX uint32 in HOST memory, read during
+ *     the call and passed to the kernel by value.  A six-round Feistel network over 2h bits, walked until it lands inside
+ *     the range; exact uint32 arithmetic (wrapping multiplies):
+ *       k = max(2, bit_length(n - 1));   h = (k + 1) / 2;   mask = 2^h - 1        (n < 2^31, so 2h <= 32)
+ *       fmix32(x): x ^= x >> 16; x *= 0x85EBCA6B; x ^= x >> 13; x *= 0xC2B2AE35; x ^= x >> 16
+ *       F(x):  L = x >> h;  R = x & mask;  for r in 0..5:  (L, R) = (R, L ^ (fmix32(R ^ keys[r]) & mask));  (L << h) | R
+ *       p(i):  x = F(i);  while x >= n: x = F(x)
+ *     F is a bijection of [0, 2^2h) and i lies on its own cycle, so the walk ends; 2^2h < 4n.
+ * A null pointer with n > 0, n < 0 or n > 2^31 - 1: VN_EINVAL.  out overlapping points (a gather cannot run in place) or
+ * the index table: VN_EINVAL.  Misaligned pointers: VN_EUNSUPPORTED.  n == 0 is a no-op.  Every argument is checked
+ * before anything is launched.  One launch each, one thread per output row; asynchronous; no workspace.
+ * ---------------------------------------------------------------------- */
+int vn_permute_points(const float *points, int64_t n, const int32_t *index, float *out, vnStream stream);
+int vn_shuffle_points(const float *points, int64_t n, const uint32_t keys[6], float *out, vnStream stream);
+
+/* ------------------------------------------------------------------------
  * Native step executor — MiddleConvNet.forward (model.py:257-281) and its backward as ONE call
  * each (csrc/runtime.hip): layer table, launch geometry and workspace arena live in C++, so the
  * ~450 launches of a step cost microseconds of host time instead of a Python round trip each.

@@ -163,6 +163,8 @@ SIGNATURES = {
     "vn_points_in_boxes": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_vp, c_vp, c_vp]),
     "vn_gt_paste_workspace_bytes": (c_sz, [c_i64]),
     "vn_gt_paste": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_sz, c_vp]),
+    "vn_permute_points": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "vn_shuffle_points": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp]),
     "vn_comm_rccl_version": (c_i32, []),
     "vn_comm_unique_id": (c_i32, [c_vp]),
     "vn_comm_create": (c_i32, [_P(c_vp), c_vp, c_i32, c_i32]),

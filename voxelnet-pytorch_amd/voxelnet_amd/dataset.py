@@ -20,7 +20,12 @@ Ground-truth database sampling (gtsample.py; SECOND's "GT-paste", no counterpart
 of the augmentation: copy -> [field-of-view crop] -> paste -> augment -> voxelize.  `DeviceCollate(..., gt_sampler=s)` /
 `DeviceBatcher(..., gt_sampler=s)` draw the pasted objects per sample on the host (after the sample's shuffle, before the
 augmentation's draw, which then runs on the enlarged labels), paste their points on the device (csrc/gtsample.hip) and
-hand the model labels + the pasted objects' lines."""
+hand the model labels + the pasted objects' lines.
+
+The sample's shuffle (utils.py:35) is by default the reference's: `np.random.shuffle` of the host cloud, in the thread that
+also enqueues the train step.  `shuffle_points="index"` / `"device"` move the per-point half to the device (shuffle.py,
+csrc/shuffle.hip), as the first stage behind the copy: copy -> shuffle -> [field-of-view crop] -> paste -> augment ->
+voxelize; the host then draws an index table (the same np.random draws, the same voxel buffers) or six round keys."""
 import glob
 import os
 
@@ -78,7 +83,18 @@ class DeviceCollate:
 
     def __init__(self, device="cuda:0", target="Car", shuffle_points=True, fov_calib_dir=None, image_shape=(375, 1242),
                  augment=False, gt_sampler=None):
-        """augment: the reference's pcl_augmentation (dataset.py:122-219) per sample — drawn from np.random after the
+        """shuffle_points: the sample's shuffle in front of the voxelizer (utils.py:35).
+          True / "host": np.random.shuffle of the sample's cloud on the host, in place like the reference; False: none.
+          "index":  shuffle.draw_index at that place — the sample's first draw, the same np.random draws — the cloud is
+                    uploaded as read and `vn_permute_points` gathers the rows right behind the copy, in front of the crop,
+                    the paste and the augmentation: voxel buffers, labels and the np.random state after the batch are
+                    those of True, bit for bit.
+          "device": shuffle.draw_keys at that place (one randint of six uint32), then `vn_shuffle_points`: a keyed
+                    bijection evaluated per thread, no host work proportional to the cloud.  Another shuffle than the
+                    reference's, and other np.random consumption.
+          Anything else raises ValueError.  Divergence of the two device modes: the caller's `pcl` array is NOT modified,
+          and the batch's raw-lidar element (element 6) is the cloud AS READ, not the shuffled one.
+        augment: the reference's pcl_augmentation (dataset.py:122-219) per sample — drawn from np.random after the
         sample's shuffle, applied to the (cropped) cloud on the device in front of the voxelizer; the batch's `label`
         element then holds the MOVED label lines (augment.augment_labels), its raw-lidar element the host cloud as shuffled.
         fov_calib_dir: RAW sweeps — crop every cloud to the camera field of view on the device before it is voxelized
@@ -91,6 +107,13 @@ class DeviceCollate:
         pasted into the (cropped) cloud on the device in front of the augmentation (the scene points inside their boxes
         go) and the batch's `label` element holds labels + their lines (moved by the augmentation when it is on).  None:
         nothing is drawn, nothing is launched."""
+        # (strings are truthy: an unknown one must not fall through to the host shuffle)
+        if isinstance(shuffle_points, str) and shuffle_points in ("host", "index", "device"):
+            self._shuffle_mode = shuffle_points
+        elif isinstance(shuffle_points, (bool, np.bool_, int)) and shuffle_points in (True, False):
+            self._shuffle_mode = "host" if shuffle_points else None
+        else:
+            raise ValueError(f"shuffle_points={shuffle_points!r}: expected True, False, 'host', 'index' or 'device'")
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise _lib.VoxelnetHipError("DeviceCollate needs a HIP device (no CPU path)")
@@ -110,11 +133,18 @@ class DeviceCollate:
             from . import gtsample as G
         if self.augment or self.gt_sampler is not None:
             parts = list(parts)
+        mode = self._shuffle_mode
+        if mode in ("index", "device"):
+            from . import shuffle as S
         with torch.cuda.stream(self.stream):
             for b, p in enumerate(parts):
                 pcl = p[2]
-                if self.shuffle_points:
+                if mode == "host":
                     np.random.shuffle(pcl)                                     # utils.py:35, in place like the reference
+                elif mode == "index":
+                    perm = S.draw_index(pcl.shape[0])                          # the same draws; the rows move on the device
+                elif mode == "device":
+                    perm = S.draw_keys()
                 pasted = None
                 if self.gt_sampler is not None:
                     pasted = self.gt_sampler.draw(p[3], p[0])                  # host: O(boxes); no points yet
@@ -127,6 +157,14 @@ class DeviceCollate:
                     parts[b] = (p[0], p[1], p[2], A.augment_labels(p[3], params), *p[4:])
                 host = torch.from_numpy(np.ascontiguousarray(pcl[:, :4], dtype=np.float32)).pin_memory()
                 pts = host.to(self.device, non_blocking=True)
+                if mode == "index":
+                    # right behind the copy on this stream; `keep` = the staged index table, referenced by the handle
+                    # until the batch is consumed, like `host`
+                    pts, keep = S.enqueue_permute_points(pts, perm)
+                    host = (host, keep)
+                elif mode == "device":
+                    pts, keep = S.enqueue_shuffle_points(pts, perm)
+                    host = (host, keep)
                 if self.fov_calib_dir is not None:
                     from .fov import fov_crop_device, load_calib
                     P, Tr, R = load_calib(os.path.join(self.fov_calib_dir, str(p[0]) + ".txt"))
