@@ -914,12 +914,14 @@ int vn_rpn_loss_spec_fwd_bwd_rows(const float *prob, const float *delta, const f
                                   const vnLossSpec *spec);
 
 /* ---- optimizer tail (voxelnet/train.py:153-154 with the optimizer of train.py:130-132) ---------------------
- * torch.nn.utils.clip_grad_norm_(parameters, max_norm) followed by SGD(lr) without momentum / weight decay:
- *   total = sqrt(sum |g|^2) over every chunk;  coef = min(1, max_norm / (total + 1e-6));  p -= lr * coef * g
- * in two launches.  `chunks` is a DEVICE array the caller builds once for a fixed set of fp32 tensors: every
- * (parameter, gradient) pair cut into pieces of at most VN_OPT_CHUNK elements.  scale_grads != 0 also stores
- * g *= coef (what clip_grad_norm_ leaves behind); total_norm (device, may be NULL) receives the norm before
- * clipping, clip_grad_norm_'s return value. */
+ * torch.nn.utils.clip_grad_norm_(parameters, max_norm) followed by an update rule, in two launches.  The clip is the
+ * same code under both rules (vn_clip_sgd here, vn_clip_adamw below):
+ *   total = sqrt(sum |g|^2) over EVERY chunk;  coef = min(1, max_norm / (total + 1e-6))  (NaN stays NaN);  g' = g * coef
+ * Sums: fp32 per thread, one fp32 partial per chunk, added in double in one fixed order by every workgroup of the second
+ * launch — no atomics, bit-identical from run to run.  scale_grads != 0 also stores g' (what clip_grad_norm_ leaves
+ * behind); total_norm (device, may be NULL) receives the norm before clipping, clip_grad_norm_'s return value.
+ * vn_clip_sgd: SGD(lr) without momentum / weight decay, p -= lr * g'.  `chunks` is a DEVICE array the caller builds once
+ * for a fixed set of fp32 tensors: every (parameter, gradient) pair cut into pieces of at most VN_OPT_CHUNK elements. */
 #define VN_OPT_CHUNK 4096
 typedef struct vnParamChunk {
     float *param;
@@ -932,11 +934,10 @@ int vn_clip_sgd(const vnParamChunk *chunks, int32_t n_chunks, float max_norm, fl
                 void *workspace, size_t workspace_bytes, float *total_norm, vnStream stream);
 
 /* ---- optimizer tail with AdamW in SGD's place (voxelnet/train.py:153-154; what every successor trains with) ----
- * torch.nn.utils.clip_grad_norm_(parameters, max_norm) followed by torch.optim.AdamW's update (torch/optim/adam.py
- * _single_tensor_adam with decoupled_weight_decay, amsgrad = False, maximize = False), in two launches:
- *   total = sqrt(sum |g|^2) over EVERY chunk, whatever its slot;  coef = min(1, max_norm / (total + 1e-6))  (NaN stays NaN)
- *   per element, with the values of its chunk's slot:
- *     g' = g * coef;  p *= 1 - lr * wd;  m += (g' - m) * (1 - beta1);  v = beta2 * v + (1 - beta2) * g'^2
+ * The clip of vn_clip_sgd (above: norm over every chunk whatever its slot, coefficient, sums, scale_grads, total_norm)
+ * followed by torch.optim.AdamW's update (torch/optim/adam.py _single_tensor_adam with decoupled_weight_decay, amsgrad =
+ * False, maximize = False), in two launches; per element, with the values of its chunk's slot:
+ *     p *= 1 - lr * wd;  m += (g' - m) * (1 - beta1);  v = beta2 * v + (1 - beta2) * g'^2
  *     p -= (lr / (1 - beta1^t)) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
  * `chunks` is a DEVICE array built once for a fixed set of fp32 tensors: every (parameter, gradient, exp_avg, exp_avg_sq)
  * quadruple cut into pieces of at most VN_OPT_CHUNK elements, each naming the hyperparameter slot it takes; the kernel
@@ -944,9 +945,6 @@ int vn_clip_sgd(const vnParamChunk *chunks, int32_t n_chunks, float max_norm, fl
  * and the step count can change from call to call (schedulers) without touching the device table.  The slot's five
  * floats are widened to the double with the shortest decimal form that rounds to the float (0.999f means 0.999, not
  * 0.99900001287...), 1 - beta, 1 - lr * wd and 1 - beta^t are taken in double, and the results go to the kernel by value.
- * scale_grads != 0 also stores g' (what clip_grad_norm_ leaves behind); total_norm (device, may be NULL) receives the norm
- * before clipping.  Sums as in vn_clip_sgd: fp32 per thread, one fp32 partial per chunk, added in double in one fixed
- * order by every workgroup of the second launch — no atomics, bit-identical from run to run.
  * VN_EINVAL (before any HIP call): a NULL chunks / hyper / workspace, n_chunks <= 0, max_norm <= 0 or NaN, n_slots outside
  * 1..VN_OPT_MAX_SLOTS, a slot (of the first n_slots) with a beta outside [0,1), eps < 0, lr < 0, weight_decay < 0, step < 1
  * or a NaN; VN_EWORKSPACE: workspace_bytes < vn_clip_adamw_workspace_bytes(n_chunks).  Asynchronous. */

@@ -1,4 +1,4 @@
-"""CPU: the host side of the fused gradient-clip + AdamW tail (vn_clip_adamw, csrc/adamw.hip; voxelnet_amd.optim.ClipAdamW):
+"""CPU: the host side of the fused gradient-clip + AdamW tail (vn_clip_adamw, csrc/optim.hip; voxelnet_amd.optim.ClipAdamW):
 the symbols and the ctypes mirror of the header, the argument checks (status codes, before any HIP call — there is no device
 here), the optimizer's torch.optim.Optimizer face and its state-dict exchange with torch.optim.AdamW, and
 decay_param_groups on the detector's real tensor set.  The arithmetic is tested on the GPU (tests/test_gpu_adamw.py)."""

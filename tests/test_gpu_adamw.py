@@ -1,4 +1,4 @@
-"""Fused gradient-clip + AdamW tail (csrc/adamw.hip through vn_clip_adamw / voxelnet_amd.optim.ClipAdamW) against
+"""Fused gradient-clip + AdamW tail (csrc/optim.hip through vn_clip_adamw / voxelnet_amd.optim.ClipAdamW) against
 tests/adamw_ref.py, the float64 NumPy restatement of clip_grad_norm_ + torch.optim.AdamW's single-tensor rules.
 
 Tolerance: measured, not chosen.  For p, exp_avg and exp_avg_sq the bar at a step is 4 x the largest absolute difference
@@ -392,7 +392,7 @@ def test_train_step_with_clip_adamw_stays_on_the_one_call_path(monkeypatch):
     lr-sized steps of opposite sign out of gradients that are rounding noise.  Measured on the MI355X with an element update
     that was within 0.43 of the bars of torch's but not equal to it in the last bit: step 1 norms 881.774109 on both sides
     (equal bit for bit) and parameters at 0.011 of this bar; step 2 norms 339.1069 against 339.0435 (1.9e-4 relative) and
-    parameters at 3088 times the bar (lr = 1e-3: step 2 norms 4506.72 against 4502.67).  csrc/adamw.hip's element update
+    parameters at 3088 times the bar (lr = 1e-3: step 2 norms 4506.72 against 4502.67).  csrc/optim.hip's element update
     therefore rounds where torch's device kernels round; with it the step 2 norms are equal bit for bit (339.043549) and
     the parameters sit at 0.011 and 0.015 of the bar after the two steps."""
     from voxelnet_amd import _lib, synth

@@ -57,6 +57,36 @@ def test_clip_sgd_matches_oracle(scale, flat, scale_grads):
     assert torch.equal(params[2].detach(), kept)
 
 
+@pytest.mark.parametrize("scale,flat,nan", [(1.0, False, False), (1e-4, False, False), (1.0, True, False), (1e-4, True, False),
+                                            (1.0, False, True), (1.0, True, True)])
+def test_clip_sgd_and_clip_adamw_clip_alike(scale, flat, nan):
+    """The clip is one piece of code under both update rules: on equal gradients ClipSGD and ClipAdamW return the same norm
+    and leave the same scaled gradients (g * coef with one coef), bit for bit, on both sides of the clamp, on the vector
+    path (separate tensors) and the element path (views of a flat buffer, off 16-byte boundaries).  A NaN among the
+    gradients makes the norm, the coefficient and with it every scaled gradient NaN under both."""
+    from voxelnet_amd.optim import ClipAdamW, ClipSGD
+    norms, grads = [], []
+    for cls in (ClipSGD, ClipAdamW):
+        _, _, dp, dg = _tensors(scale, 11, flat)
+        if nan:
+            dg[4].view(-1)[12345] = float("nan")
+        params = [torch.nn.Parameter(p) for p in dp]
+        for p, g in zip(params, dg):
+            p.grad = g
+        norms.append(cls(params, lr=0.01, max_norm=5.0, scale_grads=True).step())
+        grads.append(dg)
+    torch.cuda.synchronize()
+    if nan:
+        assert torch.isnan(norms[0]) and torch.isnan(norms[1])
+        for a, b in zip(*grads):
+            assert torch.equal(torch.isnan(a), torch.isnan(b)) and torch.isnan(a).all()
+    else:
+        assert torch.equal(norms[0], norms[1])
+        assert (norms[0].item() > 5.0) == (scale == 1.0)      # the cases cover both sides of the clamp
+        for a, b in zip(*grads):
+            assert torch.equal(a, b)
+
+
 def test_clip_sgd_refuses_cpu_tensors():
     from voxelnet_amd import _lib
     from voxelnet_amd.optim import ClipSGD

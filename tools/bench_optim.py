@@ -1,7 +1,7 @@
 """The optimizer tail alone on the detector's real tensor set: RPN3D("Car"), 104 tensors, 6,809,392 elements, gradients in
 the module's flat gradient buffer (what RPN3D.train_step leaves in .grad).  Four arms, alternated inside one process:
   clip_sgd      voxelnet_amd.optim.ClipSGD              (vn_clip_sgd, csrc/optim.hip: two launches)
-  clip_adamw    voxelnet_amd.optim.ClipAdamW            (vn_clip_adamw, csrc/adamw.hip: two launches)
+  clip_adamw    voxelnet_amd.optim.ClipAdamW            (vn_clip_adamw, csrc/optim.hip: two launches)
   torch_foreach clip_grad_norm_ + torch.optim.AdamW(foreach=True)
   torch_fused   clip_grad_norm_ + torch.optim.AdamW(fused=True)
 Per arm and round: ROUND updates back to back between two device events (us per update as the device saw them, host gaps

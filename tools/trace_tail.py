@@ -5,7 +5,7 @@ import csv, sys
 rows = list(csv.DictReader(open(sys.argv[1])))
 win = float(sys.argv[2]) if len(sys.argv) > 2 else 2000.0
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
-idx = [i for i, r in enumerate(rows) if "k_opt_update" in r["Kernel_Name"]]
+idx = [i for i, r in enumerate(rows) if "k_clip_update" in r["Kernel_Name"]]
 b, e = idx[-3], idx[-2]
 t0 = int(rows[b]["End_Timestamp"])
 span = (int(rows[e]["End_Timestamp"]) - t0) / 1e3

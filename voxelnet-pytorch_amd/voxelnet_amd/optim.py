@@ -8,7 +8,8 @@ whatever their placement (the module's flat gradient buffer, the DDP buckets' vi
 No CPU / torch fallback: the HIP library must be present.
 
 `ClipAdamW` is the same tail with torch.optim.AdamW in SGD's place (what SECOND, PointPillars and their successors train
-with): csrc/adamw.hip, `vn_clip_adamw`, again two launches, over (parameter, gradient, exp_avg, exp_avg_sq) chunks."""
+with): the same file's other update rule, `vn_clip_adamw`, again two launches, over (parameter, gradient, exp_avg,
+exp_avg_sq) chunks.  What the two classes share — the chunk table's life and the checks — is `_ClipOptimizer`."""
 import ctypes
 
 import numpy as np
@@ -17,9 +18,112 @@ import torch
 from . import _lib
 
 CHUNK = 4096    # VN_OPT_CHUNK (include/voxelnet_hip.h)
+_SGD_ROW = np.dtype([("param", "<u8"), ("grad", "<u8"), ("n", "<i4"), ("reserved", "<i4")])
+_ADAM_ROW = np.dtype([("param", "<u8"), ("grad", "<u8"), ("exp_avg", "<u8"), ("exp_avg_sq", "<u8"), ("n", "<i4"), ("slot", "<i4")])
+assert _SGD_ROW.itemsize == ctypes.sizeof(_lib.VnParamChunk) and _ADAM_ROW.itemsize == ctypes.sizeof(_lib.VnAdamChunk)
 
 
-class ClipSGD(torch.optim.Optimizer):
+class _ClipOptimizer(torch.optim.Optimizer):
+    """The part of the tail that does not depend on the update rule: a device chunk table of raw pointers, built when the
+    tensors of a step are not those of the step before and dropped (_forget) whenever param_groups or state change hands.
+    A subclass supplies _check_groups(), _prepare(taking, dev) -> the table's rows, and _launch()."""
+
+    def __init__(self, params, defaults):
+        super().__init__(params, defaults)
+        if not any(len(g["params"]) for g in self.param_groups):
+            raise ValueError(f"{type(self).__name__} got an empty parameter list")
+        self._forget()
+
+    def _forget(self):
+        """drop everything derived from param_groups / state: the device chunk table is rebuilt on the next step"""
+        self._key = None
+        self._table = self._ws = self._norm = None
+        self._n_chunks = self._n_elems = 0
+        self._plist = self._last_grads = self._last_pptrs = None
+
+    # (kept for callers of the round-1 class)
+    @property
+    def params(self):
+        return [p for g in self.param_groups for p in g["params"]]
+
+    def __setstate__(self, state):        # unpickling, copy.deepcopy and the tail of load_state_dict
+        super().__setstate__(state)       # (the base class pickles defaults / state / param_groups only)
+        self._forget()
+
+    def add_param_group(self, group):
+        super().add_param_group(group)
+        self._forget()
+
+    def zero_grad(self, set_to_none=True):
+        """torch.optim.Optimizer.zero_grad without its per-parameter foreach bookkeeping (104 small tensors)"""
+        if not set_to_none:
+            return super().zero_grad(set_to_none=False)
+        for p in self.params:
+            p.grad = None
+
+    def _params(self):
+        if self._plist is None:
+            self._plist = self.params
+        return self._plist
+
+    def _check(self, dev, *tensors):
+        if not all(t.is_cuda and t.device == dev for t in tensors):
+            raise _lib.VoxelnetHipError(f"{type(self).__name__}: parameters and gradients must live on one HIP device (no CPU path)")
+        if not all(t.dtype == torch.float32 and t.is_contiguous() for t in tensors):
+            raise _lib.VoxelnetHipError(f"{type(self).__name__}: fp32 contiguous parameters and gradients only")
+
+    @staticmethod
+    def _cut(ptrs, n, last):
+        """the rows of one tensor tuple: its base pointers advanced chunk by chunk, the chunk's length, the last column"""
+        return [tuple(b + 4 * off for b in ptrs) + (min(CHUNK, n - off), last) for off in range(0, n, CHUNK)]
+
+    def _upload(self, rows, dtype, workspace_fn, dev):
+        """table, workspace and norm for `rows`; pointers are stable from step to step (flat gradient buffer): built once"""
+        key = tuple(rows)
+        if key == self._key:
+            return
+        self._table = torch.from_numpy(np.array(rows, dtype=dtype).view(np.uint8).copy()).to(dev)
+        self._n_chunks = len(rows)
+        self._ws = torch.empty(getattr(_lib.load(), workspace_fn)(self._n_chunks), dtype=torch.uint8, device=dev)
+        self._norm = torch.zeros(1, dtype=torch.float32, device=dev)
+        self._key = key
+
+    def _same_tensors(self, plist):
+        """the same gradient tensors as in the previous step (the model's flat buffer / bucket views), the same parameter
+        storage (a `p.data = ...` / `set_()` swap keeps the Parameter object but not its memory) and — no load_state_dict
+        / add_param_group since, which call _forget — the same state tensors: the chunk table of raw pointers is still
+        valid, nothing to rebuild or re-check"""
+        last = self._last_grads
+        return (last is not None and self._table is not None and all(p.grad is g for p, g in zip(plist, last))
+                and self._last_pptrs == [p.data_ptr() for p in plist])
+
+    def _remember(self, plist, grads, n_elems):
+        """`grads`: every parameter's gradient tensor in plist's order, or None when some parameter has none"""
+        self._n_elems = n_elems
+        self._last_grads = grads
+        self._last_pptrs = [p.data_ptr() for p in plist]
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        if closure is not None:
+            raise _lib.VoxelnetHipError(f"{type(self).__name__}.step: closures are not supported")
+        self._check_groups()
+        plist = self._params()
+        if not self._same_tensors(plist):
+            taking = [(i, p) for i, p in enumerate(plist) if p.grad is not None]
+            if not taking:
+                return None
+            dev = taking[0][1].device
+            for _, p in taking:
+                self._check(dev, p, p.grad)
+            self._prepare(taking, dev)
+            self._remember(plist, [p.grad for p in plist] if len(taking) == len(plist) else None,
+                           sum(p.numel() for _, p in taking))
+        self._launch()
+        return self._norm[0]
+
+
+class ClipSGD(_ClipOptimizer):
     """`ClipSGD(params, lr, max_norm).step()` == `clip_grad_norm_(params, max_norm); SGD(params, lr).step()`.
     step() returns the total gradient norm before clipping (a device scalar, clip_grad_norm_'s return value).
 
@@ -29,19 +133,11 @@ class ClipSGD(torch.optim.Optimizer):
     train.py:153 does), so every group must carry the same lr / max_norm."""
 
     def __init__(self, params, lr, max_norm, scale_grads=False):
-        defaults = dict(lr=float(lr), max_norm=float(max_norm), scale_grads=bool(scale_grads))
-        super().__init__(params, defaults)
-        if not any(len(g["params"]) for g in self.param_groups):
-            raise ValueError("ClipSGD got an empty parameter list")
-        self._key = None
-        self._table = self._ws = self._norm = None
-        self._n_chunks = 0
-        self._plist = self._last_grads = self._last_pptrs = self._fused_key = None
+        super().__init__(params, dict(lr=float(lr), max_norm=float(max_norm), scale_grads=bool(scale_grads)))
 
-    # (kept for callers of the round-1 class)
-    @property
-    def params(self):
-        return [p for g in self.param_groups for p in g["params"]]
+    def _forget(self):
+        super()._forget()
+        self._fused_key = None
 
     @property
     def lr(self):
@@ -55,117 +151,54 @@ class ClipSGD(torch.optim.Optimizer):
     def scale_grads(self):
         return bool(self.param_groups[0]["scale_grads"])
 
-    def __setstate__(self, state):        # (the base class pickles defaults / state / param_groups only)
-        super().__setstate__(state)
-        self._key = None                  # device chunk table / workspace: rebuilt on the first step
-        self._table = self._ws = self._norm = None
-        self._n_chunks = 0
-        self._plist = self._last_grads = self._last_pptrs = self._fused_key = None
+    def _one_lr(self):
+        g0 = self.param_groups[0]
+        return all(g["lr"] == g0["lr"] and g["max_norm"] == g0["max_norm"] for g in self.param_groups[1:])
 
-    def zero_grad(self, set_to_none=True):
-        """torch.optim.Optimizer.zero_grad without its per-parameter foreach bookkeeping (104 small tensors)"""
-        if not set_to_none:
-            return super().zero_grad(set_to_none=False)
-        for p in self.params:
-            p.grad = None
+    def _check_groups(self):
+        if not self._one_lr():
+            raise _lib.VoxelnetHipError("ClipSGD: one lr / max_norm for all parameter groups (the clip norm is global)")
 
-    def add_param_group(self, group):
-        super().add_param_group(group)
-        self._plist = self._last_grads = self._last_pptrs = self._fused_key = None
-
-    def _build(self, pairs, dev):
-        rows = []
-        for p, g in pairs:
-            n, pp, gp = p.numel(), p.data_ptr(), g.data_ptr()
-            for off in range(0, n, CHUNK):
-                rows.append((pp + 4 * off, gp + 4 * off, min(CHUNK, n - off), 0))
-        tab = np.array(rows, dtype=np.dtype([("param", "<u8"), ("grad", "<u8"), ("n", "<i4"), ("reserved", "<i4")]))
-        assert tab.dtype.itemsize == ctypes.sizeof(_lib.VnParamChunk)
-        self._table = torch.from_numpy(tab.view(np.uint8).copy()).to(dev)
-        self._n_chunks = len(rows)
-        nbytes = _lib.load().vn_clip_sgd_workspace_bytes(self._n_chunks)
-        self._ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        self._norm = torch.zeros(1, dtype=torch.float32, device=dev)
+    def _prepare(self, taking, dev):
+        rows = [r for _, p in taking for r in self._cut((p.data_ptr(), p.grad.data_ptr()), p.numel(), 0)]
+        self._upload(rows, _SGD_ROW, "vn_clip_sgd_workspace_bytes", dev)
 
     def _step_table(self, params, grads):
         """RPN3D.train_step (vn_net_step): make sure the device chunk table covers exactly the pairs (params[i], grads[i]) —
         the gradients are not attached to the parameters yet, the update runs inside the library call — and that this
         optimizer's parameters are those.  -> True: _table / _ws / _norm are valid for the call; False: use step()."""
-        for g in self.param_groups[1:]:
-            if g["lr"] != self.param_groups[0]["lr"] or g["max_norm"] != self.param_groups[0]["max_norm"]:
-                return False
-        plist = self.__dict__.get("_plist")
-        if plist is None:
-            plist = self._plist = self.params
+        if not self._one_lr():
+            return False
+        plist = self._params()
         pptrs = [p.data_ptr() for p in params]
-        hit = self.__dict__.get("_fused_key")
+        hit = self._fused_key
         if hit is not None and hit[0] is params and hit[1] is grads and hit[2] == pptrs and self._table is not None:
             return True
         if len(plist) != len(params) or {id(p) for p in plist} != {id(p) for p in params}:
             return False
         dev = params[0].device
-        for p, g in zip(params, grads):
-            if not (p.is_cuda and g.is_cuda and p.device == dev and g.device == dev and p.dtype == torch.float32
-                    and g.dtype == torch.float32 and p.is_contiguous() and g.is_contiguous() and p.numel() == g.numel()):
-                return False
+        try:
+            for p, g in zip(params, grads):
+                self._check(dev, p, g)
+        except _lib.VoxelnetHipError:
+            return False
+        if any(p.numel() != g.numel() for p, g in zip(params, grads)):
+            return False
         gmap = {id(p): g for p, g in zip(params, grads)}
-        pairs = [(p, gmap[id(p)]) for p in plist]
-        key = tuple((p.data_ptr(), g.data_ptr(), p.numel()) for p, g in pairs)
-        if key != self._key:
-            self._build(pairs, dev)
-            self._key = key
-        self._n_elems = sum(p.numel() for p in plist)
-        self._last_grads = [gmap[id(p)] for p in plist]      # (step() right after the call would see the same tensors)
-        self._last_pptrs = [p.data_ptr() for p in plist]
+        glist = [gmap[id(p)] for p in plist]
+        rows = [r for p, g in zip(plist, glist) for r in self._cut((p.data_ptr(), g.data_ptr()), p.numel(), 0)]
+        self._upload(rows, _SGD_ROW, "vn_clip_sgd_workspace_bytes", dev)
+        self._remember(plist, glist, sum(p.numel() for p in plist))      # (step() right after the call would see the same tensors)
         self._fused_key = (params, grads, pptrs)
         return True
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        if closure is not None:
-            raise _lib.VoxelnetHipError("ClipSGD.step: closures are not supported")
-        for g in self.param_groups[1:]:
-            if g["lr"] != self.param_groups[0]["lr"] or g["max_norm"] != self.param_groups[0]["max_norm"]:
-                raise _lib.VoxelnetHipError("ClipSGD: one lr / max_norm for all parameter groups (the clip norm is global)")
-        plist = self.__dict__.get("_plist")
-        if plist is None:
-            plist = self._plist = self.params
-        last = self.__dict__.get("_last_grads")
-        if (last is not None and self._table is not None and all(p.grad is g for p, g in zip(plist, last))
-                and self._last_pptrs == [p.data_ptr() for p in plist]):
-            # the same gradient tensors as in the previous step (the model's flat buffer / bucket views) and the same
-            # parameter storage (a `p.data = ...` / `set_()` swap keeps the Parameter object but not its memory): the chunk
-            # table of raw pointers is still valid, nothing to rebuild or re-check
-            with _lib.on_device(self._table.device):
-                stream = _lib.raw_stream()
-                from . import engine as E
-                with E.section("clip_sgd", 16.0 * self._n_elems):
-                    _lib.call("vn_clip_sgd", self._table.data_ptr(), self._n_chunks, self.max_norm, self.lr,
-                              int(self.scale_grads), self._ws.data_ptr(), self._ws.numel(), self._norm.data_ptr(), stream)
-            return self._norm[0]
-        pairs = [(p, p.grad) for p in plist if p.grad is not None]
-        if not pairs:
-            return None
-        dev = pairs[0][0].device
-        for p, g in pairs:
-            if not (p.is_cuda and g.is_cuda and p.device == dev and g.device == dev):
-                raise _lib.VoxelnetHipError("ClipSGD: parameters and gradients must live on one HIP device (no CPU path)")
-            if p.dtype != torch.float32 or g.dtype != torch.float32 or not p.is_contiguous() or not g.is_contiguous():
-                raise _lib.VoxelnetHipError("ClipSGD: fp32 contiguous parameters and gradients only")
-        key = tuple((p.data_ptr(), g.data_ptr(), p.numel()) for p, g in pairs)
-        if key != self._key:
-            self._build(pairs, dev)        # pointers are stable from step to step (flat gradient buffer): built once
-            self._key = key
-        self._n_elems = sum(p.numel() for p, _ in pairs)
-        self._last_grads = [p.grad for p in plist] if len(pairs) == len(plist) else None
-        self._last_pptrs = [p.data_ptr() for p in plist]
-        with _lib.on_device(dev):
+    def _launch(self):
+        with _lib.on_device(self._table.device):
             stream = _lib.raw_stream()
             from . import engine as E
-            with E.section("clip_sgd", 16.0 * sum(p.numel() for p, _ in pairs)):      # grad read twice, param read + written
+            with E.section("clip_sgd", 16.0 * self._n_elems):      # grad read twice, param read + written
                 _lib.call("vn_clip_sgd", self._table.data_ptr(), self._n_chunks, self.max_norm, self.lr, int(self.scale_grads),
                           self._ws.data_ptr(), self._ws.numel(), self._norm.data_ptr(), stream)
-        return self._norm[0]
 
 
 def decay_param_groups(model, weight_decay):
@@ -176,7 +209,7 @@ def decay_param_groups(model, weight_decay):
             {"params": [p for p in params if p.dim() <= 1], "weight_decay": 0.0}]
 
 
-class ClipAdamW(torch.optim.Optimizer):
+class ClipAdamW(_ClipOptimizer):
     """`ClipAdamW(params, lr, betas, eps, weight_decay, max_norm).step()` ==
     `clip_grad_norm_(params, max_norm); torch.optim.AdamW(params, lr, betas, eps, weight_decay).step()` (single-tensor
     rules, amsgrad=False, maximize=False, decoupled decay).  step() returns the total gradient norm before clipping (a
@@ -209,40 +242,17 @@ class ClipAdamW(torch.optim.Optimizer):
         defaults = dict(lr=float(lr), betas=(float(betas[0]), float(betas[1])), eps=float(eps), weight_decay=float(weight_decay),
                         max_norm=float(max_norm), scale_grads=bool(scale_grads))
         super().__init__(params, defaults)
-        if not any(len(g["params"]) for g in self.param_groups):
-            raise ValueError("ClipAdamW got an empty parameter list")
-        self._forget()
 
     def _forget(self):
-        """drop everything derived from param_groups / state: the device chunk table is rebuilt on the next step"""
-        self._key = None
-        self._table = self._ws = self._norm = None
-        self._n_chunks = self._n_elems = 0
-        self._plist = self._pgroup = self._last_grads = self._last_pptrs = None
+        super()._forget()
         self._slots = self._steps = None
         self._hyper = _lib.VnAdamHyper()
 
-    @property
-    def params(self):
-        return [p for g in self.param_groups for p in g["params"]]
-
-    def __setstate__(self, state):        # unpickling, copy.deepcopy and the tail of load_state_dict
+    def __setstate__(self, state):
         super().__setstate__(state)
         for g in self.param_groups:       # (a torch.optim.AdamW state dict has no max_norm / scale_grads)
             for k, v in self.defaults.items():
                 g.setdefault(k, v)
-        self._forget()
-
-    def zero_grad(self, set_to_none=True):
-        """torch.optim.Optimizer.zero_grad without its per-parameter foreach bookkeeping (104 small tensors)"""
-        if not set_to_none:
-            return super().zero_grad(set_to_none=False)
-        for p in self.params:
-            p.grad = None
-
-    def add_param_group(self, group):
-        super().add_param_group(group)
-        self._forget()
 
     def _new_state(self, params):
         """zero moments for `params` as views of ONE flat buffer, each tensor on a 16-byte boundary"""
@@ -256,15 +266,42 @@ class ClipAdamW(torch.optim.Optimizer):
             self.state[p] = {"step": torch.tensor(0.0, dtype=torch.float32),
                              "exp_avg": flat[off:off + n].view_as(p), "exp_avg_sq": flat[total + off:total + off + n].view_as(p)}
 
-    def _build(self, rows, dev):
-        tab = np.array(rows, dtype=np.dtype([("param", "<u8"), ("grad", "<u8"), ("exp_avg", "<u8"), ("exp_avg_sq", "<u8"),
-                                             ("n", "<i4"), ("slot", "<i4")]))
-        assert tab.dtype.itemsize == ctypes.sizeof(_lib.VnAdamChunk)
-        self._table = torch.from_numpy(tab.view(np.uint8).copy()).to(dev)
-        self._n_chunks = len(rows)
-        nbytes = _lib.load().vn_clip_adamw_workspace_bytes(self._n_chunks)
-        self._ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        self._norm = torch.zeros(1, dtype=torch.float32, device=dev)
+    def _check_groups(self):
+        g0 = self.param_groups[0]
+        for g in self.param_groups[1:]:
+            if g["max_norm"] != g0["max_norm"] or bool(g["scale_grads"]) != bool(g0["scale_grads"]):
+                raise _lib.VoxelnetHipError("ClipAdamW: one max_norm / scale_grads for all parameter groups (the clip norm is global)")
+
+    def _prepare(self, taking, dev):
+        fresh = [p for _, p in taking if len(self.state.get(p, ())) == 0]
+        if fresh:
+            self._new_state(fresh)
+        pgroup = [gi for gi, g in enumerate(self.param_groups) for _ in g["params"]]
+        slots, rows, steps = {}, [], []
+        for i, p in taking:
+            st = self.state[p]
+            m, v = st["exp_avg"], st["exp_avg_sq"]
+            for t_ in (m, v):
+                if not (t_.is_cuda and t_.device == dev and t_.dtype == torch.float32 and t_.is_contiguous()
+                        and t_.numel() == p.numel()):
+                    raise _lib.VoxelnetHipError("ClipAdamW: exp_avg / exp_avg_sq must be fp32 contiguous tensors of the "
+                                                "parameter's size on its device")
+            t = int(float(st["step"]))
+            steps.append(float(t))
+            slot = slots.setdefault((pgroup[i], t), len(slots))
+            rows += self._cut((p.data_ptr(), p.grad.data_ptr(), m.data_ptr(), v.data_ptr()), p.numel(), slot)
+        if len(slots) > _lib.VN_OPT_MAX_SLOTS:
+            raise _lib.VoxelnetHipError(
+                f"ClipAdamW: the parameters of this step fall into {len(slots)} distinct (parameter group, step count) "
+                f"combinations, and one call carries at most {_lib.VN_OPT_MAX_SLOTS} hyperparameter sets: use fewer groups, or "
+                "keep the step counts together (parameters skipped for want of a gradient fall behind the others)")
+        self._upload(rows, _ADAM_ROW, "vn_clip_adamw_workspace_bytes", dev)
+        # the step counters of the parameters taking part move into one CPU buffer (one add per step instead of one per
+        # parameter); a counter that arrived through load_state_dict is copied, not aliased
+        self._steps = torch.tensor(steps, dtype=torch.float32)
+        for j, (_, p) in enumerate(taking):
+            self.state[p]["step"] = self._steps[j]
+        self._slots = [[gi, t] for (gi, t) in slots]
 
     def _launch(self):
         """one vn_clip_adamw call for the slots of the current table, hyperparameters as param_groups hold them NOW; then
@@ -287,72 +324,3 @@ class ClipAdamW(torch.optim.Optimizer):
         for s in self._slots:
             s[1] += 1
         self._steps += 1          # every taking-part parameter's state["step"] is a view of this CPU buffer
-
-    @torch.no_grad()
-    def step(self, closure=None):
-        if closure is not None:
-            raise _lib.VoxelnetHipError("ClipAdamW.step: closures are not supported")
-        g0 = self.param_groups[0]
-        for g in self.param_groups[1:]:
-            if g["max_norm"] != g0["max_norm"] or bool(g["scale_grads"]) != bool(g0["scale_grads"]):
-                raise _lib.VoxelnetHipError("ClipAdamW: one max_norm / scale_grads for all parameter groups (the clip norm is global)")
-        plist = self._plist
-        if plist is None:
-            plist = self._plist = self.params
-            self._pgroup = [gi for gi, g in enumerate(self.param_groups) for _ in g["params"]]
-        last = self._last_grads
-        if (last is not None and self._table is not None and all(p.grad is g for p, g in zip(plist, last))
-                and self._last_pptrs == [p.data_ptr() for p in plist]):
-            # the same gradient tensors as in the previous step (the model's flat buffer / bucket views), the same parameter
-            # storage and — no load_state_dict / add_param_group since, which call _forget — the same state tensors: the
-            # chunk table of raw pointers is still valid and every step count went up by one together
-            self._launch()
-            return self._norm[0]
-        pairs = [(i, p) for i, p in enumerate(plist) if p.grad is not None]
-        if not pairs:
-            return None
-        dev = pairs[0][1].device
-        for _, p in pairs:
-            g = p.grad
-            if not (p.is_cuda and g.is_cuda and p.device == dev and g.device == dev):
-                raise _lib.VoxelnetHipError("ClipAdamW: parameters and gradients must live on one HIP device (no CPU path)")
-            if p.dtype != torch.float32 or g.dtype != torch.float32 or not p.is_contiguous() or not g.is_contiguous():
-                raise _lib.VoxelnetHipError("ClipAdamW: fp32 contiguous parameters and gradients only")
-        fresh = [p for _, p in pairs if len(self.state.get(p, ())) == 0]
-        if fresh:
-            self._new_state(fresh)
-        slots, rows, steps = {}, [], []
-        for i, p in pairs:
-            st = self.state[p]
-            m, v = st["exp_avg"], st["exp_avg_sq"]
-            for t_ in (m, v):
-                if not (t_.is_cuda and t_.device == dev and t_.dtype == torch.float32 and t_.is_contiguous()
-                        and t_.numel() == p.numel()):
-                    raise _lib.VoxelnetHipError("ClipAdamW: exp_avg / exp_avg_sq must be fp32 contiguous tensors of the "
-                                                "parameter's size on its device")
-            t = int(float(st["step"]))
-            steps.append(float(t))
-            slot = slots.setdefault((self._pgroup[i], t), len(slots))
-            n, pp, gp, mp, vp = p.numel(), p.data_ptr(), p.grad.data_ptr(), m.data_ptr(), v.data_ptr()
-            for off in range(0, n, CHUNK):
-                rows.append((pp + 4 * off, gp + 4 * off, mp + 4 * off, vp + 4 * off, min(CHUNK, n - off), slot))
-        if len(slots) > _lib.VN_OPT_MAX_SLOTS:
-            raise _lib.VoxelnetHipError(
-                f"ClipAdamW: the parameters of this step fall into {len(slots)} distinct (parameter group, step count) "
-                f"combinations, and one call carries at most {_lib.VN_OPT_MAX_SLOTS} hyperparameter sets: use fewer groups, or "
-                "keep the step counts together (parameters skipped for want of a gradient fall behind the others)")
-        key = tuple(rows)
-        if key != self._key:
-            self._build(rows, dev)        # pointers are stable from step to step (flat gradient buffer): built once
-            self._key = key
-        # the step counters of the parameters taking part move into one CPU buffer (one add per step instead of one per
-        # parameter); a counter that arrived through load_state_dict is copied, not aliased
-        self._steps = torch.tensor(steps, dtype=torch.float32)
-        for j, (_, p) in enumerate(pairs):
-            self.state[p]["step"] = self._steps[j]
-        self._slots = [[gi, t] for (gi, t) in slots]
-        self._n_elems = sum(p.numel() for _, p in pairs)
-        self._last_grads = [p.grad for p in plist] if len(pairs) == len(plist) else None
-        self._last_pptrs = [p.data_ptr() for p in plist]
-        self._launch()
-        return self._norm[0]
