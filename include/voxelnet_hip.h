@@ -969,6 +969,52 @@ size_t vn_clip_adamw_workspace_bytes(int32_t n_chunks);
 int vn_clip_adamw(const vnAdamChunk *chunks, int32_t n_chunks, const vnAdamHyper *hyper, float max_norm,
                   int32_t scale_grads, void *workspace, size_t workspace_bytes, float *total_norm, vnStream stream);
 
+/* ---- exponential moving average of the weights (timm ModelEmaV2, torch.optim.swa_utils) --------
+ *     ema = lerp(ema, x, weight),  weight = 1 - decay, handed over by value (the schedule is the caller's)
+ * with torch.lerp's rounding: d = x - ema;  weight < 0.5: fmaf(weight, d, ema);  otherwise: fmaf(-d, 1 - weight, x) — the
+ * form the AdamW rule uses for exp_avg, one piece of code for both.  weight = 1 copies x, weight = 0 keeps ema (finite
+ * values).  Three entry points:
+ * vn_ema_update: ONE launch over a DEVICE table of (source, shadow) pieces of at most VN_OPT_CHUNK fp32 elements, one
+ *   workgroup per piece, no workspace.  For what no update rule touches (BatchNorm running statistics, parameters without
+ *   a gradient) and for callers with an optimizer of their own.
+ * vn_clip_sgd_ema / vn_clip_adamw_ema: vn_clip_sgd / vn_clip_adamw with one more pointer per chunk; the second launch
+ *   averages the parameter value it has just computed (from the register: not read again) into `ema`.  p, the moments,
+ *   the stored gradients and total_norm are those of the plain entry points bit for bit, and the shadow is what
+ *   vn_ema_update over the same tensors right after the plain call gives, bit for bit.  Workspace: that of
+ *   vn_clip_sgd_workspace_bytes / vn_clip_adamw_workspace_bytes.
+ * A piece whose `ema` (or, for vn_ema_update, `src`) is NULL is left out of the average.  16-byte accesses where every
+ * pointer of the piece allows them, element by element otherwise.
+ * VN_EINVAL (before any HIP call): what the plain entry point refuses; a weight outside [0,1] or NaN; for vn_ema_update a
+ * NULL chunks or n_chunks <= 0.  Asynchronous. */
+typedef struct vnEmaChunk {
+    const float *src;
+    float *ema;
+    int32_t n;          /* elements in this piece, 1..VN_OPT_CHUNK */
+    int32_t reserved;
+} vnEmaChunk;
+typedef struct vnParamChunkEma {
+    float *param;
+    float *grad;
+    float *ema;         /* NULL: no average for this piece */
+    int32_t n;          /* elements in this piece, 1..VN_OPT_CHUNK */
+    int32_t reserved;
+} vnParamChunkEma;
+typedef struct vnAdamChunkEma {
+    float *param;
+    float *grad;
+    float *exp_avg;
+    float *exp_avg_sq;
+    float *ema;         /* NULL: no average for this piece */
+    int32_t n;          /* elements in this piece, 1..VN_OPT_CHUNK */
+    int32_t slot;       /* index into vnAdamHyper.slot */
+} vnAdamChunkEma;
+int vn_ema_update(const vnEmaChunk *chunks, int32_t n_chunks, float weight, vnStream stream);
+int vn_clip_sgd_ema(const vnParamChunkEma *chunks, int32_t n_chunks, float max_norm, float lr, int32_t scale_grads,
+                    float ema_weight, void *workspace, size_t workspace_bytes, float *total_norm, vnStream stream);
+int vn_clip_adamw_ema(const vnAdamChunkEma *chunks, int32_t n_chunks, const vnAdamHyper *hyper, float max_norm,
+                      int32_t scale_grads, float ema_weight, void *workspace, size_t workspace_bytes, float *total_norm,
+                      vnStream stream);
+
 /* ---- RPN training targets (voxelnet/utils.py:376-473 generate_targets, :344-373 bbox_iou, :213-227
  * anchor_to_standup_box2d; called by RPN3D.forward, voxelnet/model.py:309) -------------------------------
  * Per sample b: gt_count[b] ground-truth boxes in lidar coordinates, gt [B,max_gt,7] = (x,y,z,h,w,l,r) float64 and

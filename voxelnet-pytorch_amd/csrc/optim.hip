@@ -19,12 +19,17 @@
 // or beta1 costs no device table rebuild and no copy.
 // HBM-bound: 4 B read per element in the first pass; in the second 12 B for SGD (g read, p read+write) and 28 B for AdamW
 // (g, p, m, v read; p, m, v written), +4 when the scaled gradients are written back.
+// Weight average: ema = lerp(ema, p, w), w = 1 - decay by value.  Each rule has an Ema flavour (vn_clip_sgd_ema,
+// vn_clip_adamw_ema) whose chunks carry the shadow's pointer and whose apply<V> averages the parameter it has just computed:
+// +8 B per element in the second launch (20 B SGD, 36 B AdamW) against 12 B and a launch for a pass of its own; k_clip_sumsq
+// and the head of k_clip_update are the same code.  vn_ema_update (k_ema_update) is that pass, for what no rule touches.
 // Sums: fp32 per thread -> one fp32 partial per chunk -> every workgroup of the second kernel adds the partials in
 // double in the same fixed order (deterministic, no atomics, no third launch).
 #include "common.h"
 
 #include <charconv>
 #include <cmath>
+#include <type_traits>
 
 namespace {
 
@@ -97,27 +102,54 @@ __global__ void __launch_bounds__(OPT_THREADS) k_clip_update(const typename Rule
     // inside a flat buffer)
     if (Rule::aligned(c)) {
         const int n4 = c.n >> 2;
-        for (int i = threadIdx.x; i < n4; i += OPT_THREADS) Rule::template apply<float4>(c, i, coef, h, scale_grads);
-        for (int i = (n4 << 2) + threadIdx.x; i < c.n; i += OPT_THREADS) Rule::template apply<float>(c, i, coef, h, scale_grads);
+        for (int i = threadIdx.x; i < n4; i += OPT_THREADS) rule.template apply<float4>(c, i, coef, h, scale_grads);
+        for (int i = (n4 << 2) + threadIdx.x; i < c.n; i += OPT_THREADS) rule.template apply<float>(c, i, coef, h, scale_grads);
     } else {
-        for (int i = threadIdx.x; i < c.n; i += OPT_THREADS) Rule::template apply<float>(c, i, coef, h, scale_grads);
+        for (int i = threadIdx.x; i < c.n; i += OPT_THREADS) rule.template apply<float>(c, i, coef, h, scale_grads);
     }
 }
 
-struct SgdRule {
-    using Chunk = vnParamChunk;
+// lerp(a, b, w) = a + w * (b - a) with the roundings of torch's device kernel for lerp_: contracted, and the other form
+// from weight 0.5 on.  AdamW's exp_avg and the weight average (vn_ema_update, the Ema rules) are this one function.
+__device__ __forceinline__ float lerp_element(float a, float b, float w) {
+    const float d = b - a;
+    return w < 0.5f ? fmaf(w, d, a) : fmaf(-d, 1.f - w, b);
+}
+
+// The Ema flavour of a rule: its chunk carries one more pointer, its kernel argument one more float (the average's
+// weight), and apply<V> averages the parameter value it holds in a register into the shadow: one load and one store more.
+// A NULL shadow (device data, looked at per chunk) leaves the average out.  The plain flavour has neither the member nor
+// the code: its instantiations are what they were before the average existed.
+template <bool Ema> struct EmaWeight {};
+template <> struct EmaWeight<true> { float ema_w; };
+
+template <class V> __device__ __forceinline__ void ema_store(float *ema, int i, const V &pv, float w) {
+    if (!ema) return;
+    V *__restrict__ e = reinterpret_cast<V *>(ema);
+    V ev = e[i], xv = pv;
+    per_lane([=](float &e1, float &x1) { e1 = lerp_element(e1, x1, w); }, ev, xv);
+    e[i] = ev;
+}
+
+template <bool Ema> struct SgdRuleT : EmaWeight<Ema> {
+    using Chunk = std::conditional_t<Ema, vnParamChunkEma, vnParamChunk>;
     float lr;
     __device__ float bind(const Chunk &) const { return lr; }
-    static __device__ bool aligned(const Chunk &c) { return aligned16(c.param, c.grad); }
-    template <class V> static __device__ void apply(const Chunk &c, int i, float coef, float lr, int scale_grads) {
+    static __device__ bool aligned(const Chunk &c) {
+        if constexpr (Ema) return aligned16(c.param, c.grad, c.ema);
+        else return aligned16(c.param, c.grad);
+    }
+    template <class V> __device__ void apply(const Chunk &c, int i, float coef, float lr, int scale_grads) const {
         V *__restrict__ p = reinterpret_cast<V *>(c.param);
         V *__restrict__ g = reinterpret_cast<V *>(c.grad);
         V gv = g[i], pv = p[i];
         per_lane([=](float &g1, float &p1) { g1 *= coef; p1 -= lr * g1; }, gv, pv);
         p[i] = pv;
         if (scale_grads) g[i] = gv;
+        if constexpr (Ema) ema_store<V>(c.ema, i, pv, this->ema_w);
     }
 };
+using SgdRule = SgdRuleT<false>;
 
 struct AdamSlotK {          // one slot as the kernel wants it
     float neg_step_size;    // -lr / (1 - beta1^t)
@@ -139,21 +171,23 @@ struct AdamSlotK {          // one slot as the kernel wants it
 __device__ __forceinline__ void adam_element(float &p, float &g, float &m, float &v, float coef, const AdamSlotK &h) {
     g *= coef;
     p *= h.decay;
-    const float d = g - m;
-    m = h.omb1 < 0.5f ? fmaf(h.omb1, d, m) : fmaf(-d, 1.f - h.omb1, g);
+    m = lerp_element(m, g, h.omb1);
     v = fmaf(h.omb2 * g, g, h.beta2 * v);
     const float denom = sqrtf(v) * h.inv_bc2_sqrt + h.eps;
     p = fmaf(h.neg_step_size, m / denom, p);
 }
 
-struct AdamRule {
-    using Chunk = vnAdamChunk;
+template <bool Ema> struct AdamRuleT : EmaWeight<Ema> {
+    using Chunk = std::conditional_t<Ema, vnAdamChunkEma, vnAdamChunk>;
     AdamSlotK slot[VN_OPT_MAX_SLOTS];
     int n_slots;
     // the slot index is device data: clamped, never trusted
     __device__ AdamSlotK bind(const Chunk &c) const { return slot[c.slot < 0 ? 0 : (c.slot >= n_slots ? n_slots - 1 : c.slot)]; }
-    static __device__ bool aligned(const Chunk &c) { return aligned16(c.param, c.grad, c.exp_avg, c.exp_avg_sq); }
-    template <class V> static __device__ void apply(const Chunk &c, int i, float coef, const AdamSlotK &h, int scale_grads) {
+    static __device__ bool aligned(const Chunk &c) {
+        if constexpr (Ema) return aligned16(c.param, c.grad, c.exp_avg, c.exp_avg_sq, c.ema);
+        else return aligned16(c.param, c.grad, c.exp_avg, c.exp_avg_sq);
+    }
+    template <class V> __device__ void apply(const Chunk &c, int i, float coef, const AdamSlotK &h, int scale_grads) const {
         V *__restrict__ p = reinterpret_cast<V *>(c.param);
         V *__restrict__ g = reinterpret_cast<V *>(c.grad);
         V *__restrict__ m = reinterpret_cast<V *>(c.exp_avg);
@@ -164,8 +198,24 @@ struct AdamRule {
         m[i] = mv;
         v[i] = vv;
         if (scale_grads) g[i] = gv;
+        if constexpr (Ema) ema_store<V>(c.ema, i, pv, this->ema_w);
     }
 };
+using AdamRule = AdamRuleT<false>;
+
+// the average alone: one workgroup per (source, shadow) piece
+__global__ void __launch_bounds__(OPT_THREADS) k_ema_update(const vnEmaChunk *__restrict__ chunks, float w) {
+    const vnEmaChunk c = chunks[blockIdx.x];
+    if (!c.src || !c.ema) return;
+    const float *__restrict__ x = c.src;
+    if (aligned16(c.src, c.ema)) {
+        const int n4 = c.n >> 2;
+        for (int i = threadIdx.x; i < n4; i += OPT_THREADS) ema_store<float4>(c.ema, i, reinterpret_cast<const float4 *>(x)[i], w);
+        for (int i = (n4 << 2) + threadIdx.x; i < c.n; i += OPT_THREADS) ema_store<float>(c.ema, i, x[i], w);
+    } else {
+        for (int i = threadIdx.x; i < c.n; i += OPT_THREADS) ema_store<float>(c.ema, i, x[i], w);
+    }
+}
 
 size_t workspace_bytes(int32_t n_chunks) {      // one fp32 partial per chunk
     if (n_chunks <= 0) return 0;
@@ -199,21 +249,9 @@ double widen(float x) {
     return d;
 }
 
-}  // namespace
-
-extern "C" size_t vn_clip_sgd_workspace_bytes(int32_t n_chunks) { return workspace_bytes(n_chunks); }
-extern "C" size_t vn_clip_adamw_workspace_bytes(int32_t n_chunks) { return workspace_bytes(n_chunks); }
-
-extern "C" int vn_clip_sgd(const vnParamChunk *chunks, int32_t n_chunks, float max_norm, float lr, int32_t scale_grads,
-                           void *workspace, size_t workspace_bytes, float *total_norm, vnStream stream) {
-    return clip_update(chunks, n_chunks, max_norm, SgdRule{lr}, scale_grads, workspace, workspace_bytes, total_norm, stream);
-}
-
-extern "C" int vn_clip_adamw(const vnAdamChunk *chunks, int32_t n_chunks, const vnAdamHyper *hyper, float max_norm,
-                             int32_t scale_grads, void *workspace, size_t workspace_bytes, float *total_norm,
-                             vnStream stream) {
+// vnAdamHyper -> the rule's slots (checks first; the scalars in double, see widen)
+template <class Rule> int adam_slots(const vnAdamHyper *hyper, Rule &rule) {
     VN_CHECK_ARG(hyper && hyper->n_slots >= 1 && hyper->n_slots <= VN_OPT_MAX_SLOTS);
-    AdamRule rule = {};
     rule.n_slots = hyper->n_slots;
     for (int i = 0; i < hyper->n_slots; ++i) {
         const vnAdamSlot &s = hyper->slot[i];
@@ -231,5 +269,51 @@ extern "C" int vn_clip_adamw(const vnAdamChunk *chunks, int32_t n_chunks, const 
         k.inv_bc2_sqrt = 1.f / (float)std::sqrt(bc2);
         k.eps = s.eps;
     }
+    return VN_OK;
+}
+
+}  // namespace
+
+extern "C" size_t vn_clip_sgd_workspace_bytes(int32_t n_chunks) { return workspace_bytes(n_chunks); }
+extern "C" size_t vn_clip_adamw_workspace_bytes(int32_t n_chunks) { return workspace_bytes(n_chunks); }
+
+extern "C" int vn_clip_sgd(const vnParamChunk *chunks, int32_t n_chunks, float max_norm, float lr, int32_t scale_grads,
+                           void *workspace, size_t workspace_bytes, float *total_norm, vnStream stream) {
+    SgdRule rule = {};
+    rule.lr = lr;
+    return clip_update(chunks, n_chunks, max_norm, rule, scale_grads, workspace, workspace_bytes, total_norm, stream);
+}
+
+extern "C" int vn_clip_sgd_ema(const vnParamChunkEma *chunks, int32_t n_chunks, float max_norm, float lr, int32_t scale_grads,
+                               float ema_weight, void *workspace, size_t workspace_bytes, float *total_norm, vnStream stream) {
+    VN_CHECK_ARG(ema_weight >= 0.f && ema_weight <= 1.f);          // (a NaN fails both)
+    SgdRuleT<true> rule = {};
+    rule.lr = lr;
+    rule.ema_w = ema_weight;
+    return clip_update(chunks, n_chunks, max_norm, rule, scale_grads, workspace, workspace_bytes, total_norm, stream);
+}
+
+extern "C" int vn_ema_update(const vnEmaChunk *chunks, int32_t n_chunks, float weight, vnStream stream) {
+    VN_CHECK_ARG(chunks && n_chunks > 0 && weight >= 0.f && weight <= 1.f);
+    k_ema_update<<<n_chunks, OPT_THREADS, 0, vn_stream(stream)>>>(chunks, weight);
+    VN_LAUNCH_STATUS();
+    return VN_OK;
+}
+
+extern "C" int vn_clip_adamw(const vnAdamChunk *chunks, int32_t n_chunks, const vnAdamHyper *hyper, float max_norm,
+                             int32_t scale_grads, void *workspace, size_t workspace_bytes, float *total_norm,
+                             vnStream stream) {
+    AdamRule rule = {};
+    if (const int st = adam_slots(hyper, rule)) return st;
+    return clip_update(chunks, n_chunks, max_norm, rule, scale_grads, workspace, workspace_bytes, total_norm, stream);
+}
+
+extern "C" int vn_clip_adamw_ema(const vnAdamChunkEma *chunks, int32_t n_chunks, const vnAdamHyper *hyper, float max_norm,
+                                 int32_t scale_grads, float ema_weight, void *workspace, size_t workspace_bytes,
+                                 float *total_norm, vnStream stream) {
+    VN_CHECK_ARG(ema_weight >= 0.f && ema_weight <= 1.f);          // (a NaN fails both)
+    AdamRuleT<true> rule = {};
+    rule.ema_w = ema_weight;
+    if (const int st = adam_slots(hyper, rule)) return st;
     return clip_update(chunks, n_chunks, max_norm, rule, scale_grads, workspace, workspace_bytes, total_norm, stream);
 }

@@ -99,6 +99,18 @@ class VnAdamHyper(ctypes.Structure):   # vnAdamHyper: HOST memory, read during t
     _fields_ = [("n_slots", c_i32), ("slot", VnAdamSlot * VN_OPT_MAX_SLOTS)]
 
 
+class VnEmaChunk(ctypes.Structure):   # vnEmaChunk (vn_ema_update): one row of the device table, 24 bytes
+    _fields_ = [("src", c_vp), ("ema", c_vp), ("n", c_i32), ("reserved", c_i32)]
+
+
+class VnParamChunkEma(ctypes.Structure):   # vnParamChunkEma (vn_clip_sgd_ema), 32 bytes
+    _fields_ = [("param", c_vp), ("grad", c_vp), ("ema", c_vp), ("n", c_i32), ("reserved", c_i32)]
+
+
+class VnAdamChunkEma(ctypes.Structure):   # vnAdamChunkEma (vn_clip_adamw_ema), 48 bytes
+    _fields_ = [("param", c_vp), ("grad", c_vp), ("exp_avg", c_vp), ("exp_avg_sq", c_vp), ("ema", c_vp), ("n", c_i32), ("slot", c_i32)]
+
+
 VN_LOSS_BCE, VN_LOSS_FOCAL = 0, 1       # vnLossSpec.cls_kind
 
 
@@ -298,6 +310,9 @@ SIGNATURES = {
     "vn_clip_sgd": (c_i32, [c_vp, c_i32, c_f32, c_f32, c_i32, c_vp, c_sz, c_vp, c_vp]),
     "vn_clip_adamw_workspace_bytes": (c_sz, [c_i32]),
     "vn_clip_adamw": (c_i32, [c_vp, c_i32, _P(VnAdamHyper), c_f32, c_i32, c_vp, c_sz, c_vp, c_vp]),
+    "vn_ema_update": (c_i32, [c_vp, c_i32, c_f32, c_vp]),
+    "vn_clip_sgd_ema": (c_i32, [c_vp, c_i32, c_f32, c_f32, c_i32, c_f32, c_vp, c_sz, c_vp, c_vp]),
+    "vn_clip_adamw_ema": (c_i32, [c_vp, c_i32, _P(VnAdamHyper), c_f32, c_i32, c_f32, c_vp, c_sz, c_vp, c_vp]),
 }
 
 _lib = None

@@ -14,6 +14,7 @@ parameters and buffers (identical init and state_dict keys); their ATen forwards
 never called — every forward/backward goes through the C ABI via the
 torch.autograd.Functions below.  There is no CPU path: CPU tensors raise.
 """
+import contextlib
 import ctypes
 import os
 
@@ -1087,15 +1088,17 @@ class RPN3D(nn.Module):
             self.anchors = dec.anchors
         return dec
 
-    def evaluate(self, batches, device, evaluator=None, decoder=None, decode=None):
+    def evaluate(self, batches, device, evaluator=None, decoder=None, decode=None, ema=None):
         """The validation loop a user would otherwise write around `predict`: every batch tuple of `batches` (the
         7-tuples forward takes; x[1] = label lines) goes through an eval-mode, no_grad forward, BoxDecoder.decode_device
         and evaluator.update — the maps, the decoded boxes and the matching stay on the device, nothing is waited for
         until the caller asks the returned evaluator to compute().  evaluator: an evaluate.DetectionEvaluator (default:
         a new one for this class); decoder: a predict.BoxDecoder (default: the module's own, full anchor grid); decode: a dict of
         BoxDecoder.decode_device keyword arguments (e.g. predict.EVAL_DECODE: a pre-NMS top-K and the rotated NMS; None:
-        the reference's tail); the post-NMS cap is always evaluator.top_k.  The module is back in the mode it was in
-        afterwards."""
+        the reference's tail); the post-NMS cap is always evaluator.top_k.  ema: an ema.ModelEMA of this module — the loop then
+        runs inside `ema.applied()`, i.e. scores the averaged weights (and averaged running statistics); the eval forward
+        reads the parameters afresh at every call (weights are packed per forward, nothing is cached from their values), so
+        the exchange needs no invalidation.  The module is back in the mode it was in afterwards, and holds its own weights."""
         from .evaluate import DetectionEvaluator
         device = torch.device(device)
         if evaluator is None:
@@ -1104,10 +1107,12 @@ class RPN3D(nn.Module):
         kw = dict(decode or {})
         if "top_k" in kw:
             raise ValueError("evaluate: the post-NMS cap is evaluator.top_k; `decode` may not set top_k")
+        if ema is not None and ema.model is not self:
+            raise ValueError("evaluate: `ema` averages another module")
         was_training = self.training
         self.eval()
         try:
-            with torch.no_grad():
+            with torch.no_grad(), (ema.applied() if ema is not None else contextlib.nullcontext()):
                 for x in batches:
                     prob, delta = self.detect(_parts_to(x[2], device), _parts_to(x[4], device))
                     evaluator.update(*dec.decode_device(prob, delta, top_k=evaluator.top_k, **kw), x[1])
@@ -1249,7 +1254,8 @@ class RPN3D(nn.Module):
         Returns the tuple forward() returns (tensors without an autograd graph: the backward has already run); the
         parameters' .grad are set as backward() leaves them.  optimizer: a ClipSGD (its update runs inside the call when no
         gradient reducer is attached, after the reducer's exchange otherwise), a ClipAdamW (the call runs without a parameter
-        update and optimizer.step() follows on the same stream, after the reducer's exchange) or None (no update).
+        update and optimizer.step() follows on the same stream, after the reducer's exchange) or None (no update).  With a
+        weight average attached to the optimizer (optim.attach_ema) a ClipSGD steps after the call too, same parameters.
         Whatever the fused call does not cover — per-layer orchestration, eval mode, target_fn, gradient accumulation, a
         reducer without a communication stream, bench.py's per-section timer — takes the separate calls, same results."""
         from .optim import ClipSGD
@@ -1344,7 +1350,8 @@ class RPN3D(nn.Module):
                 grads = (views, [views[n] for n, _ in self._named_params_in_flat_order()])
                 self.__dict__["_mg_cache"] = grads
             out_grads = grads[1]
-            # (only ClipSGD's update is part of vnStep; a ClipAdamW steps after the call)
+            # (only a plain ClipSGD's update is part of vnStep; a ClipAdamW, and a ClipSGD with a weight average attached —
+            # _step_table answers False —, step after the call)
             inside = isinstance(optimizer, ClipSGD) and red is None and optimizer._step_table(plist, out_grads)
             if inside:
                 a.chunks, a.n_chunks = optimizer._table.data_ptr(), optimizer._n_chunks

@@ -9,7 +9,10 @@ No CPU / torch fallback: the HIP library must be present.
 
 `ClipAdamW` is the same tail with torch.optim.AdamW in SGD's place (what SECOND, PointPillars and their successors train
 with): the same file's other update rule, `vn_clip_adamw`, again two launches, over (parameter, gradient, exp_avg,
-exp_avg_sq) chunks.  What the two classes share — the chunk table's life and the checks — is `_ClipOptimizer`."""
+exp_avg_sq) chunks.  What the two classes share — the chunk table's life and the checks — is `_ClipOptimizer`.
+
+Either class takes a weight average along (`attach_ema`, voxelnet_amd/ema.py): the chunks then carry the shadow's pointer
+and the second launch averages the parameter it has just computed (`vn_clip_sgd_ema`, `vn_clip_adamw_ema`)."""
 import ctypes
 
 import numpy as np
@@ -21,12 +24,19 @@ CHUNK = 4096    # VN_OPT_CHUNK (include/voxelnet_hip.h)
 _SGD_ROW = np.dtype([("param", "<u8"), ("grad", "<u8"), ("n", "<i4"), ("reserved", "<i4")])
 _ADAM_ROW = np.dtype([("param", "<u8"), ("grad", "<u8"), ("exp_avg", "<u8"), ("exp_avg_sq", "<u8"), ("n", "<i4"), ("slot", "<i4")])
 assert _SGD_ROW.itemsize == ctypes.sizeof(_lib.VnParamChunk) and _ADAM_ROW.itemsize == ctypes.sizeof(_lib.VnAdamChunk)
+_SGD_EMA_ROW = np.dtype([("param", "<u8"), ("grad", "<u8"), ("ema", "<u8"), ("n", "<i4"), ("reserved", "<i4")])
+_ADAM_EMA_ROW = np.dtype([("param", "<u8"), ("grad", "<u8"), ("exp_avg", "<u8"), ("exp_avg_sq", "<u8"), ("ema", "<u8"), ("n", "<i4"),
+                          ("slot", "<i4")])
+assert _SGD_EMA_ROW.itemsize == ctypes.sizeof(_lib.VnParamChunkEma)
+assert _ADAM_EMA_ROW.itemsize == ctypes.sizeof(_lib.VnAdamChunkEma)
 
 
 class _ClipOptimizer(torch.optim.Optimizer):
     """The part of the tail that does not depend on the update rule: a device chunk table of raw pointers, built when the
     tensors of a step are not those of the step before and dropped (_forget) whenever param_groups or state change hands.
     A subclass supplies _check_groups(), _prepare(taking, dev) -> the table's rows, and _launch()."""
+
+    _ema = None       # an attached ema.ModelEMA (class-level default: the attachment does not travel with a pickle / deepcopy)
 
     def __init__(self, params, defaults):
         super().__init__(params, defaults)
@@ -40,6 +50,26 @@ class _ClipOptimizer(torch.optim.Optimizer):
         self._table = self._ws = self._norm = None
         self._n_chunks = self._n_elems = 0
         self._plist = self._last_grads = self._last_pptrs = None
+        self._ema_rest = None
+
+    def attach_ema(self, ema):
+        """Average the weights into `ema` (an ema.ModelEMA, or None to detach) as part of every step(): the parameters that
+        take part in the step inside the update's second launch, every other shadowed tensor (BatchNorm running statistics,
+        parameters without a gradient this step) by one vn_ema_update launch on the same stream right after — so each
+        shadowed tensor is averaged once per step, with one weight.  A step() that finds no gradient at all does nothing,
+        the average included.  The attachment is not part of state_dict(): attach again after loading into a new optimizer."""
+        if self._ema is not None:
+            self._ema._optimizer = None
+        self._ema = ema
+        if ema is not None:
+            if ema._optimizer is not None and ema._optimizer is not self:
+                ema._optimizer.attach_ema(None)
+            ema._optimizer = self
+        self._forget()
+
+    def _ema_rows(self, taking, dev):
+        """the attached average's side of _prepare: the follow-up launch's table for what `taking` leaves out"""
+        self._ema_rest = self._ema._rest_table([p for _, p in taking if self._ema.shadow(p) is not None], dev)
 
     # (kept for callers of the round-1 class)
     @property
@@ -74,8 +104,9 @@ class _ClipOptimizer(torch.optim.Optimizer):
 
     @staticmethod
     def _cut(ptrs, n, last):
-        """the rows of one tensor tuple: its base pointers advanced chunk by chunk, the chunk's length, the last column"""
-        return [tuple(b + 4 * off for b in ptrs) + (min(CHUNK, n - off), last) for off in range(0, n, CHUNK)]
+        """the rows of one tensor tuple: its base pointers advanced chunk by chunk (a 0 — no shadow — stays 0), the chunk's
+        length, the last column"""
+        return [tuple(b and b + 4 * off for b in ptrs) + (min(CHUNK, n - off), last) for off in range(0, n, CHUNK)]
 
     def _upload(self, rows, dtype, workspace_fn, dev):
         """table, workspace and norm for `rows`; pointers are stable from step to step (flat gradient buffer): built once"""
@@ -160,14 +191,21 @@ class ClipSGD(_ClipOptimizer):
             raise _lib.VoxelnetHipError("ClipSGD: one lr / max_norm for all parameter groups (the clip norm is global)")
 
     def _prepare(self, taking, dev):
-        rows = [r for _, p in taking for r in self._cut((p.data_ptr(), p.grad.data_ptr()), p.numel(), 0)]
-        self._upload(rows, _SGD_ROW, "vn_clip_sgd_workspace_bytes", dev)
+        ema = self._ema
+        if ema is None:
+            rows = [r for _, p in taking for r in self._cut((p.data_ptr(), p.grad.data_ptr()), p.numel(), 0)]
+            self._upload(rows, _SGD_ROW, "vn_clip_sgd_workspace_bytes", dev)
+            return
+        self._ema_rows(taking, dev)          # (first: it checks that the shadow lives on `dev`)
+        rows = [r for _, p in taking for r in self._cut((p.data_ptr(), p.grad.data_ptr(), ema._shadow_ptr(p)), p.numel(), 0)]
+        self._upload(rows, _SGD_EMA_ROW, "vn_clip_sgd_workspace_bytes", dev)
 
     def _step_table(self, params, grads):
         """RPN3D.train_step (vn_net_step): make sure the device chunk table covers exactly the pairs (params[i], grads[i]) —
         the gradients are not attached to the parameters yet, the update runs inside the library call — and that this
-        optimizer's parameters are those.  -> True: _table / _ws / _norm are valid for the call; False: use step()."""
-        if not self._one_lr():
+        optimizer's parameters are those.  -> True: _table / _ws / _norm are valid for the call; False: use step().
+        vnStep carries the plain table only: with a weight average attached the update runs after the call."""
+        if not self._one_lr() or self._ema is not None:
             return False
         plist = self._params()
         pptrs = [p.data_ptr() for p in params]
@@ -196,9 +234,17 @@ class ClipSGD(_ClipOptimizer):
         with _lib.on_device(self._table.device):
             stream = _lib.raw_stream()
             from . import engine as E
-            with E.section("clip_sgd", 16.0 * self._n_elems):      # grad read twice, param read + written
-                _lib.call("vn_clip_sgd", self._table.data_ptr(), self._n_chunks, self.max_norm, self.lr, int(self.scale_grads),
-                          self._ws.data_ptr(), self._ws.numel(), self._norm.data_ptr(), stream)
+            ema = self._ema
+            if ema is None:
+                with E.section("clip_sgd", 16.0 * self._n_elems):      # grad read twice, param read + written
+                    _lib.call("vn_clip_sgd", self._table.data_ptr(), self._n_chunks, self.max_norm, self.lr, int(self.scale_grads),
+                              self._ws.data_ptr(), self._ws.numel(), self._norm.data_ptr(), stream)
+                return
+            w = ema._weight()
+            with E.section("clip_sgd_ema", 24.0 * self._n_elems):      # + the shadow read + written
+                _lib.call("vn_clip_sgd_ema", self._table.data_ptr(), self._n_chunks, self.max_norm, self.lr, int(self.scale_grads),
+                          w, self._ws.data_ptr(), self._ws.numel(), self._norm.data_ptr(), stream)
+            ema._after_step(self._ema_rest, w)
 
 
 def decay_param_groups(model, weight_decay):
@@ -273,6 +319,8 @@ class ClipAdamW(_ClipOptimizer):
                 raise _lib.VoxelnetHipError("ClipAdamW: one max_norm / scale_grads for all parameter groups (the clip norm is global)")
 
     def _prepare(self, taking, dev):
+        if self._ema is not None:
+            self._ema_rows(taking, dev)          # (first: it checks that the shadow lives on `dev`, before any state is made)
         fresh = [p for _, p in taking if len(self.state.get(p, ())) == 0]
         if fresh:
             self._new_state(fresh)
@@ -289,13 +337,14 @@ class ClipAdamW(_ClipOptimizer):
             t = int(float(st["step"]))
             steps.append(float(t))
             slot = slots.setdefault((pgroup[i], t), len(slots))
-            rows += self._cut((p.data_ptr(), p.grad.data_ptr(), m.data_ptr(), v.data_ptr()), p.numel(), slot)
+            ptrs = (p.data_ptr(), p.grad.data_ptr(), m.data_ptr(), v.data_ptr())
+            rows += self._cut(ptrs if self._ema is None else ptrs + (self._ema._shadow_ptr(p),), p.numel(), slot)
         if len(slots) > _lib.VN_OPT_MAX_SLOTS:
             raise _lib.VoxelnetHipError(
                 f"ClipAdamW: the parameters of this step fall into {len(slots)} distinct (parameter group, step count) "
                 f"combinations, and one call carries at most {_lib.VN_OPT_MAX_SLOTS} hyperparameter sets: use fewer groups, or "
                 "keep the step counts together (parameters skipped for want of a gradient fall behind the others)")
-        self._upload(rows, _ADAM_ROW, "vn_clip_adamw_workspace_bytes", dev)
+        self._upload(rows, _ADAM_ROW if self._ema is None else _ADAM_EMA_ROW, "vn_clip_adamw_workspace_bytes", dev)
         # the step counters of the parameters taking part move into one CPU buffer (one add per step instead of one per
         # parameter); a counter that arrived through load_state_dict is copied, not aliased
         self._steps = torch.tensor(steps, dtype=torch.float32)
@@ -318,9 +367,17 @@ class ClipAdamW(_ClipOptimizer):
         with _lib.on_device(self._table.device):
             stream = _lib.raw_stream()
             from . import engine as E
-            with E.section("clip_adamw", 32.0 * self._n_elems):      # grad read twice; p, m, v read + written
-                _lib.call("vn_clip_adamw", self._table.data_ptr(), self._n_chunks, ctypes.byref(h), float(g0["max_norm"]),
-                          int(bool(g0["scale_grads"])), self._ws.data_ptr(), self._ws.numel(), self._norm.data_ptr(), stream)
+            ema = self._ema
+            if ema is None:
+                with E.section("clip_adamw", 32.0 * self._n_elems):      # grad read twice; p, m, v read + written
+                    _lib.call("vn_clip_adamw", self._table.data_ptr(), self._n_chunks, ctypes.byref(h), float(g0["max_norm"]),
+                              int(bool(g0["scale_grads"])), self._ws.data_ptr(), self._ws.numel(), self._norm.data_ptr(), stream)
+            else:
+                w = ema._weight()
+                with E.section("clip_adamw_ema", 40.0 * self._n_elems):      # + the shadow read + written
+                    _lib.call("vn_clip_adamw_ema", self._table.data_ptr(), self._n_chunks, ctypes.byref(h), float(g0["max_norm"]),
+                              int(bool(g0["scale_grads"])), w, self._ws.data_ptr(), self._ws.numel(), self._norm.data_ptr(), stream)
+                ema._after_step(self._ema_rest, w)
         for s in self._slots:
             s[1] += 1
         self._steps += 1          # every taking-part parameter's state["step"] is a view of this CPU buffer
