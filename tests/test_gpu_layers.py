@@ -325,6 +325,144 @@ def test_bn_bwd_apply_flagged_skips_unflagged_rows():
     assert bool((part[~f] == 5.0).all())
 
 
+# ---- the BatchNorm row passes against float64 on the same stored inputs, at the shapes no other test reaches ------------
+U32, U16 = 2.0 ** -24, 2.0 ** -8       # unit roundoff of fp32 and of bf16 (half an ulp, relative)
+
+
+def _bn_inputs(M, C, dt, seed):
+    """y, da as stored (dt), stats = [mean | invstd | S | beta], coef = [c0 | c1 | c2]; the same seed gives the same tensors"""
+    g = torch.Generator().manual_seed(seed)
+    y = (torch.randn(M, C, generator=g) * 1.5 + 0.3).to("cuda:0").to(dt)
+    da = torch.randn(M, C, generator=g).to("cuda:0").to(dt)
+    stats = torch.cat([torch.randn(C, generator=g) * 0.2, torch.rand(C, generator=g) + 0.5, torch.rand(C, generator=g) + 0.5,
+                       torch.randn(C, generator=g) * 0.2]).to("cuda:0")
+    coef = torch.randn(3 * C, generator=g).to("cuda:0")
+    return y, da, stats, coef
+
+
+def _bn_reference(y, da, stats, coef, relu):
+    """float64 reference of the element math and the error bars derived in check_bn_rows' docstring"""
+    C = y.shape[1]
+    mean, invstd, S, beta = stats.double().view(4, C)
+    c0, c1, c2 = coef.double().view(3, C)
+    d0 = y.double() - mean
+    z = S * d0 + beta
+    ez = 3 * U32 * ((S * d0).abs() + beta.abs())
+    on = (z > 0) if relu else torch.ones_like(z, dtype=torch.bool)
+    unsure = (z.abs() <= ez) if relu else torch.zeros_like(on)
+    dz = torch.where(on, da.double(), torch.zeros_like(z))
+    xhat = d0 * invstd
+    dy = c0 * dz + c1 * d0 + c2
+    edy = 4 * U32 * ((c0 * dz).abs() + (c1 * d0).abs() + c2.abs())
+    return dict(z=z, ez=ez, unsure=unsure, dz=dz, xhat=xhat, dy=dy, edy=edy, da=da.double())
+
+
+def _worst(tag, got, ref, bound, keep=None):
+    """prints the worst error / bound before it asserts"""
+    ratio = (got.double() - ref).abs() / bound.clamp_min(1e-300)
+    if keep is not None:
+        ratio = ratio[keep]
+    worst = float(ratio.max())
+    print(f"{tag}: worst error / bound {worst:.3f} over {ratio.numel()} elements")
+    assert worst <= 1.0, (tag, worst)
+
+
+def _check_unsure(tag, unsure):
+    share = float(unsure.double().mean())
+    print(f"{tag}: {int(unsure.sum())} of {unsure.numel()} elements within the error bar of z = 0 ({share:.2e})")
+    assert share < 1e-3, (tag, share)          # the mask cannot hide a failure
+
+
+def _check_bwd(tag, r, slab, dy, dt, chain):
+    """slab (rows, 2, C) and dy (M, C) of the backward passes against the reference r"""
+    _check_unsure(tag, r["unsure"])
+    t1, t2 = r["dz"], r["dz"] * r["xhat"]
+    flip1 = torch.where(r["unsure"], r["da"].abs(), torch.zeros_like(t1))          # a flipped mask moves the sum by its term
+    for k, (t, flip) in enumerate(((t1, flip1), (t2, flip1 * r["xhat"].abs()))):
+        bound = chain * U32 * t.abs().sum(0) + flip.sum(0)
+        _worst(f"{tag} column sum {k + 1} (chain {chain})", slab[:, k].double().sum(0), t.sum(0), bound)
+    bound = r["edy"] if dt == torch.float32 else r["edy"] + U16 * (r["dy"].abs() + r["edy"])
+    _worst(f"{tag} dy", dy, r["dy"], bound, keep=~r["unsure"])
+
+
+@pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+@pytest.mark.parametrize("M,C", [(77, 24), (24581, 256)], ids=["C24-per-iteration-path", "C256-two-rows-in-flight"])
+def test_bn_rows_against_float64(M, C, dt):
+    """vn_bn_apply, vn_bn_bwd_reduce_slab and vn_bn_bwd_apply against float64 on the same stored inputs, at two shapes no other
+    test reaches: C = 24 (256 % groups != 0: the per-iteration paths of k_bn_apply / k_bn_bwd_apply that read stats[] per
+    element) and C = 256, M = 3*8*1024 + 5 (3 rows per lane on 1025 workgroups: the two-in-flight body AND the single-row tail
+    of k_bn_bwd_reduce; at M <= 4800 the body never runs).
+
+    Bounds, derived (u = 2^-24; every kernel value is one fp32 rounding of an expression of exact inputs):
+      forward   a = relu(fma(S, fl(y - mean), beta)): the rounding of d0 = y - mean reaches a as u |S d0|, the fma adds
+                u |z| <= u (|S d0| + |beta|): 2u (|S d0| + |beta|) to first order, 3u with the second-order terms; ReLU is
+                1-Lipschitz.  A bf16 result (relu & 2, or a bf16 output) adds half a bf16 ulp: 2^-8 of the computed value.
+      backward  dy = fma(c0, dz, fma(c1, d0, c2)): u (|c0 dz| + 3 |c1 d0| + 2 |c2|) to first order, <= 4u (|c0 dz| + |c1 d0|
+                + |c2|); + half a bf16 ulp for a bf16 dy.
+      sums      a slab entry is an fp32 chain of (rows per lane + rows per block) additions: chain * u * sum |term|; the
+                test adds the slab rows in float64.
+      ReLU mask an element whose reference |z| is below the forward bound may take the other branch: it is left out of the
+                dy comparison, its |term| is added to the sums' bounds, and such elements must be fewer than 0.1 %."""
+    from voxelnet_amd import _lib, engine as E
+    lib = _lib.load()
+    vdt = _lib.VN_BF16 if dt == torch.bfloat16 else _lib.VN_F32
+    y, da, stats, coef = _bn_inputs(M, C, dt, 31)
+    mean, _, S, beta = stats.double().view(4, C)
+    for relu in (0, 1, 3):
+        a = torch.empty_like(y)
+        _lib.call("vn_bn_apply", y.data_ptr(), vdt, C, M, C, stats.data_ptr(), relu, a.data_ptr(), vdt, C, 0, E.stream())
+        d0 = y.double() - mean
+        z = S * d0 + beta
+        ref = torch.relu(z) if relu & 1 else z
+        bound = 3 * U32 * ((S * d0).abs() + beta.abs())
+        if dt == torch.bfloat16 or relu & 2:
+            bound = bound + U16 * (ref.abs() + bound)
+        _worst(f"vn_bn_apply relu {relu}", a, ref, bound)
+        if relu & 2:
+            assert torch.equal(a.float(), a.to(torch.bfloat16).float())          # the result is a bf16 value
+    rows = lib.vn_bn_bwd_slab_rows(M, C)
+    rpb = 256 // (C // 8)
+    chain = -(-M // (rows * rpb)) + rpb
+    for relu in (0, 1):
+        r = _bn_reference(y, da, stats, coef, relu)
+        slab = torch.empty((rows, 2, C), device="cuda:0")
+        _lib.call("vn_bn_bwd_reduce_slab", da.data_ptr(), vdt, C, y.data_ptr(), vdt, C, M, C, stats.data_ptr(), relu, slab.data_ptr(),
+                  E.stream())
+        dy = torch.empty_like(y)
+        _lib.call("vn_bn_bwd_apply", da.data_ptr(), vdt, C, y.data_ptr(), vdt, C, M, C, stats.data_ptr(), coef.data_ptr(), relu,
+                  dy.data_ptr(), vdt, C, 0, E.stream())
+        _check_bwd(f"relu {relu}", r, slab, dy, dt, chain)
+
+
+@pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+def test_bn_bev_backward_against_float64(dt):
+    """vn_bn_bwd_reduce_slab_bev / vn_bn_bwd_apply_bev (da read through the BEV fold: row m = ((b*2+d)*HW + r) of the
+    (B,2,H,W,64) layer is row b*HW + r, channels d*64.. of the 128-wide tensor) against float64 on the same stored inputs;
+    bounds as in test_bn_rows_against_float64."""
+    from voxelnet_amd import _lib, engine as E
+    lib = _lib.load()
+    vdt = _lib.VN_BF16 if dt == torch.bfloat16 else _lib.VN_F32
+    C, hw, wide = 64, 6 * 5, 128
+    M = 2 * 2 * hw
+    y, _, stats, coef = _bn_inputs(M, C, dt, 32)
+    daw = torch.randn(M // 2, wide, generator=torch.Generator().manual_seed(33)).to("cuda:0").to(dt)
+    m = torch.arange(M, device="cuda:0")
+    seg, rr = m // hw, m % hw
+    da = daw[(seg >> 1) * hw + rr].view(M, 2, C)[m, seg & 1]          # the rows the fold hands the (M, 64) layer
+    rows = lib.vn_bn_bwd_slab_rows(M, C)
+    rpb = 256 // (C // 8)
+    chain = -(-M // (rows * rpb)) + rpb
+    for relu in (0, 1):
+        r = _bn_reference(y, da, stats, coef, relu)
+        slab = torch.empty((rows, 2, C), device="cuda:0")
+        _lib.call("vn_bn_bwd_reduce_slab_bev", daw.data_ptr(), vdt, wide, y.data_ptr(), vdt, M, C, hw, stats.data_ptr(), relu,
+                  slab.data_ptr(), E.stream())
+        dy = torch.empty_like(y)
+        _lib.call("vn_bn_bwd_apply_bev", daw.data_ptr(), vdt, wide, y.data_ptr(), vdt, M, C, hw, stats.data_ptr(), coef.data_ptr(),
+                  relu, dy.data_ptr(), vdt, E.stream())
+        _check_bwd(f"bev relu {relu}", r, slab, dy, dt, chain)
+
+
 @pytest.mark.parametrize("dt", [torch.bfloat16, torch.float32])
 def test_first_layer_sparse_batchnorm_passes_equal_the_dense_ones(dt):
     """vn_bn_apply_flagged / vn_bn_bwd_reduce_slab_flagged / vn_bn_bwd_apply_list (first middle layer: rows without an

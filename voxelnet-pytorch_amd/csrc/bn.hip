@@ -56,42 +56,121 @@ __device__ __forceinline__ void store8(void *base, int dtype, int64_t lo_off, in
     }
 }
 
-// block-level column reduction of 2 x 8 floats per thread -> double atomics
-__device__ __forceinline__ void block_reduce_atomic(const float s1[8], const float s2[8], int groups, int rpb, int C,
-                                                    double *sums) {
-    __shared__ float red[256 * 16];
+// ---- the element math of every pass: written once ----------------------------------------------------------------------
+// A lane's eight channel constants, channels c .. c+7 of stats = [mean | invstd | S = gamma*invstd | beta][C]
+// (invstd on request, for the backward sums: left to the compiler as a dead load it still changed the address arithmetic
+// of the apply kernels' prologues)
+struct Chan8 { float mean[8], invstd[8], S[8], beta[8]; };
+template <bool INVSTD = false>
+__device__ __forceinline__ Chan8 load_chan8(const float *__restrict__ stats, int C, int c) {
+    Chan8 k;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-        red[threadIdx.x * 16 + j] = s1[j];
-        red[threadIdx.x * 16 + 8 + j] = s2[j];
+        k.mean[j] = stats[c + j]; k.invstd[j] = INVSTD ? stats[C + c + j] : 0.f; k.S[j] = stats[2 * C + c + j]; k.beta[j] = stats[3 * C + c + j];
     }
-    __syncthreads();
-    // thread t < groups*16 sums one (group, slot) column over the rpb row-slices
-    for (int t = threadIdx.x; t < groups * 16; t += 256) {
-        const int g = t >> 4, slot = t & 15;
-        double acc = 0.0;
-        for (int r = 0; r < rpb; ++r) acc += (double)red[(r * groups + g) * 16 + slot];
-        const int c = g * 8 + (slot & 7);
-        atomicAdd(sums + (slot >= 8 ? C : 0) + c, acc);
+    return k;
+}
+// ... and of coef = [c0 | c1 | c2][C] (k_bn_bwd_finalize*): dy = c0 dz + c1 (y - mean) + c2
+struct Coef8 { float c0[8], c1[8], c2[8]; };
+__device__ __forceinline__ Coef8 load_coef8(const float *__restrict__ coef, int C, int c) {
+    Coef8 q;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { q.c0[j] = coef[c + j]; q.c1[j] = coef[C + c + j]; q.c2[j] = coef[2 * C + c + j]; }
+    return q;
+}
+// forward: a = relu(S (y - mean) + beta); relu & 1: apply the ReLU, relu & 2: round the result to bf16
+__device__ __forceinline__ float bn_fwd(float y, float mean, float S, float beta, int relu) {
+    const float z = fmaf(S, y - mean, beta);
+    float a = (relu & 1) ? fmaxf(z, 0.f) : z;
+    if (relu & 2) a = (float)(bf16_t)a;
+    return a;
+}
+// backward: the gradient dz at the BatchNorm output (da behind the ReLU mask of the recomputed z), and d0 = y - mean
+__device__ __forceinline__ float bn_bwd_dz(float y, float da, float mean, float S, float beta, int relu, float &d0) {
+    d0 = y - mean;
+    const float z = fmaf(S, d0, beta);
+    return (!relu || z > 0.f) ? da : 0.f;
+}
+__device__ __forceinline__ float bn_bwd_dy(float c0, float c1, float c2, float dz, float d0) {
+    return fmaf(c0, dz, fmaf(c1, d0, c2));
+}
+// one row into a lane's partials of the backward sums: s[0] += dz, s[1] += dz * xhat
+template <int N>
+__device__ __forceinline__ void bwd_sums_row(const Chan8 &k, int relu, const float yv[8], const float dv[8], float (&s)[N][8]) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        float d0;
+        const float dz = bn_bwd_dz(yv[j], dv[j], k.mean[j], k.S[j], k.beta[j], relu, d0);
+        s[0][j] += dz;
+        s[1][j] += dz * (d0 * k.invstd[j]);
+    }
+}
+// ... and into a row of dy
+__device__ __forceinline__ void bwd_dy_row(const Chan8 &k, const Coef8 &q, int relu, const float yv[8], const float dv[8], float o[8]) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        float d0;
+        const float dz = bn_bwd_dz(yv[j], dv[j], k.mean[j], k.S[j], k.beta[j], relu, d0);
+        o[j] = bn_bwd_dy(q.c0[j], q.c1[j], q.c2[j], dz, d0);
     }
 }
 
-// same reduction, written as one slab row per workgroup: slab[block][2][C] floats (plain stores)
-__device__ __forceinline__ void block_reduce_slab(const float s1[8], const float s2[8], int groups, int rpb, int C,
-                                                  float *slab_row) {
-    __shared__ float red[256 * 16];
+// Block-level column reduction of N x 8 fp32 partials per lane through LDS: thread t sums one (group, slot, channel)
+// column over the workgroup's rpb row slices in Acc, in the order r = 0 .. rpb-1, and hands sink(slot, channel, total).
+// Every instantiation owns its LDS (256 * N * 32 B).
+template <int N, typename Acc, typename Sink>
+__device__ __forceinline__ void block_reduce(const float (&s)[N][8], int groups, int rpb, Sink sink) {
+    __shared__ float red[256 * N * 8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        red[threadIdx.x * 16 + j] = s1[j];
-        red[threadIdx.x * 16 + 8 + j] = s2[j];
-    }
+    for (int k = 0; k < N; ++k)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) red[threadIdx.x * (N * 8) + k * 8 + j] = s[k][j];
     __syncthreads();
-    for (int t = threadIdx.x; t < groups * 16; t += 256) {
-        const int g = t >> 4, slot = t & 15;
-        float acc = 0.f;
-        for (int r = 0; r < rpb; ++r) acc += red[(r * groups + g) * 16 + slot];
-        slab_row[(slot >= 8 ? C : 0) + g * 8 + (slot & 7)] = acc;
+    for (int t = threadIdx.x; t < groups * (N * 8); t += 256) {
+        const int g = t / (N * 8), slot = t - g * (N * 8);
+        Acc acc = 0;
+        for (int r = 0; r < rpb; ++r) acc += (Acc)red[(r * groups + g) * (N * 8) + slot];
+        sink(slot >> 3, g * 8 + (slot & 7), acc);
     }
+}
+
+// A wave's share of N interleaved slab columns (column k of slab row r at col[(r * N + k) * C]) in double: rows first,
+// first + step, .. below `rows` per lane, then the __shfl_xor ladder (fixed order: deterministic).  Every lane gets the sums.
+template <int N>
+__device__ __forceinline__ void wave_col_sums(const float *__restrict__ col, int C, int64_t first, int64_t rows, int step,
+                                              double a[N]) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) a[k] = 0.0;
+    for (int64_t r = first; r < rows; r += step)
+#pragma unroll
+        for (int k = 0; k < N; ++k) a[k] += (double)col[(r * N + k) * C];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1)
+#pragma unroll
+        for (int k = 0; k < N; ++k) a[k] += __shfl_xor(a[k], o, 64);
+}
+// The same over the workgroup's 256 threads: the four waves meet through LDS and ONE barrier (not an 8-barrier LDS tree)
+template <int N>
+__device__ __forceinline__ void block_col_sums(const float *__restrict__ col, int C, int64_t rows, double t[N]) {
+    __shared__ double red[N][4];
+    double a[N];
+    wave_col_sums<N>(col, C, threadIdx.x, rows, 256, a);
+    if ((threadIdx.x & 63) == 0)
+#pragma unroll
+        for (int k = 0; k < N; ++k) red[k][threadIdx.x >> 6] = a[k];
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < N; ++k) t[k] = (red[k][0] + red[k][1]) + (red[k][2] + red[k][3]);
+}
+
+// the (b,d,h,w) int64 site list of vn_active_sites: its valid length (*count, clamped to the capacity) and entry e's row
+__device__ __forceinline__ int64_t list_len(const int32_t *__restrict__ count, int64_t cap) {
+    const int64_t n = count ? (int64_t)count[0] : cap;
+    return n > cap ? cap : n;
+}
+__device__ __forceinline__ int64_t site_row(const int64_t *__restrict__ list, int64_t e, int D, int H, int W) {
+    const int64_t *rc = list + e * 4;
+    return ((rc[0] * D + rc[1]) * H + rc[2]) * W + rc[3];
 }
 
 __global__ void __launch_bounds__(256) k_bn_stats(const void *__restrict__ y, int dtype, int64_t M, int C,
@@ -104,7 +183,7 @@ __global__ void __launch_bounds__(256) k_bn_stats(const void *__restrict__ y, in
     float sh[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) sh[j] = shift ? shift[(g * 8 + j) % creal] : 0.f;
-    float s1[8] = {0}, s2[8] = {0};
+    float s[2][8] = {};
     if (rr < rpb) {
         for (int64_t m = (int64_t)blockIdx.x * rpb + rr; m < M; m += (int64_t)gridDim.x * rpb) {
             float v[8];
@@ -112,12 +191,12 @@ __global__ void __launch_bounds__(256) k_bn_stats(const void *__restrict__ y, in
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const float d = v[j] - sh[j];
-                s1[j] += d;
-                s2[j] += d * d;
+                s[0][j] += d;
+                s[1][j] += d * d;
             }
         }
     }
-    block_reduce_atomic(s1, s2, groups, rpb, C, sums);
+    block_reduce<2, double>(s, groups, rpb, [&](int k, int c, double v) { atomicAdd(sums + (k ? C : 0) + c, v); });
 }
 
 __global__ void __launch_bounds__(256) k_bn_finalize(const double *__restrict__ sums, int64_t M, int C, int fold,
@@ -168,8 +247,7 @@ __global__ void __launch_bounds__(256) k_bn_finalize_slab(const float *__restric
     VN_PRIO_MAIN();
     // This launch sits on the dependency chain 46 times per step and is pure latency: the per-channel parameters are
     // requested before the slab loop (not after the reduction: one memory round trip less), and the 256 partial sums
-    // meet through wave shuffles + one barrier (fixed order: deterministic) instead of an 8-barrier LDS tree.
-    __shared__ double r1[4], r2[4];
+    // meet through wave shuffles + one barrier (block_col_sums) instead of an 8-barrier LDS tree.
     const int c = blockIdx.x;
     float p_shift = 0.f, p_gamma = 0.f, p_beta = 0.f, p_rm = 0.f, p_rv = 0.f;
     if (threadIdx.x == 0) {
@@ -179,23 +257,12 @@ __global__ void __launch_bounds__(256) k_bn_finalize_slab(const float *__restric
         if (running_mean) p_rm = running_mean[c];
         if (running_var) p_rv = running_var[c];
     }
-    double s1 = 0.0, s2 = 0.0;
-    for (int64_t r = threadIdx.x; r < rows; r += 256) {
-        s1 += (double)slab[(r * 2 + 0) * C + c];
-        s2 += (double)slab[(r * 2 + 1) * C + c];
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        s1 += __shfl_xor(s1, o, 64);
-        s2 += __shfl_xor(s2, o, 64);
-    }
-    if ((threadIdx.x & 63) == 0) { r1[threadIdx.x >> 6] = s1; r2[threadIdx.x >> 6] = s2; }
-    __syncthreads();
+    double t[2];
+    block_col_sums<2>(slab + c, C, rows, t);
     if (threadIdx.x == 0) {
-        const double t1 = (r1[0] + r1[1]) + (r1[2] + r1[3]), t2 = (r2[0] + r2[1]) + (r2[2] + r2[3]);
         const double n = (double)M;
-        const double ms = t1 / n;
-        double var = t2 / n - ms * ms;
+        const double ms = t[0] / n;
+        double var = t[1] / n - ms * ms;
         if (var < 0.0) var = 0.0;
         const double mean = ms + (double)p_shift;
         if (running_mean) running_mean[c] = (float)((1.0 - momentum) * p_rm + momentum * mean);
@@ -221,48 +288,37 @@ template <bool FLAGGED>
 __global__ void __launch_bounds__(256) k_bn_apply(const void *__restrict__ y, int ydt, int64_t ystride, int64_t M, int C,
                                                   const float *__restrict__ stats, int relu, void *__restrict__ a,
                                                   int adt, int64_t astride, int64_t lo_off, int64_t fold,
-                                                  const uint8_t *__restrict__ flags, const float *__restrict__ inactive,
-                                                  int hoist) {
+                                                  const uint8_t *__restrict__ flags, const float *__restrict__ inactive) {
     VN_PRIO_MAIN();
     const int groups = C >> 3;
     const int64_t total = M * groups;
-    {
-        if (256 % groups == 0 && !fold && (FLAGGED || hoist)) {
-            // a thread keeps one group of 8 channels: the activation of an inactive row is computed ONCE (the rows without a
-            // flag — 90 % of the first layer's — are then 16-B stores of it: the pass is a write stream)
-            const int rpb = 256 / groups;
-            const int c = (threadIdx.x % groups) << 3, rr = threadIdx.x / groups;
-            float mean[8], S[8], be[8], cv[8];
+    if (256 % groups == 0 && !fold) {
+        // a thread keeps one group of 8 channels: the activation of an inactive row is computed ONCE (the rows without a
+        // flag — 90 % of the first layer's — are then 16-B stores of it: the pass is a write stream)
+        const int rpb = 256 / groups;
+        const int c = (threadIdx.x % groups) << 3, rr = threadIdx.x / groups;
+        const Chan8 k = load_chan8(stats, C, c);
+        float cv[8];
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                mean[j] = stats[c + j]; S[j] = stats[2 * C + c + j]; be[j] = stats[3 * C + c + j];
-                cv[j] = 0.f;
-                if constexpr (FLAGGED) {
-                    const float z = fmaf(S[j], as_stored(inactive[c + j], ydt) - mean[j], be[j]);
-                    cv[j] = (relu & 1) ? fmaxf(z, 0.f) : z;
-                    if (relu & 2) cv[j] = (float)(bf16_t)cv[j];
-                }
-            }
-            for (int64_t m = (int64_t)blockIdx.x * rpb + rr; m < M; m += (int64_t)gridDim.x * rpb) {
-                float v[8];
-                bool inact = false;
-                if constexpr (FLAGGED) inact = !flags[m];
-                if (inact) {
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) v[j] = cv[j];
-                } else {
-                    load8(y, ydt, m * ystride + c, v);
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const float z = fmaf(S[j], v[j] - mean[j], be[j]);
-                        v[j] = (relu & 1) ? fmaxf(z, 0.f) : z;
-                        if (relu & 2) v[j] = (float)(bf16_t)v[j];
-                    }
-                }
-                store8(a, adt, lo_off, m * astride + c, v);
-            }
-            return;
+        for (int j = 0; j < 8; ++j) {
+            cv[j] = 0.f;
+            if constexpr (FLAGGED) cv[j] = bn_fwd(as_stored(inactive[c + j], ydt), k.mean[j], k.S[j], k.beta[j], relu);
         }
+        for (int64_t m = (int64_t)blockIdx.x * rpb + rr; m < M; m += (int64_t)gridDim.x * rpb) {
+            float v[8];
+            bool inact = false;
+            if constexpr (FLAGGED) inact = !flags[m];
+            if (inact) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) v[j] = cv[j];
+            } else {
+                load8(y, ydt, m * ystride + c, v);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) v[j] = bn_fwd(v[j], k.mean[j], k.S[j], k.beta[j], relu);
+            }
+            store8(a, adt, lo_off, m * astride + c, v);
+        }
+        return;
     }
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
         const int64_t m = i / groups;
@@ -277,11 +333,7 @@ __global__ void __launch_bounds__(256) k_bn_apply(const void *__restrict__ y, in
             load8(y, ydt, m * ystride + c, v);
         }
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            float z = fmaf(stats[2 * C + c + j], v[j] - stats[c + j], stats[3 * C + c + j]);
-            v[j] = (relu & 1) ? fmaxf(z, 0.f) : z;
-            if (relu & 2) v[j] = (float)(bf16_t)v[j];
-        }
+        for (int j = 0; j < 8; ++j) v[j] = bn_fwd(v[j], stats[c + j], stats[2 * C + c + j], stats[3 * C + c + j], relu);
         store8(a, adt, lo_off, (fold ? fold_off(m, fold, astride, C) : m * astride) + c, v);
     }
 }
@@ -295,15 +347,14 @@ __global__ void __launch_bounds__(256) k_bn_bwd_reduce(const void *__restrict__ 
     VN_PRIO_MAIN();
     const int groups = C >> 3, rpb = 256 / groups;
     const int g = threadIdx.x % groups, rr = threadIdx.x / groups;
-    float mean[8], invstd[8], S[8], be[8], yin[8];
+    const Chan8 k = load_chan8<true>(stats, C, g * 8);
+    float yin[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-        const int c = g * 8 + j;
-        mean[j] = stats[c]; invstd[j] = stats[C + c]; S[j] = stats[2 * C + c]; be[j] = stats[3 * C + c];
         yin[j] = 0.f;
-        if constexpr (FLAGGED) yin[j] = as_stored(inactive[c], ydt);      // what y holds in the rows with flag 0 (not read there)
+        if constexpr (FLAGGED) yin[j] = as_stored(inactive[g * 8 + j], ydt);      // what y holds in the rows with flag 0 (not read there)
     }
-    float s1[8] = {0}, s2[8] = {0};
+    float s[2][8] = {};
     if (rr < rpb) {
         // two rows in flight per lane (the loads of both are issued before either is used)
         const int64_t step = (int64_t)gridDim.x * rpb;
@@ -324,15 +375,7 @@ __global__ void __launch_bounds__(256) k_bn_bwd_reduce(const void *__restrict__ 
                 load8(da, dadt, (fold ? fold_off(mu, fold, dastride, C) : mu * dastride) + g * 8, dv[u]);
             }
 #pragma unroll
-            for (int u = 0; u < 2; ++u)
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const float d0 = yv[u][j] - mean[j];
-                    const float z = fmaf(S[j], d0, be[j]);
-                    const float dz = (!relu || z > 0.f) ? dv[u][j] : 0.f;
-                    s1[j] += dz;
-                    s2[j] += dz * (d0 * invstd[j]);
-                }
+            for (int u = 0; u < 2; ++u) bwd_sums_row(k, relu, yv[u], dv[u], s);
         }
         for (; m < M; m += step) {
             float yv[8], dv[8];
@@ -345,52 +388,40 @@ __global__ void __launch_bounds__(256) k_bn_bwd_reduce(const void *__restrict__ 
                 load8(y, ydt, m * ystride + g * 8, yv);
             }
             load8(da, dadt, (fold ? fold_off(m, fold, dastride, C) : m * dastride) + g * 8, dv);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float d0 = yv[j] - mean[j];
-                const float z = fmaf(S[j], d0, be[j]);
-                const float dz = (!relu || z > 0.f) ? dv[j] : 0.f;
-                s1[j] += dz;
-                s2[j] += dz * (d0 * invstd[j]);
-            }
+            bwd_sums_row(k, relu, yv, dv, s);
         }
     }
-    if (slab) block_reduce_slab(s1, s2, groups, rpb, C, slab + (size_t)blockIdx.x * 2 * C);
-    else block_reduce_atomic(s1, s2, groups, rpb, C, sums);
+    // (both sinks are instantiated: this kernel reserves the LDS of both)
+    if (slab) {
+        float *row = slab + (size_t)blockIdx.x * 2 * C;      // one slab row per workgroup: slab[block][2][C], plain stores
+        block_reduce<2, float>(s, groups, rpb, [&](int q, int c, float v) { row[(q ? C : 0) + c] = v; });
+    } else {
+        block_reduce<2, double>(s, groups, rpb, [&](int q, int c, double v) { atomicAdd(sums + (q ? C : 0) + c, v); });
+    }
+}
+
+// channel c's gradients and coefficients from its sums s1 = sum dz, s2 = sum dz * xhat over n rows
+__device__ __forceinline__ void write_coef(float *__restrict__ coef, float *__restrict__ d_gamma, float *__restrict__ d_beta,
+                                           int C, int c, float S, float invstd, double s1, double s2, double n) {
+    if (d_gamma) d_gamma[c] = (float)s2;
+    if (d_beta) d_beta[c] = (float)s1;
+    coef[c] = S;
+    coef[C + c] = -S * invstd * (float)(s2 / n);
+    coef[2 * C + c] = -S * (float)(s1 / n);
 }
 
 // one workgroup per channel: coef from the slab of k_bn_bwd_reduce
-__global__ void __launch_bounds__(256) k_bn_bwd_finalize_slab(const float *__restrict__ slab, int rows, int64_t M, int C,
+__global__ void __launch_bounds__(256) k_bn_bwd_finalize_slab(const float *__restrict__ slab, int64_t rows, int64_t M, int C,
                                                               const float *__restrict__ gamma,
                                                               const float *__restrict__ stats, float *__restrict__ coef,
                                                               float *__restrict__ d_gamma, float *__restrict__ d_beta) {
     VN_PRIO_MAIN();
-    __shared__ double r1[4], r2[4];   // (same shape as k_bn_finalize_slab: parameters first, shuffles + one barrier)
-    const int c = blockIdx.x;
+    const int c = blockIdx.x;     // (same shape as k_bn_finalize_slab: parameters first, then block_col_sums)
     float invstd = 0.f, p_gamma = 0.f;
     if (threadIdx.x == 0) { invstd = stats[C + c]; p_gamma = gamma[c]; }
-    double s1 = 0.0, s2 = 0.0;
-    for (int r = threadIdx.x; r < rows; r += 256) {
-        s1 += (double)slab[((size_t)r * 2 + 0) * C + c];
-        s2 += (double)slab[((size_t)r * 2 + 1) * C + c];
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        s1 += __shfl_xor(s1, o, 64);
-        s2 += __shfl_xor(s2, o, 64);
-    }
-    if ((threadIdx.x & 63) == 0) { r1[threadIdx.x >> 6] = s1; r2[threadIdx.x >> 6] = s2; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const double t1 = (r1[0] + r1[1]) + (r1[2] + r1[3]), t2 = (r2[0] + r2[1]) + (r2[2] + r2[3]);
-        const double n = (double)M;
-        const float S = p_gamma * invstd;
-        if (d_gamma) d_gamma[c] = (float)t2;
-        if (d_beta) d_beta[c] = (float)t1;
-        coef[c] = S;
-        coef[C + c] = -S * invstd * (float)(t2 / n);
-        coef[2 * C + c] = -S * (float)(t1 / n);
-    }
+    double t[2];
+    block_col_sums<2>(slab + c, C, rows, t);
+    if (threadIdx.x == 0) write_coef(coef, d_gamma, d_beta, C, c, p_gamma * invstd, invstd, t[0], t[1], (double)M);
 }
 
 __global__ void __launch_bounds__(256) k_bn_bwd_finalize(const double *__restrict__ sums, int64_t M, int C, int fold,
@@ -431,24 +462,14 @@ __global__ void __launch_bounds__(256) k_bn_bwd_apply(const void *__restrict__ d
     if (256 % groups == 0) {
         const int rpb = 256 / groups;
         const int c = (threadIdx.x % groups) << 3, rr = threadIdx.x / groups;
-        float mean[8], S[8], be[8], c0[8], c1[8], c2[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            mean[j] = stats[c + j]; S[j] = stats[2 * C + c + j]; be[j] = stats[3 * C + c + j];
-            c0[j] = coef[c + j]; c1[j] = coef[C + c + j]; c2[j] = coef[2 * C + c + j];
-        }
+        const Chan8 k = load_chan8(stats, C, c);
+        const Coef8 q = load_coef8(coef, C, c);
         for (int64_t m = (int64_t)blockIdx.x * rpb + rr; m < M; m += (int64_t)gridDim.x * rpb) {
             if (flags && !flags[m]) continue;
             float yv[8], dv[8], o[8];
             load8(y, ydt, m * ystride + c, yv);
             load8(da, dadt, (fold ? fold_off(m, fold, dastride, C) : m * dastride) + c, dv);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float d0 = yv[j] - mean[j];
-                const float z = fmaf(S[j], d0, be[j]);
-                const float dz = (!relu || z > 0.f) ? dv[j] : 0.f;
-                o[j] = fmaf(c0[j], dz, fmaf(c1[j], d0, c2[j]));
-            }
+            bwd_dy_row(k, q, relu, yv, dv, o);
             store8(dy, dydt, lo_off, m * dystride + c, o);
         }
         return;
@@ -463,10 +484,9 @@ __global__ void __launch_bounds__(256) k_bn_bwd_apply(const void *__restrict__ d
         load8(da, dadt, (fold ? fold_off(m, fold, dastride, C) : m * dastride) + c, dv);
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const float d0 = yv[j] - stats[c + j];
-            const float z = fmaf(stats[2 * C + c + j], d0, stats[3 * C + c + j]);
-            const float dz = (!relu || z > 0.f) ? dv[j] : 0.f;
-            o[j] = fmaf(coef[c + j], dz, fmaf(coef[C + c + j], d0, coef[2 * C + c + j]));
+            float d0;
+            const float dz = bn_bwd_dz(yv[j], dv[j], stats[c + j], stats[2 * C + c + j], stats[3 * C + c + j], relu, d0);
+            o[j] = bn_bwd_dy(coef[c + j], coef[C + c + j], coef[2 * C + c + j], dz, d0);
         }
         store8(dy, dydt, lo_off, m * dystride + c, o);
     }
@@ -484,27 +504,15 @@ __global__ void __launch_bounds__(256) k_bn_bwd_apply_list(const void *__restric
     const int groups = C >> 3, rpb = 256 / groups;
     const int c = (threadIdx.x % groups) << 3, rr = threadIdx.x / groups;
     if (rr >= rpb) return;
-    int64_t n = count ? (int64_t)count[0] : cap;
-    if (n > cap) n = cap;
-    float mean[8], S[8], be[8], c0[8], c1[8], c2[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        mean[j] = stats[c + j]; S[j] = stats[2 * C + c + j]; be[j] = stats[3 * C + c + j];
-        c0[j] = coef[c + j]; c1[j] = coef[C + c + j]; c2[j] = coef[2 * C + c + j];
-    }
+    const int64_t n = list_len(count, cap);
+    const Chan8 k = load_chan8(stats, C, c);
+    const Coef8 q = load_coef8(coef, C, c);
     for (int64_t e = (int64_t)blockIdx.x * rpb + rr; e < n; e += (int64_t)gridDim.x * rpb) {
-        const int64_t *rc = list + e * 4;
-        const int64_t m = ((rc[0] * D + rc[1]) * H + rc[2]) * W + rc[3];
+        const int64_t m = site_row(list, e, D, H, W);
         float yv[8], dv[8], o[8];
         load8(y, ydt, m * C + c, yv);
         load8(da, dadt, (da_compact ? e : m) * C + c, dv);     // da_compact: row e of a [cap][C] matrix in list order
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float d0 = yv[j] - mean[j];
-            const float z = fmaf(S[j], d0, be[j]);
-            const float dz = (!relu || z > 0.f) ? dv[j] : 0.f;
-            o[j] = fmaf(c0[j], dz, fmaf(c1[j], d0, c2[j]));
-        }
+        bwd_dy_row(k, q, relu, yv, dv, o);
         store8(dy, dydt, 0, m * C + c, o);
     }
 }
@@ -526,51 +534,28 @@ __global__ void __launch_bounds__(256) k_bn_bwd_reduce_list(const void *__restri
                                                             float *__restrict__ slab, const int64_t *__restrict__ list,
                                                             const int32_t *__restrict__ count, int64_t cap) {
     VN_PRIO_MAIN();
-    __shared__ float red[256 * 24];
     const int groups = C >> 3, rpb = 256 / groups;
-    const int g = threadIdx.x % groups, c = g << 3, rr = threadIdx.x / groups;
-    int64_t n = count ? (int64_t)count[0] : cap;
-    if (n > cap) n = cap;
-    float mean[8], invstd[8], S[8], be[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { mean[j] = stats[c + j]; invstd[j] = stats[C + c + j]; S[j] = stats[2 * C + c + j]; be[j] = stats[3 * C + c + j]; }
-    float s1[8] = {0}, s2[8] = {0}, s3[8] = {0};
+    const int c = (threadIdx.x % groups) << 3, rr = threadIdx.x / groups;
+    const int64_t n = list_len(count, cap);
+    const Chan8 k = load_chan8<true>(stats, C, c);
+    float s[3][8] = {};
     if (rr < rpb) {
         for (int64_t e = (int64_t)blockIdx.x * rpb + rr; e < n; e += (int64_t)gridDim.x * rpb) {
-            const int64_t *rc = list + e * 4;
-            const int64_t m = ((rc[0] * D + rc[1]) * H + rc[2]) * W + rc[3];
+            const int64_t m = site_row(list, e, D, H, W);
             float yv[8], dv[8];
             load8(y, ydt, m * C + c, yv);
             load8(da, dadt, e * C + c, dv);
+            bwd_sums_row(k, relu, yv, dv, s);
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float d0 = yv[j] - mean[j];
-                const float z = fmaf(S[j], d0, be[j]);
-                const float dz = (!relu || z > 0.f) ? dv[j] : 0.f;
-                s1[j] += dz;
-                s2[j] += dz * (d0 * invstd[j]);
-                s3[j] += dv[j];
-            }
+            for (int j = 0; j < 8; ++j) s[2][j] += dv[j];
         }
     }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        red[threadIdx.x * 24 + j] = s1[j];
-        red[threadIdx.x * 24 + 8 + j] = s2[j];
-        red[threadIdx.x * 24 + 16 + j] = s3[j];
-    }
-    __syncthreads();
     float *row = slab + (size_t)blockIdx.x * 3 * C;
-    for (int t = threadIdx.x; t < groups * 24; t += 256) {
-        const int gg = t / 24, slot = t - gg * 24;
-        float acc = 0.f;
-        for (int r = 0; r < rpb; ++r) acc += red[(r * groups + gg) * 24 + slot];
-        row[(slot >> 3) * C + gg * 8 + (slot & 7)] = acc;
-    }
+    block_reduce<3, float>(s, groups, rpb, [&](int q, int ch, float v) { row[q * C + ch] = v; });
 }
 
 // one workgroup per channel: the three slab columns in double, then the inactive sites' closed form and the coefficients
-__global__ void __launch_bounds__(256) k_bn_bwd_finalize_list(const float *__restrict__ slab, int rows, int64_t M, int C,
+__global__ void __launch_bounds__(256) k_bn_bwd_finalize_list(const float *__restrict__ slab, int64_t rows, int64_t M, int C,
                                                               const float *__restrict__ gamma, const float *__restrict__ stats,
                                                               const float *__restrict__ total, const float *__restrict__ inactive,
                                                               int ydt, int relu, float *__restrict__ coef,
@@ -579,10 +564,10 @@ __global__ void __launch_bounds__(256) k_bn_bwd_finalize_list(const float *__res
     __shared__ double r1[256], r2[256], r3[256];
     const int c = blockIdx.x;
     double a1 = 0.0, a2 = 0.0, a3 = 0.0;
-    for (int r = threadIdx.x; r < rows; r += 256) {
-        a1 += (double)slab[((size_t)r * 3 + 0) * C + c];
-        a2 += (double)slab[((size_t)r * 3 + 1) * C + c];
-        a3 += (double)slab[((size_t)r * 3 + 2) * C + c];
+    for (int64_t r = threadIdx.x; r < rows; r += 256) {
+        a1 += (double)slab[(r * 3 + 0) * C + c];
+        a2 += (double)slab[(r * 3 + 1) * C + c];
+        a3 += (double)slab[(r * 3 + 2) * C + c];
     }
     r1[threadIdx.x] = a1; r2[threadIdx.x] = a2; r3[threadIdx.x] = a3;
     __syncthreads();
@@ -593,18 +578,12 @@ __global__ void __launch_bounds__(256) k_bn_bwd_finalize_list(const float *__res
         __syncthreads();
     }
     if (threadIdx.x == 0) {
-        const float mean = stats[c], invstd = stats[C + c], Sc = stats[2 * C + c], be = stats[3 * C + c];
-        const float d0 = as_stored(inactive[c], ydt) - mean;           // the same fp32 expressions as the row kernels
-        const float z = fmaf(Sc, d0, be);
-        const double rest = (!relu || z > 0.f) ? (double)total[c] - r3[0] : 0.0;   // sum of dz over the inactive sites
-        const double s1 = r1[0] + rest, s2 = r2[0] + rest * (double)(d0 * invstd);
-        const double n = (double)M;
-        const float S = gamma[c] * invstd;
-        if (d_gamma) d_gamma[c] = (float)s2;
-        if (d_beta) d_beta[c] = (float)s1;
-        coef[c] = S;
-        coef[C + c] = -S * invstd * (float)(s2 / n);
-        coef[2 * C + c] = -S * (float)(s1 / n);
+        const float invstd = stats[C + c];
+        float d0;      // the constant row through the row kernels' own element function: its ReLU mask (da = 1) and y - mean
+        const float mask = bn_bwd_dz(as_stored(inactive[c], ydt), 1.f, stats[c], stats[2 * C + c], stats[3 * C + c], relu, d0);
+        const double rest = mask != 0.f ? (double)total[c] - r3[0] : 0.0;          // sum of dz over the inactive sites
+        write_coef(coef, d_gamma, d_beta, C, c, gamma[c] * invstd, invstd, r1[0] + rest,
+                   r2[0] + rest * (double)(d0 * invstd), (double)M);
     }
 }
 
@@ -612,13 +591,26 @@ __global__ void __launch_bounds__(256) k_bn_bwd_finalize_list(const float *__res
 // nb + k*BOX_EB .. +BOX_EB sum edge k: 0 h=0, 1 h=H-1, 2 w=0, 3 w=W-1, 4..7 the corners (0,0) (0,W-1) (H-1,0) (H-1,W-1)
 // (over all b, d).
 constexpr int BOX_EB = 16;
+// Box(hc, wc) from the total and the eight edge sums in that numbering; hc / wc: 0 = exclude the first row / column,
+// 1 = all, 2 = exclude the last (inclusion-exclusion: a corner is removed twice by its two edges)
+__device__ __forceinline__ double box_from_edges(double tot, const double e[8], int hc, int wc) {
+    double v = tot;
+    if (hc == 0) v -= e[0];
+    if (hc == 2) v -= e[1];
+    if (wc == 0) v -= e[2];
+    if (wc == 2) v -= e[3];
+    if (hc == 0 && wc == 0) v += e[4];
+    if (hc == 0 && wc == 2) v += e[5];
+    if (hc == 2 && wc == 0) v += e[6];
+    if (hc == 2 && wc == 2) v += e[7];
+    return v;
+}
 __global__ void __launch_bounds__(256) k_box_partials(const void *__restrict__ x, int dt, int B, int D, int H, int W, int C,
                                                       int nb, float *__restrict__ slab) {
     VN_PRIO_MAIN();
-    __shared__ float red[256 * 8];
     const int groups = C >> 3, rpb = 256 / groups;
-    const int g = threadIdx.x % groups, c = g << 3, rr = threadIdx.x / groups;
-    float s[8] = {0};
+    const int c = (threadIdx.x % groups) << 3, rr = threadIdx.x / groups;
+    float s[1][8] = {};
     if (rr < rpb) {
         if ((int)blockIdx.x < nb) {
             const int64_t M = (int64_t)B * D * H * W, step = (int64_t)nb * rpb;
@@ -630,13 +622,13 @@ __global__ void __launch_bounds__(256) k_box_partials(const void *__restrict__ x
                 load8(x, dt, (m + 2 * step) * C + c, v2);
                 load8(x, dt, (m + 3 * step) * C + c, v3);
 #pragma unroll
-                for (int j = 0; j < 8; ++j) s[j] += (v0[j] + v1[j]) + (v2[j] + v3[j]);
+                for (int j = 0; j < 8; ++j) s[0][j] += (v0[j] + v1[j]) + (v2[j] + v3[j]);
             }
             for (; m < M; m += step) {
                 float v[8];
                 load8(x, dt, m * C + c, v);
 #pragma unroll
-                for (int j = 0; j < 8; ++j) s[j] += v[j];
+                for (int j = 0; j < 8; ++j) s[0][j] += v[j];
             }
         } else {
             const int k = (blockIdx.x - nb) / BOX_EB, part = (blockIdx.x - nb) % BOX_EB;     // BOX_EB blocks share an edge
@@ -652,18 +644,12 @@ __global__ void __launch_bounds__(256) k_box_partials(const void *__restrict__ x
                 float v[8];
                 load8(x, dt, ((bd * H + h) * W + w) * C + c, v);
 #pragma unroll
-                for (int j = 0; j < 8; ++j) s[j] += v[j];
+                for (int j = 0; j < 8; ++j) s[0][j] += v[j];
             }
         }
     }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) red[threadIdx.x * 8 + j] = s[j];
-    __syncthreads();
-    for (int t = threadIdx.x; t < C; t += 256) {
-        float acc = 0.f;
-        for (int r = 0; r < rpb; ++r) acc += red[(r * groups + (t >> 3)) * 8 + (t & 7)];
-        slab[(size_t)blockIdx.x * C + t] = acc;
-    }
+    float *row = slab + (size_t)blockIdx.x * C;
+    block_reduce<1, float>(s, groups, rpb, [&](int, int ch, float v) { row[ch] = v; });
 }
 
 // T[ci] = sum over taps (kd,kh,kw) and co of  Box(kh,kw)[co] * w[co][ci][kd][kh][kw]   (w: the torch Conv3d weight, fp32), with
@@ -715,18 +701,7 @@ __global__ void __launch_bounds__(256) k_box_total(const float *__restrict__ sla
         double e[8];
         for (int k = 0; k < 8; ++k) e[k] = edge[k][co];
         for (int hc = 0; hc < 3; ++hc)
-            for (int wc = 0; wc < 3; ++wc) {
-                double v = tot;
-                if (hc == 0) v -= e[0];
-                if (hc == 2) v -= e[1];
-                if (wc == 0) v -= e[2];
-                if (wc == 2) v -= e[3];
-                if (hc == 0 && wc == 0) v += e[4];
-                if (hc == 0 && wc == 2) v += e[5];
-                if (hc == 2 && wc == 0) v += e[6];
-                if (hc == 2 && wc == 2) v += e[7];
-                box[hc * 3 + wc][co] = v;
-            }
+            for (int wc = 0; wc < 3; ++wc) box[hc * 3 + wc][co] = box_from_edges(tot, e, hc, wc);
     }
     __syncthreads();
     double t = 0.0;
@@ -767,6 +742,54 @@ inline int apply_epl(int64_t total) {
     return r < 1 ? 1 : (r > 4 ? 4 : (int)r);
 }
 inline bool rows_ok(int C, int64_t stride) { return C >= 8 && (C & 7) == 0 && C <= 2048 && (stride & 7) == 0; }
+inline unsigned bwd_reduce_blocks(int64_t M, int C) {
+    const int rpb = 256 / (C >> 3);
+    return gs_blocks(M, rpb * bwd_rpl(M, rpb), 2048);
+}
+
+// ---- one launcher per row kernel (grid rule + launch line), behind the entry points' own argument checks.
+//      fold: the BEV fold's H*W, 0 for plain rows; flags / inactive: NULL unless FLAGGED
+template <bool FLAGGED>
+int launch_bn_apply(const void *y, vnDtype ydt, int64_t ystride, int64_t M, int C, const float *stats, int relu, void *a,
+                    vnDtype adt, int64_t astride, int64_t lo_off, int64_t fold, const uint8_t *flags, const float *inactive,
+                    vnStream stream) {
+    k_bn_apply<FLAGGED><<<gs_blocks(M * (C >> 3), 256, 8192), 256, 0, vn_stream(stream)>>>(
+        y, (int)ydt, ystride, M, C, stats, relu, a, (int)adt, astride, lo_off, fold, flags, inactive);
+    VN_LAUNCH_STATUS();
+    return VN_OK;
+}
+// sums (double atomics) or slab (one row per workgroup): exactly one is non-NULL
+template <bool FLAGGED>
+int launch_bn_bwd_reduce(const void *da, vnDtype dadt, int64_t dastride, const void *y, vnDtype ydt, int64_t ystride, int64_t M,
+                         int C, const float *stats, int relu, double *sums, float *slab, int64_t fold, const uint8_t *flags,
+                         const float *inactive, vnStream stream) {
+    k_bn_bwd_reduce<FLAGGED><<<bwd_reduce_blocks(M, C), 256, 0, vn_stream(stream)>>>(
+        da, (int)dadt, dastride, y, (int)ydt, ystride, M, C, stats, relu, sums, slab, fold, flags, inactive);
+    VN_LAUNCH_STATUS();
+    return VN_OK;
+}
+int launch_bn_bwd_apply(const void *da, vnDtype dadt, int64_t dastride, const void *y, vnDtype ydt, int64_t ystride, int64_t M,
+                        int C, const float *stats, const float *coef, int relu, void *dy, vnDtype dydt, int64_t dystride,
+                        int64_t lo_off, const uint8_t *flags, int64_t fold, vnStream stream) {
+    const int64_t total = M * (C >> 3);
+    k_bn_bwd_apply<<<gs_blocks(total, 256 * apply_epl(total), 8192), 256, 0, vn_stream(stream)>>>(
+        da, (int)dadt, dastride, y, (int)ydt, ystride, M, C, stats, coef, relu, dy, (int)dydt, dystride, lo_off, flags, fold);
+    VN_LAUNCH_STATUS();
+    return VN_OK;
+}
+// vn_bn_bwd_apply_list (da dense) and vn_bn_bwd_apply_list_rows (da_compact: [cap][C] rows in list order) in full
+int bn_bwd_apply_list(const void *da, vnDtype dadt, const void *y, vnDtype ydt, int C, int D, int H, int W, const float *stats,
+                      const float *coef, int relu, void *dy, vnDtype dydt, const int64_t *list, const int32_t *count,
+                      int64_t cap, int da_compact, vnStream stream) {
+    VN_CHECK_ARG(rows_ok(C, C) && 256 % (C >> 3) == 0 && D > 0 && H > 0 && W > 0 && cap >= 0);
+    if (cap == 0) return VN_OK;
+    VN_CHECK_ARG(da && y && stats && coef && dy && list);
+    const int rpb = 256 / (C >> 3);
+    k_bn_bwd_apply_list<<<gs_blocks(cap, rpb * 2, 4096), 256, 0, vn_stream(stream)>>>(
+        da, (int)dadt, y, (int)ydt, C, D, H, W, stats, coef, relu, dy, (int)dydt, list, count, cap, da_compact);
+    VN_LAUNCH_STATUS();
+    return VN_OK;
+}
 
 }  // namespace
 
@@ -807,11 +830,7 @@ extern "C" int vn_bn_apply(const void *y, vnDtype y_dtype, int64_t y_stride, int
     VN_CHECK_ARG(M >= 0 && rows_ok(C, y_stride) && (a_stride & 7) == 0 && (lo_off & 7) == 0 && lo_off >= 0 && (!lo_off || a_dtype == VN_BF16));
     if (M == 0) return VN_OK;
     VN_CHECK_ARG(y && a && stats);
-    k_bn_apply<false><<<gs_blocks(M * (C >> 3), 256, 8192), 256, 0, vn_stream(stream)>>>(y, (int)y_dtype, y_stride, M, C, stats,
-                                                                                          relu, a, (int)a_dtype, a_stride, lo_off, 0,
-                                                                                          nullptr, nullptr, 1);
-    VN_LAUNCH_STATUS();
-    return VN_OK;
+    return launch_bn_apply<false>(y, y_dtype, y_stride, M, C, stats, relu, a, a_dtype, a_stride, lo_off, 0, nullptr, nullptr, stream);
 }
 
 // vn_bn_apply for a conv output whose rows with row_flags[m] == 0 all hold `inactive` (float[C], e.g. the conv bias of
@@ -823,11 +842,7 @@ extern "C" int vn_bn_apply_flagged(const void *y, vnDtype y_dtype, int64_t y_str
     VN_CHECK_ARG(M >= 0 && rows_ok(C, y_stride) && (a_stride & 7) == 0);
     if (M == 0) return VN_OK;
     VN_CHECK_ARG(y && a && stats && row_flags && inactive);
-    k_bn_apply<true><<<gs_blocks(M * (C >> 3), 256, 8192), 256, 0, vn_stream(stream)>>>(y, (int)y_dtype, y_stride, M, C, stats,
-                                                                                         relu, a, (int)a_dtype, a_stride, 0, 0,
-                                                                                         row_flags, inactive, 1);
-    VN_LAUNCH_STATUS();
-    return VN_OK;
+    return launch_bn_apply<true>(y, y_dtype, y_stride, M, C, stats, relu, a, a_dtype, a_stride, 0, 0, row_flags, inactive, stream);
 }
 
 extern "C" int vn_bn_bwd_reduce(const void *da, vnDtype da_dtype, int64_t da_stride, const void *y, vnDtype y_dtype,
@@ -836,29 +851,21 @@ extern "C" int vn_bn_bwd_reduce(const void *da, vnDtype da_dtype, int64_t da_str
     VN_CHECK_ARG(sums && M >= 0 && rows_ok(C, y_stride) && (da_stride & 7) == 0);
     if (M == 0) return VN_OK;
     VN_CHECK_ARG(da && y && stats);
-    const int rpb = 256 / (C >> 3);
-    k_bn_bwd_reduce<false><<<gs_blocks(M, rpb * bwd_rpl(M, rpb), 2048), 256, 0, vn_stream(stream)>>>(da, (int)da_dtype, da_stride, y,
-                                                                                 (int)y_dtype, y_stride, M, C, stats,
-                                                                                 relu, sums, nullptr, 0, nullptr, nullptr);
-    VN_LAUNCH_STATUS();
-    return VN_OK;
+    return launch_bn_bwd_reduce<false>(da, da_dtype, da_stride, y, y_dtype, y_stride, M, C, stats, relu, sums, nullptr, 0, nullptr,
+                                       nullptr, stream);
 }
 
 extern "C" int64_t vn_bn_bwd_slab_rows(int64_t M, int32_t C) {
     if (M <= 0 || !rows_ok(C, 8)) return 0;
-    return gs_blocks(M, (256 / (C >> 3)) * bwd_rpl(M, 256 / (C >> 3)), 2048);
+    return bwd_reduce_blocks(M, C);
 }
 
 extern "C" int vn_bn_bwd_reduce_slab(const void *da, vnDtype da_dtype, int64_t da_stride, const void *y, vnDtype y_dtype,
                                      int64_t y_stride, int64_t M, int32_t C, const float *stats, int32_t relu,
                                      float *slab, vnStream stream) {
     VN_CHECK_ARG(slab && M > 0 && rows_ok(C, y_stride) && (da_stride & 7) == 0 && da && y && stats);
-    const int rpb = 256 / (C >> 3);
-    k_bn_bwd_reduce<false><<<gs_blocks(M, rpb * bwd_rpl(M, rpb), 2048), 256, 0, vn_stream(stream)>>>(da, (int)da_dtype, da_stride, y,
-                                                                                 (int)y_dtype, y_stride, M, C, stats,
-                                                                                 relu, nullptr, slab, 0, nullptr, nullptr);
-    VN_LAUNCH_STATUS();
-    return VN_OK;
+    return launch_bn_bwd_reduce<false>(da, da_dtype, da_stride, y, y_dtype, y_stride, M, C, stats, relu, nullptr, slab, 0, nullptr,
+                                       nullptr, stream);
 }
 
 // vn_bn_bwd_reduce_slab for a y whose rows with row_flags[m] == 0 all hold `inactive` (see vn_bn_apply_flagged): y is
@@ -868,19 +875,15 @@ extern "C" int vn_bn_bwd_reduce_slab_flagged(const void *da, vnDtype da_dtype, i
                                              int32_t relu, float *slab, const uint8_t *row_flags, const float *inactive,
                                              vnStream stream) {
     VN_CHECK_ARG(slab && M > 0 && rows_ok(C, y_stride) && (da_stride & 7) == 0 && da && y && stats && row_flags && inactive);
-    const int rpb = 256 / (C >> 3);
-    k_bn_bwd_reduce<true><<<gs_blocks(M, rpb * bwd_rpl(M, rpb), 2048), 256, 0, vn_stream(stream)>>>(da, (int)da_dtype, da_stride, y,
-                                                                                 (int)y_dtype, y_stride, M, C, stats,
-                                                                                 relu, nullptr, slab, 0, row_flags, inactive);
-    VN_LAUNCH_STATUS();
-    return VN_OK;
+    return launch_bn_bwd_reduce<true>(da, da_dtype, da_stride, y, y_dtype, y_stride, M, C, stats, relu, nullptr, slab, 0, row_flags,
+                                      inactive, stream);
 }
 
 extern "C" int vn_bn_bwd_finalize_slab(const float *slab, int64_t slab_rows, int64_t M, int32_t C, const float *gamma,
                                        const float *stats, float *coef, float *d_gamma, float *d_beta,
                                        vnStream stream) {
     VN_CHECK_ARG(slab && gamma && stats && coef && slab_rows > 0 && M > 0 && C > 0);
-    k_bn_bwd_finalize_slab<<<C, 256, 0, vn_stream(stream)>>>(slab, (int)slab_rows, M, C, gamma, stats, coef, d_gamma,
+    k_bn_bwd_finalize_slab<<<C, 256, 0, vn_stream(stream)>>>(slab, slab_rows, M, C, gamma, stats, coef, d_gamma,
                                                              d_beta);
     VN_LAUNCH_STATUS();
     return VN_OK;
@@ -902,11 +905,8 @@ extern "C" int vn_bn_bwd_apply(const void *da, vnDtype da_dtype, int64_t da_stri
     VN_CHECK_ARG(lo_off >= 0 && (lo_off & 7) == 0 && (!lo_off || dy_dtype == VN_BF16));
     if (M == 0) return VN_OK;
     VN_CHECK_ARG(da && y && stats && coef && dy);
-    k_bn_bwd_apply<<<gs_blocks(M * (C >> 3), 256 * apply_epl(M * (C >> 3)), 8192), 256, 0, vn_stream(stream)>>>(
-        da, (int)da_dtype, da_stride, y, (int)y_dtype, y_stride, M, C, stats, coef, relu, dy, (int)dy_dtype, dy_stride,
-        lo_off, nullptr, 0);
-    VN_LAUNCH_STATUS();
-    return VN_OK;
+    return launch_bn_bwd_apply(da, da_dtype, da_stride, y, y_dtype, y_stride, M, C, stats, coef, relu, dy, dy_dtype, dy_stride, lo_off,
+                               nullptr, 0, stream);
 }
 
 // Row-flag variant for the first middle layer, whose weight- and data-gradient only gather dy at the sites with an
@@ -918,11 +918,8 @@ extern "C" int vn_bn_bwd_apply_flagged(const void *da, vnDtype da_dtype, int64_t
     VN_CHECK_ARG(M >= 0 && rows_ok(C, y_stride) && (da_stride & 7) == 0 && (dy_stride & 7) == 0);
     if (M == 0) return VN_OK;
     VN_CHECK_ARG(da && y && stats && coef && dy && row_flags);
-    k_bn_bwd_apply<<<gs_blocks(M * (C >> 3), 256 * apply_epl(M * (C >> 3)), 8192), 256, 0, vn_stream(stream)>>>(
-        da, (int)da_dtype, da_stride, y, (int)y_dtype, y_stride, M, C, stats, coef, relu, dy, (int)dy_dtype, dy_stride, 0,
-        row_flags, 0);
-    VN_LAUNCH_STATUS();
-    return VN_OK;
+    return launch_bn_bwd_apply(da, da_dtype, da_stride, y, y_dtype, y_stride, M, C, stats, coef, relu, dy, dy_dtype, dy_stride, 0,
+                               row_flags, 0, stream);
 }
 
 // ---- BEV-fold variants for the last Conv3d (model.py:262: its (B,2,H,W,64) output is the (B,1,H,W,128) input of
@@ -932,10 +929,7 @@ extern "C" int vn_bn_apply_bev(const void *y, vnDtype y_dtype, int64_t M, int32_
                                int32_t relu, void *a, vnDtype a_dtype, int64_t wide_stride, vnStream stream) {
     VN_CHECK_ARG(M > 0 && rows_ok(C, C) && hw > 0 && M % (2 * hw) == 0 && wide_stride >= 2 * C && (wide_stride & 7) == 0);
     VN_CHECK_ARG(y && a && stats);
-    k_bn_apply<false><<<gs_blocks(M * (C >> 3), 256, 8192), 256, 0, vn_stream(stream)>>>(y, (int)y_dtype, C, M, C, stats, relu, a,
-                                                                                          (int)a_dtype, wide_stride, 0, hw, nullptr, nullptr, 0);
-    VN_LAUNCH_STATUS();
-    return VN_OK;
+    return launch_bn_apply<false>(y, y_dtype, C, M, C, stats, relu, a, a_dtype, wide_stride, 0, hw, nullptr, nullptr, stream);
 }
 
 extern "C" int vn_bn_bwd_reduce_slab_bev(const void *da, vnDtype da_dtype, int64_t wide_stride, const void *y,
@@ -943,11 +937,8 @@ extern "C" int vn_bn_bwd_reduce_slab_bev(const void *da, vnDtype da_dtype, int64
                                          int32_t relu, float *slab, vnStream stream) {
     VN_CHECK_ARG(slab && M > 0 && rows_ok(C, C) && hw > 0 && M % (2 * hw) == 0 && wide_stride >= 2 * C && (wide_stride & 7) == 0);
     VN_CHECK_ARG(da && y && stats);
-    const int rpb = 256 / (C >> 3);
-    k_bn_bwd_reduce<false><<<gs_blocks(M, rpb * bwd_rpl(M, rpb), 2048), 256, 0, vn_stream(stream)>>>(da, (int)da_dtype, wide_stride, y, (int)y_dtype,
-                                                                                 C, M, C, stats, relu, nullptr, slab, hw, nullptr, nullptr);
-    VN_LAUNCH_STATUS();
-    return VN_OK;
+    return launch_bn_bwd_reduce<false>(da, da_dtype, wide_stride, y, y_dtype, C, M, C, stats, relu, nullptr, slab, hw, nullptr, nullptr,
+                                       stream);
 }
 
 extern "C" int vn_bn_bwd_apply_bev(const void *da, vnDtype da_dtype, int64_t wide_stride, const void *y, vnDtype y_dtype,
@@ -955,10 +946,8 @@ extern "C" int vn_bn_bwd_apply_bev(const void *da, vnDtype da_dtype, int64_t wid
                                    void *dy, vnDtype dy_dtype, vnStream stream) {
     VN_CHECK_ARG(M > 0 && rows_ok(C, C) && hw > 0 && M % (2 * hw) == 0 && wide_stride >= 2 * C && (wide_stride & 7) == 0);
     VN_CHECK_ARG(da && y && stats && coef && dy);
-    k_bn_bwd_apply<<<gs_blocks(M * (C >> 3), 256 * apply_epl(M * (C >> 3)), 8192), 256, 0, vn_stream(stream)>>>(
-        da, (int)da_dtype, wide_stride, y, (int)y_dtype, C, M, C, stats, coef, relu, dy, (int)dy_dtype, C, 0, nullptr, hw);
-    VN_LAUNCH_STATUS();
-    return VN_OK;
+    return launch_bn_bwd_apply(da, da_dtype, wide_stride, y, y_dtype, C, M, C, stats, coef, relu, dy, dy_dtype, C, 0, nullptr, hw,
+                               stream);
 }
 
 // vn_bn_bwd_apply at the rows of a site list only (vn_active_sites' (b,d,h,w) list and its device-side count): da, y, dy
@@ -967,25 +956,14 @@ extern "C" int vn_bn_bwd_apply_list(const void *da, vnDtype da_dtype, const void
                                     int32_t H, int32_t W, const float *stats, const float *coef, int32_t relu, void *dy,
                                     vnDtype dy_dtype, const int64_t *list, const int32_t *count, int64_t cap,
                                     vnStream stream) {
-    VN_CHECK_ARG(rows_ok(C, C) && 256 % (C >> 3) == 0 && D > 0 && H > 0 && W > 0 && cap >= 0);
-    if (cap == 0) return VN_OK;
-    VN_CHECK_ARG(da && y && stats && coef && dy && list);
-    const int rpb = 256 / (C >> 3);
-    k_bn_bwd_apply_list<<<gs_blocks(cap, rpb * 2, 4096), 256, 0, vn_stream(stream)>>>(da, (int)da_dtype, y, (int)y_dtype, C, D, H, W,
-                                                                                       stats, coef, relu, dy, (int)dy_dtype,
-                                                                                       list, count, cap, 0);
-    VN_LAUNCH_STATUS();
-    return VN_OK;
+    return bn_bwd_apply_list(da, da_dtype, y, y_dtype, C, D, H, W, stats, coef, relu, dy, dy_dtype, list, count, cap, 0, stream);
 }
 
 namespace {
 
 // value the activation a = relu(BN(y)) holds at the sites where y = inactive[c] (stored in y's dtype), as stored in a's dtype
 __device__ __forceinline__ float inactive_act(const float *stats, const float *inactive, int C, int c, int ydt, int adt, int relu) {
-    const float v = as_stored(inactive[c], ydt);
-    float z = fmaf(stats[2 * C + c], v - stats[c], stats[3 * C + c]);
-    if (relu) z = fmaxf(z, 0.f);
-    return as_stored(z, adt);
+    return as_stored(bn_fwd(as_stored(inactive[c], ydt), stats[c], stats[2 * C + c], stats[3 * C + c], relu ? 1 : 0), adt);
 }
 
 // delta[e][:] = a(site e)[:] - (the inactive sites' activation) for the listed sites: the sparse part of an activation that
@@ -999,14 +977,12 @@ __global__ void __launch_bounds__(256) k_act_delta_rows(const void *__restrict__
     const int groups = C >> 3, rpb = 256 / groups;
     const int c = (threadIdx.x % groups) << 3, rr = threadIdx.x / groups;
     if (rr >= rpb) return;
-    int64_t n = count ? (int64_t)count[0] : cap;
-    if (n > cap) n = cap;
+    const int64_t n = list_len(count, cap);
     float cv[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) cv[j] = inactive_act(stats, inactive, C, c + j, ydt, adt, relu);
     for (int64_t e = (int64_t)blockIdx.x * rpb + rr; e < n; e += (int64_t)gridDim.x * rpb) {
-        const int64_t *rc = list + e * 4;
-        const int64_t m = ((rc[0] * D + rc[1]) * H + rc[2]) * W + rc[3];
+        const int64_t m = site_row(list, e, D, H, W);
         float v[8];
         load8(a, adt, m * C + c, v);
 #pragma unroll
@@ -1029,26 +1005,12 @@ __global__ void __launch_bounds__(256) k_wgrad_const_add(float *__restrict__ dw,
     //  they were nine 8-barrier LDS trees in a row)
     for (int k = threadIdx.x >> 6; k < 9; k += 4) {
         const int r0 = k == 0 ? 0 : nb + (k - 1) * BOX_EB, rn = k == 0 ? nb : BOX_EB;
-        double a = 0.0;
-        for (int r = threadIdx.x & 63; r < rn; r += 64) a += (double)slab[(size_t)(r0 + r) * Co + co];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
-        if ((threadIdx.x & 63) == 0) sums[k] = a;
+        double a[1];
+        wave_col_sums<1>(slab + (size_t)r0 * Co + co, Co, threadIdx.x & 63, rn, 64, a);
+        if ((threadIdx.x & 63) == 0) sums[k] = a[0];
     }
     __syncthreads();
-    if (threadIdx.x < 9) {
-        const int hc = threadIdx.x / 3, wc = threadIdx.x % 3;
-        double v = sums[0];
-        if (hc == 0) v -= sums[1];
-        if (hc == 2) v -= sums[2];
-        if (wc == 0) v -= sums[3];
-        if (wc == 2) v -= sums[4];
-        if (hc == 0 && wc == 0) v += sums[5];
-        if (hc == 0 && wc == 2) v += sums[6];
-        if (hc == 2 && wc == 0) v += sums[7];
-        if (hc == 2 && wc == 2) v += sums[8];
-        box[threadIdx.x] = (float)v;
-    }
+    if (threadIdx.x < 9) box[threadIdx.x] = (float)box_from_edges(sums[0], sums + 1, threadIdx.x / 3, threadIdx.x % 3);
     __syncthreads();
     const int per = kD * 9;
     for (int i = threadIdx.x; i < Ci * per; i += 256) {
@@ -1080,7 +1042,7 @@ extern "C" int vn_bn_bwd_finalize_list(const float *slab, int64_t slab_rows, int
                                        const float *stats, const float *total, const float *inactive, vnDtype y_dtype,
                                        int32_t relu, float *coef, float *d_gamma, float *d_beta, vnStream stream) {
     VN_CHECK_ARG(slab && gamma && stats && total && inactive && coef && slab_rows > 0 && M > 0 && C > 0);
-    k_bn_bwd_finalize_list<<<C, 256, 0, vn_stream(stream)>>>(slab, (int)slab_rows, M, C, gamma, stats, total, inactive, (int)y_dtype,
+    k_bn_bwd_finalize_list<<<C, 256, 0, vn_stream(stream)>>>(slab, slab_rows, M, C, gamma, stats, total, inactive, (int)y_dtype,
                                                              relu, coef, d_gamma, d_beta);
     VN_LAUNCH_STATUS();
     return VN_OK;
@@ -1089,15 +1051,7 @@ extern "C" int vn_bn_bwd_apply_list_rows(const void *da_rows, vnDtype da_dtype, 
                                          int32_t D, int32_t H, int32_t W, const float *stats, const float *coef, int32_t relu,
                                          void *dy, vnDtype dy_dtype, const int64_t *list, const int32_t *count, int64_t cap,
                                          vnStream stream) {
-    VN_CHECK_ARG(rows_ok(C, C) && 256 % (C >> 3) == 0 && D > 0 && H > 0 && W > 0 && cap >= 0);
-    if (cap == 0) return VN_OK;
-    VN_CHECK_ARG(da_rows && y && stats && coef && dy && list);
-    const int rpb = 256 / (C >> 3);
-    k_bn_bwd_apply_list<<<gs_blocks(cap, rpb * 2, 4096), 256, 0, vn_stream(stream)>>>(da_rows, (int)da_dtype, y, (int)y_dtype, C, D,
-                                                                                       H, W, stats, coef, relu, dy, (int)dy_dtype,
-                                                                                       list, count, cap, 1);
-    VN_LAUNCH_STATUS();
-    return VN_OK;
+    return bn_bwd_apply_list(da_rows, da_dtype, y, y_dtype, C, D, H, W, stats, coef, relu, dy, dy_dtype, list, count, cap, 1, stream);
 }
 // total[ci] = sum over ALL sites of the data gradient of a 3x3x(kD) convolution (stride 1 and padding 1 in H/W, no padding in
 // D) with the torch weight w (Co,Ci,kD,3,3) fp32, from box sums of its dense output gradient dy (B,D,H,W,Co); two launches
