@@ -1083,6 +1083,48 @@ int vn_eval_match(const float *det_boxes, const float *det_scores, const int32_t
                   int32_t n_diff, double thr_bev, double thr_3d, int8_t *status, int32_t *matched_gt, double *iou_out,
                   void *workspace, size_t workspace_bytes, vnStream stream);
 
+/* ---- image-plane scoring (eval.py:4-5 is empty in the reference; rules: DESIGN.md section 1b-bis, which restates
+ * the image-plane rules of KITTI's object devkit: 2D AP, AOS, DontCare regions, the 2D-height bar) ----------------
+ * vn_boxes_to_image: one thread per detection slot.  det_boxes [B,top_k,7] float32 lidar boxes, det_counts [B] read ON
+ * THE DEVICE, calib [B,24] float64 = per frame [M | P2], both 3x4 row-major, M = (R0_rect . Tr_velo_to_cam)[:3],
+ * image_hw [B,2] int32 = (H, W).  All arithmetic float64.
+ *   centre c = M.(x,y,z,1);  ry = wrap(-r - pi/2);  alpha = wrap(ry - atan2(c_x, c_z));  wrap: into (-pi, pi]
+ *   the eight corners of the LIDAR-frame box (footprint (+-l/2, +-w/2) turned by r about (x, y), at z and z + h) map by
+ *   q = P2.(M.corner, 1), u = q0/q2, v = q1/q2, depth q2;  x1 = max(min u, 0), y1 = max(min v, 0),
+ *   x2 = min(max u, W-1), y2 = min(max v, H-1)
+ *   on the image <=> every field finite, h, w, l > 0, all eight depths > 0.1, x2 > x1 and y2 > y1
+ *   rows     [B,top_k,VN_EVAL_IMAGE_ROW] float64: alpha x1 y1 x2 y2 h w l xc yc zc ry (KITTI's result-line order)
+ *   on_image [B,top_k] uint8
+ * A slot beyond det_counts[b], and a box with a non-finite field or h, w or l <= 0: twelve zeros, on_image 0.  Any
+ * other detection that is off the image: x1 = y1 = x2 = y2 = 0, the other eight fields as computed, on_image 0.
+ *
+ * vn_eval_match_image: vn_eval_match with a third metric (VN_EVAL_BBOX: IoU of two axis-aligned 2D boxes, areas without
+ * "+1", 0 when the union is <= 0) and the image-plane rules.  Takes what vn_eval_match takes, plus image_rows / on_image
+ * (vn_boxes_to_image's outputs), gt_bbox [B,max_gt,4] and gt_alpha [B,max_gt] float64 (the label's x1 y1 x2 y2 and alpha),
+ * dc_boxes [B,max_dc,4] float64 with dc_counts [B] (DontCare regions; 0 <= max_dc <= VN_EVAL_MAX_DC, both may be NULL
+ * when max_dc == 0), min_height [n_diff] float64 ON THE DEVICE, and one threshold per metric.  Per frame, metric and
+ * difficulty, vn_eval_match's walk with:
+ *   - a detection with on_image == 0 or y2 - y1 < min_height[difficulty] is IGNORED (-1) before the walk and takes no
+ *     ground truth;
+ *   - after the walk, a detection left FP becomes IGNORED when area(det & D) / area(det) > 0.5 for a DontCare region D.
+ *   status, matched_gt [B,3,n_diff,top_k]: as vn_eval_match's; axis 1: VN_EVAL_BEV, VN_EVAL_3D, VN_EVAL_BBOX
+ *   similarity [B,n_diff,top_k] float64: (1 + cos(alpha_det - alpha_gt)) / 2 for a TP of the VN_EVAL_BBOX matching,
+ *                                        else 0 (slots beyond the count included)
+ *   iou_out    [B,3,top_k,max_gt] float64 or NULL;  workspace: vn_eval_match_workspace_bytes, the walk order as there
+ * One workgroup per frame, one launch, no host synchronisation; limits and VN_EINVAL as vn_eval_match. */
+#define VN_EVAL_BBOX 2
+#define VN_EVAL_MAX_DC 64
+#define VN_EVAL_IMAGE_ROW 12
+int vn_boxes_to_image(const float *det_boxes, const int32_t *det_counts, const double *calib, const int32_t *image_hw,
+                      int32_t B, int32_t top_k, double *rows, uint8_t *on_image, vnStream stream);
+int vn_eval_match_image(const float *det_boxes, const float *det_scores, const int32_t *det_counts, const double *gt,
+                        const int32_t *gt_counts, const uint8_t *gt_flags, const double *image_rows,
+                        const uint8_t *on_image, const double *gt_bbox, const double *gt_alpha, const double *dc_boxes,
+                        const int32_t *dc_counts, const double *min_height, int32_t B, int32_t top_k, int32_t max_gt,
+                        int32_t max_dc, int32_t n_diff, double thr_bev, double thr_3d, double thr_bbox, int8_t *status,
+                        int32_t *matched_gt, double *similarity, double *iou_out, void *workspace, size_t workspace_bytes,
+                        vnStream stream);
+
 /* ---- detection tail for evaluation (csrc/detect.hip; rules: DESIGN.md section 1c) ---------------------------
  * Extends the inference tail above (filter_boxes model.py:28-57, deltas_to_boxes_3d utils.py:476-489, utils.nms
  * utils.py:492-553), which lets only the NMS_POST_TOPK = 20 best candidates enter a stand-up-rectangle NMS

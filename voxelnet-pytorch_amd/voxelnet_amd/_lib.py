@@ -148,6 +148,7 @@ class VnGtBox(ctypes.Structure):   # vnGtBox (vn_points_in_boxes, vn_gt_paste): 
 VN_GT_MAX_BOXES = 128
 VN_EVAL_BEV, VN_EVAL_3D = 0, 1       # vn_box_iou_rotated's `metric`; axis 1 of vn_eval_match's outputs
 VN_EVAL_MAX_TOPK, VN_EVAL_MAX_DIFF = 32, 8
+VN_EVAL_BBOX, VN_EVAL_MAX_DC, VN_EVAL_IMAGE_ROW = 2, 64, 12       # vn_eval_match_image's third metric; vn_boxes_to_image's row
 VN_NMS_STANDUP, VN_NMS_ROTATED = 0, 1       # vn_box_nms' / vn_rpn_detect's `mode`
 VN_DETECT_MAX_PRE, VN_PREDICT_MAX_TOPK = 4096, 64
 
@@ -298,6 +299,8 @@ SIGNATURES = {
     "vn_eval_match_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32]),
     "vn_eval_match": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, ctypes.c_double, ctypes.c_double,
                               c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "vn_boxes_to_image": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp]),
+    "vn_eval_match_image": (c_i32, [c_vp] * 13 + [c_i32] * 5 + [ctypes.c_double] * 3 + [c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "vn_rpn_select_decode_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32]),
     "vn_rpn_select_decode": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, c_i32, ctypes.c_double, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz,
                                      c_vp]),

@@ -10,16 +10,16 @@ import torch
 from . import _lib
 
 
-def load_calib(calib_path):
+def load_calib(calib_path, dtype=np.float32):
     """preprocess_data.py:18-39: KITTI object calibration file -> (P2 (3,4), Tr_velo_to_cam (4,4), R_cam_to_rect (4,4))
-    float32"""
+    float32 (dtype=np.float64: as parsed, what evaluate.KittiDetectionEvaluator scores with)"""
     with open(calib_path) as fh:
         lines = [line.split()[1:] for line in fh.readlines()][:-1]
     P = np.array(lines[2], dtype=np.float64).reshape(3, 4)
     Tr = np.concatenate([np.array(lines[5], dtype=np.float64).reshape(3, 4), np.array([[0.0, 0.0, 0.0, 1.0]])], 0)
     R = np.eye(4)
     R[:3, :3] = np.array(lines[4][:9], dtype=np.float64).reshape(3, 3)
-    return P.astype(np.float32), Tr.astype(np.float32), R.astype(np.float32)
+    return P.astype(dtype), Tr.astype(dtype), R.astype(dtype)
 
 
 def fov_crop_device(points, P, Tr_velo_to_cam, R_cam_to_rect, image_rows, image_cols, return_index=False, padded=False):

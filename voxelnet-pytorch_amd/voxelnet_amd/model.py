@@ -1088,7 +1088,7 @@ class RPN3D(nn.Module):
             self.anchors = dec.anchors
         return dec
 
-    def evaluate(self, batches, device, evaluator=None, decoder=None, decode=None, ema=None):
+    def evaluate(self, batches, device, evaluator=None, decoder=None, decode=None, ema=None, calib=None):
         """The validation loop a user would otherwise write around `predict`: every batch tuple of `batches` (the
         7-tuples forward takes; x[1] = label lines) goes through an eval-mode, no_grad forward, BoxDecoder.decode_device
         and evaluator.update — the maps, the decoded boxes and the matching stay on the device, nothing is waited for
@@ -1098,9 +1098,20 @@ class RPN3D(nn.Module):
         the reference's tail); the post-NMS cap is always evaluator.top_k.  ema: an ema.ModelEMA of this module — the loop then
         runs inside `ema.applied()`, i.e. scores the averaged weights (and averaged running statistics); the eval forward
         reads the parameters afresh at every call (weights are packed per forward, nothing is cached from their values), so
-        the exchange needs no invalidation.  The module is back in the mode it was in afterwards, and holds its own weights."""
-        from .evaluate import DetectionEvaluator
+        the exchange needs no invalidation.  The module is back in the mode it was in afterwards, and holds its own weights.
+        calib: None — the protocol of DESIGN.md §1b, as above; or "mean", a directory of <tag>.txt KITTI calibration files,
+        or a callable tag -> (P2, Tr_velo_to_cam, R0_rect): KITTI's image-plane protocol (§1b-bis).  The evaluator is then an
+        evaluate.KittiDetectionEvaluator (default: a new one); x[0]'s tags pick each frame's calibration and are
+        remembered for its write_results."""
+        from .evaluate import DetectionEvaluator, KittiDetectionEvaluator, calib_source
         device = torch.device(device)
+        calib_of = None
+        if calib is not None:
+            calib_of = calib_source(calib)
+            if evaluator is None:
+                evaluator = KittiDetectionEvaluator(self.cls_name, device)
+            elif not isinstance(evaluator, KittiDetectionEvaluator):
+                raise ValueError("evaluate: `calib` needs an evaluate.KittiDetectionEvaluator")
         if evaluator is None:
             evaluator = DetectionEvaluator(self.cls_name, device)
         dec = self._box_decoder(device) if decoder is None else decoder
@@ -1115,7 +1126,11 @@ class RPN3D(nn.Module):
             with torch.no_grad(), (ema.applied() if ema is not None else contextlib.nullcontext()):
                 for x in batches:
                     prob, delta = self.detect(_parts_to(x[2], device), _parts_to(x[4], device))
-                    evaluator.update(*dec.decode_device(prob, delta, top_k=evaluator.top_k, **kw), x[1])
+                    det = dec.decode_device(prob, delta, top_k=evaluator.top_k, **kw)
+                    if calib_of is None:
+                        evaluator.update(*det, x[1])
+                    else:
+                        evaluator.update(*det, x[1], calibs=[calib_of(tag) for tag in x[0]], tags=list(x[0]))
         finally:
             self.train(was_training)
         return evaluator
