@@ -32,6 +32,14 @@ def test_fov_crop_full_sweep_and_edges(golden):
     out, idx = fov_crop_device(torch.from_numpy(pts).to(DEV), g["P"], g["Tr"], g["R"], rows, cols, return_index=True)
     assert np.array_equal(idx.cpu().numpy().astype(np.int64), ridx) and np.array_equal(out.cpu().numpy(), ref)
     assert 0.05 * n < out.shape[0] < 0.5 * n
+    # 256, 256, 257 and 513 workgroups: the one-workgroup scan takes 256 counts per trip and carries from row 65,536 on
+    k = 131_073
+    more = np.stack([rng.uniform(-80, 80, k), rng.uniform(-80, 80, k), rng.uniform(-3, 2, k), rng.uniform(0, 1, k)], 1).astype(np.float32)
+    for sub in (pts[:65_535], pts[:65_536], pts[:65_537], more):
+        r, ri = of.fov_crop(sub, g["P"], g["Tr"], g["R"], rows, cols)
+        o, oi = fov_crop_device(torch.from_numpy(np.ascontiguousarray(sub)).to(DEV), g["P"], g["Tr"], g["R"], rows, cols, return_index=True)
+        assert np.array_equal(oi.cpu().numpy().astype(np.int64), ri) and np.array_equal(o.cpu().numpy(), r)
+        assert 0.05 * len(sub) < o.shape[0] < 0.5 * len(sub)
     # empty input, a single point, nothing kept
     for sub in (pts[:0], pts[ridx[:1]], pts[pts[:, 0] < -1][:1000]):
         o = fov_crop_device(torch.from_numpy(np.ascontiguousarray(sub)).to(DEV), g["P"], g["Tr"], g["R"], rows, cols)

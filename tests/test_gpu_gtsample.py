@@ -131,13 +131,21 @@ def test_block_edges(n_boxes):
     rng = np.random.default_rng(7 + n_boxes)
     boxes = _cubes(rng, n_boxes)
     hit = 0
-    for n in (0, 1, 255, 256, 257, 1023, 1025):
-        for m in (0, 1, 300):
+    # 65,535 ... 131,073: 256, 256, 257 and 513 workgroups — the one-workgroup scan takes 256 counts per trip, so its
+    # carry starts at row 65,536 (with boxes only, and without m = 1)
+    for n in (0, 1, 255, 256, 257, 1023, 1025, 65_535, 65_536, 65_537, 131_073):
+        if n >= 65_535 and n_boxes == 0:
+            continue
+        for m in (0, 1, 300) if n < 65_535 else (0, 300):
             cloud = _cloud_near(rng, n, boxes)
             obj = _cloud_near(rng, m, boxes[:0])
             index, counts, _, count = _check_all(cloud, boxes, obj)
             assert counts.shape == (n_boxes,) and count <= n + m
             hit += int((index >= 0).sum())
+            if n >= 65_535:                      # on the restatement alone: kept rows on both sides of row 65,536
+                kept = index < 0
+                assert kept[:65_536].any() and 0 < count - m < n
+                assert n <= 65_536 or kept[65_536:].any()
     assert hit >= (300 if n_boxes else 0)                          # the boxes do take points away
     # cap exactly n + m and larger; rows past the count are NaN
     cloud, obj = _cloud_near(rng, 1025, boxes), _cloud_near(rng, 300, boxes[:0])
@@ -271,7 +279,7 @@ def test_on_a_side_stream_without_host_synchronisation():
 
 
 def test_dense_workload_cloud():
-    """config 5's frame (~300k points, > 1024 workgroups: the scan's per-thread loop runs twice), 32 boxes"""
+    """config 5's frame (~300k points, > 1024 workgroups: the one-workgroup scan makes five trips of 256 counts), 32 boxes"""
     from voxelnet_amd import synth
     cloud = synth.workload_frames(5, batch=1)[0]
     assert cloud.shape[0] > 262144

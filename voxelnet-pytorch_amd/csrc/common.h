@@ -88,6 +88,76 @@ __device__ __forceinline__ int vn_wave_min_i32(int v) {
     return v;
 }
 
+// ---- ordered compaction (count per workgroup -> one-workgroup exclusive scan of the counts -> write each survivor at
+// its scanned position), shared by fov.hip, gtsample.hip, voxelize.hip and sparse.hip.
+// Workgroup-wide exclusive scan of one value per thread (THREADS threads, all of which must reach it): returns the
+// exclusive prefix, *total = the workgroup's sum.  The trailing barrier lets a caller call it again in a loop.
+template <typename T, int THREADS>
+__device__ T vn_block_excl_scan(T v, T *total) {
+    static_assert(THREADS % VN_WAVE == 0, "whole waves");
+    __shared__ T wsum[THREADS / VN_WAVE];
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    T inc = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const T t = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += t;
+    }
+    if (lane == 63) wsum[wid] = inc;
+    __syncthreads();
+    T base = 0, tot = 0;
+#pragma unroll
+    for (int w = 0; w < THREADS / VN_WAVE; ++w) {
+        const T s = wsum[w];
+        if (w < wid) base += s;
+        tot += s;
+    }
+    __syncthreads();
+    *total = tot;
+    return base + inc - v;
+}
+
+// One workgroup of THREADS threads: exclusive scan of blk[0..nb) in place, THREADS sums per trip with a running carry;
+// returns the grand total to every thread.  nb == 0 returns 0 and touches nothing.
+template <typename T, int THREADS>
+__device__ T vn_scan_block_sums(T *blk, int64_t nb) {
+    T carry = 0;
+    for (int64_t base = 0; base < nb; base += THREADS) {
+        const int64_t i = base + threadIdx.x;
+        const T v = i < nb ? blk[i] : T(0);
+        T tot;
+        const T ex = vn_block_excl_scan<T, THREADS>(v, &tot);
+        if (i < nb) blk[i] = carry + ex;
+        carry += tot;
+    }
+    return carry;
+}
+
+// 256-thread workgroup, one flag per thread (wave ballot + popcount, the four wave counts through LDS): the exclusive
+// rank of this thread among the threads whose `keep` is set; *total (optional) = how many are set.  Every thread of the
+// workgroup must reach it (it holds a barrier), and a kernel calls it once: nothing guards wsum against a second call.
+__device__ __forceinline__ int vn_block_rank(bool keep, int *total = nullptr) {
+    __shared__ int wsum[256 / VN_WAVE];
+    const unsigned long long m = __ballot(keep);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) wsum[wave] = __popcll(m);
+    __syncthreads();
+    int base = 0, tot = 0;
+#pragma unroll
+    for (int w = 0; w < 256 / VN_WAVE; ++w) {
+        const int s = wsum[w];
+        if (w < wave) base += s;
+        tot += s;
+    }
+    if (total) *total = tot;
+    return base + __popcll(m & ((1ull << lane) - 1ull));
+}
+__device__ __forceinline__ int vn_block_count(bool keep) {
+    int total;
+    vn_block_rank(keep, &total);
+    return total;
+}
+
 // Buffer descriptor from values the compiler can PROVE wave-uniform (cdna_hip_programming.md T20): without
 // the readfirstlane of the pointer halves and the size, hipcc wraps every buffer_load ... lds that uses the
 // descriptor in a waterfall loop (v_readfirstlane x4 + s_and_saveexec + loop), ~15 instructions and a

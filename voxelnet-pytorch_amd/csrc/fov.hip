@@ -12,7 +12,8 @@
 // fma(m3, p3, fma(m2, p2, fma(m1, p1, m0 * p0))) — the order and contraction of a k-sequential sgemm micro-kernel; a point
 // changes sides only if a coordinate lies within an ulp of a decision boundary (tests/test_gpu_fov.py pins the index set
 // to a fixture made by the imported reference functions on a bundled KITTI frame).
-// Three launches: flags + per-workgroup counts, one-workgroup scan of the counts, order-preserving compaction.
+// Three launches: flags + per-workgroup counts, one-workgroup scan of the counts, order-preserving compaction; the count,
+// scan and rank helpers are the shared ones of common.h.
 #include "common.h"
 
 namespace {
@@ -39,56 +40,27 @@ __device__ __forceinline__ bool fov_keep(const float4 p, const FovCalib &c, int 
 
 __global__ void __launch_bounds__(256) k_fov_flags(const float4 *__restrict__ pts, int64_t n, FovCalib c, int rows, int cols,
                                                    uint8_t *__restrict__ flags, int32_t *__restrict__ block_counts) {
-    __shared__ int wsum[4];
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const bool keep = i < n && fov_keep(pts[i], c, rows, cols);
     if (i < n) flags[i] = keep ? 1 : 0;
-    const unsigned long long m = __ballot(keep);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = __popcll(m);
-    __syncthreads();
-    if (threadIdx.x == 0) block_counts[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    const int kept = vn_block_count(keep);
+    if (threadIdx.x == 0) block_counts[blockIdx.x] = kept;
 }
 
 // exclusive scan of the block counts in place (one workgroup; nb <= a few thousand), total -> *count
-__global__ void __launch_bounds__(1024) k_fov_scan(int32_t *__restrict__ block_counts, int nb, int32_t *__restrict__ count) {
-    __shared__ int part[1024];
-    const int per = (nb + 1023) / 1024;
-    const int b0 = threadIdx.x * per;
-    int s = 0;
-    for (int j = 0; j < per; ++j)
-        if (b0 + j < nb) s += block_counts[b0 + j];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-        const int v = threadIdx.x >= o ? part[threadIdx.x - o] : 0;
-        __syncthreads();
-        part[threadIdx.x] += v;
-        __syncthreads();
-    }
-    int run = part[threadIdx.x] - s;
-    for (int j = 0; j < per; ++j)
-        if (b0 + j < nb) {
-            const int v = block_counts[b0 + j];
-            block_counts[b0 + j] = run;
-            run += v;
-        }
-    if (threadIdx.x == 1023) *count = part[1023];
+__global__ void __launch_bounds__(256) k_fov_scan(int32_t *__restrict__ block_counts, int nb, int32_t *__restrict__ count) {
+    const int32_t total = vn_scan_block_sums<int32_t, 256>(block_counts, nb);
+    if (threadIdx.x == 0) *count = total;
 }
 
 __global__ void __launch_bounds__(256) k_fov_compact(const float4 *__restrict__ pts, int64_t n, const uint8_t *__restrict__ flags,
                                                      const int32_t *__restrict__ block_offsets, float4 *__restrict__ out,
                                                      int32_t *__restrict__ index, const int32_t *__restrict__ count) {
-    __shared__ int wsum[4];
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const bool keep = i < n && flags[i];
-    const unsigned long long m = __ballot(keep);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) wsum[wave] = __popcll(m);
-    __syncthreads();
-    int base = block_offsets[blockIdx.x];
-    for (int w = 0; w < wave; ++w) base += wsum[w];
+    const int rank = vn_block_rank(keep);
     if (keep) {
-        const int dst = base + __popcll(m & ((1ull << lane) - 1ull));
+        const int dst = block_offsets[blockIdx.x] + rank;
         out[dst] = pts[i];
         if (index) index[dst] = (int32_t)i;
     }
@@ -129,7 +101,7 @@ extern "C" int vn_fov_crop(const float *points, int64_t n, const float *P_3x4, c
     const int nb = (int)vn_ceil_div(n, 256);
     k_fov_flags<<<nb, 256, 0, st>>>(reinterpret_cast<const float4 *>(points), n, c, image_rows, image_cols, flags, counts);
     VN_LAUNCH_STATUS();
-    k_fov_scan<<<1, 1024, 0, st>>>(counts, nb, out_count);
+    k_fov_scan<<<1, 256, 0, st>>>(counts, nb, out_count);
     VN_LAUNCH_STATUS();
     k_fov_compact<<<nb, 256, 0, st>>>(reinterpret_cast<const float4 *>(points), n, flags, counts,
                                       reinterpret_cast<float4 *>(out_points), out_index, out_count);

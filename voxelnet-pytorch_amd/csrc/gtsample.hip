@@ -15,7 +15,7 @@
 // wave-uniform addresses (an LDS broadcast).
 // vn_gt_paste is three launches, the shape of fov.hip: flags + per-workgroup counts (wave ballot + popcount), a
 // one-workgroup exclusive scan of the counts, the order-preserving compaction together with the append and the NaN
-// fill.  No workgroup ever waits on another one.
+// fill; the count, scan and rank helpers are the shared ones of common.h.  No workgroup ever waits on another one.
 #include "common.h"
 
 namespace {
@@ -73,7 +73,6 @@ __global__ void __launch_bounds__(256) k_gt_index(const float4 *__restrict__ pts
 __global__ void __launch_bounds__(256) k_gt_flags(const float4 *__restrict__ pts, int64_t n, const vnGtBox *__restrict__ boxes,
                                                   int n_boxes, uint8_t *__restrict__ flags, int32_t *__restrict__ block_counts) {
     __shared__ __attribute__((aligned(16))) vnGtBox tab[VN_GT_MAX_BOXES];
-    __shared__ int wsum[4];
     stage_table(tab, boxes, n_boxes);
     __syncthreads();
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -88,40 +87,18 @@ __global__ void __launch_bounds__(256) k_gt_flags(const float4 *__restrict__ pts
         }
         flags[i] = keep ? 1 : 0;
     }
-    const unsigned long long m = __ballot(keep);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = __popcll(m);
-    __syncthreads();
-    if (threadIdx.x == 0) block_counts[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    const int kept = vn_block_count(keep);
+    if (threadIdx.x == 0) block_counts[blockIdx.x] = kept;
 }
 
 // launch two: exclusive scan of the block counts in place (one workgroup; nb may be 0), the number of kept rows -> *kept,
 // kept + m -> *count
-__global__ void __launch_bounds__(1024) k_gt_scan(int32_t *__restrict__ block_counts, int nb, int32_t m, int32_t *__restrict__ kept,
-                                                  int32_t *__restrict__ count) {
-    __shared__ int part[1024];
-    const int per = (nb + 1023) / 1024;
-    const int64_t b0 = (int64_t)threadIdx.x * per;
-    int s = 0;
-    for (int j = 0; j < per; ++j)
-        if (b0 + j < nb) s += block_counts[b0 + j];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-        const int v = (int)threadIdx.x >= o ? part[threadIdx.x - o] : 0;
-        __syncthreads();
-        part[threadIdx.x] += v;
-        __syncthreads();
-    }
-    int run = part[threadIdx.x] - s;
-    for (int j = 0; j < per; ++j)
-        if (b0 + j < nb) {
-            const int v = block_counts[b0 + j];
-            block_counts[b0 + j] = run;
-            run += v;
-        }
-    if (threadIdx.x == 1023) {
-        *kept = part[1023];
-        *count = part[1023] + m;
+__global__ void __launch_bounds__(256) k_gt_scan(int32_t *__restrict__ block_counts, int nb, int32_t m, int32_t *__restrict__ kept,
+                                                 int32_t *__restrict__ count) {
+    const int32_t total = vn_scan_block_sums<int32_t, 256>(block_counts, nb);
+    if (threadIdx.x == 0) {
+        *kept = total;
+        *count = total + m;
     }
 }
 
@@ -132,18 +109,10 @@ __global__ void __launch_bounds__(256) k_gt_compact(const float4 *__restrict__ p
                                                     const int32_t *__restrict__ block_offsets, const float4 *__restrict__ obj,
                                                     int64_t m, float4 *__restrict__ out, int64_t cap,
                                                     const int32_t *__restrict__ kept) {
-    __shared__ int wsum[4];
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const bool keep = i < n && flags[i];
-    const unsigned long long mask = __ballot(keep);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) wsum[wave] = __popcll(mask);
-    __syncthreads();
-    if (keep) {
-        int base = block_offsets[blockIdx.x];
-        for (int w = 0; w < wave; ++w) base += wsum[w];
-        out[base + __popcll(mask & ((1ull << lane) - 1ull))] = pts[i];
-    }
+    const int rank = vn_block_rank(keep);
+    if (keep) out[block_offsets[blockIdx.x] + rank] = pts[i];
     const int64_t k = (int64_t)kept[0];
     if (i < cap && i >= k) {
         const float q = __builtin_nanf("");
@@ -207,7 +176,7 @@ extern "C" int vn_gt_paste(const float *points, int64_t n, const vnGtBox *boxes,
         k_gt_flags<<<nb, 256, 0, st>>>(src, n, boxes, n_boxes, flags, counts);
         VN_LAUNCH_STATUS();
     }
-    k_gt_scan<<<1, 1024, 0, st>>>(counts, nb, (int32_t)m, kept, out_count);
+    k_gt_scan<<<1, 256, 0, st>>>(counts, nb, (int32_t)m, kept, out_count);
     VN_LAUNCH_STATUS();
     if (cap > 0) {
         k_gt_compact<<<(int)vn_ceil_div(cap, 256), 256, 0, st>>>(src, n, flags, counts, reinterpret_cast<const float4 *>(obj_points),

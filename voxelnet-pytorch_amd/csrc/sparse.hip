@@ -37,29 +37,6 @@ __global__ void __launch_bounds__(256) k_mark(const int64_t *__restrict__ coord,
     flags[(((int64_t)b * g.Do + od) * g.Ho + oh) * g.Wo + ow] = 1;
 }
 
-__device__ int block_excl_scan_i32(int v, int *total) {
-    __shared__ int wsum[AS_THREADS / 64];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += t;
-    }
-    if (lane == 63) wsum[wid] = inc;
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < AS_THREADS / 64; ++w) {
-        const int s = wsum[w];
-        if (w < wid) base += s;
-        tot += s;
-    }
-    __syncthreads();
-    *total = tot;
-    return base + inc - v;
-}
-
 __global__ void __launch_bounds__(AS_THREADS) k_as_count(const uint8_t *__restrict__ flags, int64_t n,
                                                          int32_t *__restrict__ blk) {
     VN_PRIO_MAIN();
@@ -69,22 +46,14 @@ __global__ void __launch_bounds__(AS_THREADS) k_as_count(const uint8_t *__restri
     for (int j = 0; j < AS_ITEMS; ++j)
         if (base + j < n) s += flags[base + j] ? 1 : 0;
     int tot;
-    block_excl_scan_i32(s, &tot);
+    vn_block_excl_scan<int, AS_THREADS>(s, &tot);
     if (threadIdx.x == 0) blk[blockIdx.x] = tot;
 }
 
 __global__ void __launch_bounds__(AS_THREADS) k_as_scan(int32_t *__restrict__ blk, int64_t nb, int64_t cap,
                                                         int32_t *__restrict__ count) {
     VN_PRIO_MAIN();
-    int carry = 0;
-    for (int64_t base = 0; base < nb; base += AS_THREADS) {
-        const int64_t i = base + threadIdx.x;
-        const int v = i < nb ? blk[i] : 0;
-        int tot;
-        const int ex = block_excl_scan_i32(v, &tot);
-        if (i < nb) blk[i] = carry + ex;
-        carry += tot;
-    }
+    const int carry = vn_scan_block_sums<int32_t, AS_THREADS>(blk, nb);
     if (threadIdx.x == 0) count[0] = carry < cap ? carry : (int32_t)cap;
 }
 
@@ -101,7 +70,7 @@ __global__ void __launch_bounds__(AS_THREADS) k_as_write(const uint8_t *__restri
         s += f[j] ? 1 : 0;
     }
     int tot;
-    int pos = block_excl_scan_i32(s, &tot) + blk[blockIdx.x];
+    int pos = vn_block_excl_scan<int, AS_THREADS>(s, &tot) + blk[blockIdx.x];
 #pragma unroll
     for (int j = 0; j < AS_ITEMS; ++j) {
         if (!f[j]) continue;

@@ -79,31 +79,6 @@ __device__ __forceinline__ unsigned long long pack(int32_t c) {
     return c > 0 ? ((1ull << 32) | (unsigned long long)(uint32_t)c) : 0ull;
 }
 
-// block-wide exclusive scan of one u64 per thread (256 threads); returns the
-// exclusive prefix, *total = block sum
-__device__ unsigned long long block_excl_scan(unsigned long long v, unsigned long long *total) {
-    __shared__ unsigned long long wsum[SCAN_THREADS / VN_WAVE];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    unsigned long long inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        unsigned long long t = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += t;
-    }
-    if (lane == 63) wsum[wid] = inc;
-    __syncthreads();
-    unsigned long long base = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < SCAN_THREADS / VN_WAVE; ++w) {
-        unsigned long long s = wsum[w];
-        if (w < wid) base += s;
-        tot += s;
-    }
-    __syncthreads();
-    *total = tot;
-    return base + inc - v;
-}
-
 __global__ void __launch_bounds__(SCAN_THREADS) k_scan_reduce(const int32_t *__restrict__ cell, int64_t cells,
                                                               unsigned long long *__restrict__ blk) {
     int64_t base = (int64_t)blockIdx.x * SCAN_TILE + (int64_t)threadIdx.x * SCAN_ITEMS;
@@ -112,7 +87,7 @@ __global__ void __launch_bounds__(SCAN_THREADS) k_scan_reduce(const int32_t *__r
     for (int j = 0; j < SCAN_ITEMS; ++j)
         if (base + j < cells) s += pack(cell[base + j]);
     unsigned long long tot;
-    block_excl_scan(s, &tot);
+    vn_block_excl_scan<unsigned long long, SCAN_THREADS>(s, &tot);
     if (threadIdx.x == 0) blk[blockIdx.x] = tot;
 }
 
@@ -120,15 +95,7 @@ __global__ void __launch_bounds__(SCAN_THREADS) k_scan_reduce(const int32_t *__r
 // publishes K and the number of in-range points.
 __global__ void __launch_bounds__(SCAN_THREADS) k_scan_blocks(unsigned long long *__restrict__ blk, int64_t nb,
                                                               int32_t *__restrict__ k_out) {
-    unsigned long long carry = 0;
-    for (int64_t base = 0; base < nb; base += SCAN_THREADS) {
-        int64_t i = base + threadIdx.x;
-        unsigned long long v = i < nb ? blk[i] : 0ull;
-        unsigned long long tot;
-        unsigned long long ex = block_excl_scan(v, &tot);
-        if (i < nb) blk[i] = carry + ex;
-        carry += tot;
-    }
+    const unsigned long long carry = vn_scan_block_sums<unsigned long long, SCAN_THREADS>(blk, nb);
     if (threadIdx.x == 0) {
         blk[nb] = carry;
         k_out[0] = (int32_t)(carry >> 32);
@@ -149,7 +116,7 @@ __global__ void __launch_bounds__(SCAN_THREADS) k_scan_write(int32_t *__restrict
         s += pack(c[j]);
     }
     unsigned long long tot;
-    unsigned long long ex = block_excl_scan(s, &tot) + blk[blockIdx.x];
+    unsigned long long ex = vn_block_excl_scan<unsigned long long, SCAN_THREADS>(s, &tot) + blk[blockIdx.x];
 #pragma unroll
     for (int j = 0; j < SCAN_ITEMS; ++j) {
         if (base + j < cells) {
