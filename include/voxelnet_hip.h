@@ -402,6 +402,35 @@ typedef struct vnAugmentBox {
 int vn_augment_points(const float *points, int64_t n, int32_t mode, const vnAugmentBox *boxes, int32_t n_boxes, double c,
                       double s, float scale, float *out, vnStream stream);
 
+/* The composed recipe (SECOND / PointPillars: per-object noise, flip, global rotation, scaling, translation) in ONE
+ * launch — vn_augment_compose, beside the three modes above (csrc/augment.hip; the draw is voxelnet_amd/augment.py's
+ * draw_compose).  points / out as above (out may BE points); moves = DEVICE table of 0 <= n_moves <=
+ * VN_AUGMENT_MAX_BOXES entries, 16-byte aligned; affine = HOST pointer, read at call time.  Per point, widened exactly to
+ * float64, evaluated as written without contraction, rounded once to fp32; every cos / sin is the host's:
+ *   membership  the test of vn_points_in_boxes on the ORIGINAL point and the UNMOVED box:
+ *                 dx = px - x; dy = py - y; u = dx*c + dy*s; v = -(dx*s) + dy*c
+ *                 inside <=> |u| <= hl and |v| <= hw and z0 <= pz <= z1                      (inclusive)
+ *               the lowest entry that holds the point wins; a point takes AT MOST ONE object move
+ *   object move X = (x + tx) + (dx*rc - dy*rs);  Y = (y + ty) + (dx*rs + dy*rc);  Z = pz + tz
+ *               (the point turns about ITS box's centre, then travels with it); in no box: X, Y, Z = px, py, pz
+ *   affine      x' = (a00*X + a01*Y) + bx;  y' = (a10*X + a11*Y) + by;  z' = sz*Z + bz      for every point
+ * Reflectance is copied.  A NaN coordinate fails the membership test and stays NaN through the affine.
+ * VN_EINVAL: n outside [0, 2^31), n_moves outside [0, VN_AUGMENT_MAX_BOXES], affine NULL, moves NULL with n_moves > 0,
+ * points or out NULL with n > 0; VN_EUNSUPPORTED: a misaligned pointer.  n == 0 is a no-op.  Asynchronous; no workspace. */
+typedef struct vnObjectMove {
+    double x, y, z0, z1, hl, hw, c, s;   /* the UNMOVED box: vnGtBox's fields (below) and its inside test */
+    double tx, ty, tz;                   /* translation of the object */
+    double rc, rs;                       /* cos / sin of the object's turn about ITS centre */
+    double pad[3];
+} vnObjectMove;                          /* 128 bytes */
+typedef struct vnAffine {
+    double a00, a01, a10, a11;           /* the x / y part */
+    double sz;                           /* z scale */
+    double bx, by, bz;                   /* translation, applied last */
+} vnAffine;                              /* 64 bytes */
+int vn_augment_compose(const float *points, int64_t n, const vnObjectMove *moves, int32_t n_moves, const vnAffine *affine,
+                       float *out, vnStream stream);
+
 /* ------------------------------------------------------------------------
  * Ground-truth database sampling ("GT-paste") — the per-point half (csrc/gtsample.hip): cut labelled objects with their
  * points out of the training frames, paste a few into every training frame where they collide with nothing.  The

@@ -3,7 +3,10 @@
      time per launch in a back-to-back train of launches (device events), against the HBM floor of 32 B per point;
   2. the input pipeline's stage per batch (DeviceCollate.launch + concat + finish, batch of 2 car frames from memory)
      with augment=False and augment=True, interleaved: the host's time per batch and the pipeline stream's busy time
-     per batch (events on the pipeline stream around the batch's work).
+     per batch (events on the pipeline stream around the batch's work);
+  3. the composed recipe: `vn_augment_compose` (one launch) against the three existing launches run back to back
+     (boxes -> rotate -> scale) on both clouds with 7 and 128 table entries, median [min, max] of alternated rounds,
+     and the pipeline stage per batch with augment=True against augment=ComposeRecipe().
 usage: python tools/bench_augment.py [--out FILE]"""
 import os
 import sys
@@ -131,6 +134,95 @@ for mode in ("boxes", "rotate", "scale"):
         if p.mode == mode:
             ts.append(time.perf_counter() - t0)
     say(f"host draw + labels, one sample, {mode:6s}: {np.mean(ts) * 1e3:6.3f} ms")
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the composed recipe (vn_augment_compose): one launch against the three existing ones run back to back
+# ---------------------------------------------------------------------------------------------------------------------
+import ctypes  # noqa: E402
+
+from voxelnet_amd import _lib  # noqa: E402
+from voxelnet_amd import gtsample as G  # noqa: E402
+
+
+def fmt(v):
+    return f"{np.median(v):7.2f} [{min(v):7.2f}, {max(v):7.2f}]"
+
+
+say("== composed launch vs boxes -> rotate -> scale back to back: us per cloud, median [min, max] of 9 alternated rounds of 200 ==")
+rng = np.random.default_rng(0)
+for name, cloud in (("car 20k", synth.workload_frames(2, batch=1)[0]), ("dense 300k", synth.workload_frames(5, batch=1)[0])):
+    pts = torch.from_numpy(cloud).to(dev)
+    n = pts.shape[0]
+    dst = torch.empty_like(pts)
+    for g in (7, 128):
+        boxes = np.stack([rng.uniform(2, 68, g), rng.uniform(-38, 38, g), rng.uniform(-2.0, -1.4, g), np.full(g, 1.56), np.full(g, 1.6),
+                          np.full(g, 3.9), rng.uniform(-1.5, 1.5, g)], 1)
+        old = np.zeros(g, dtype=A.BOX_DTYPE)
+        new = np.zeros(g, dtype=A.MOVE_DTYPE)
+        unmoved = G.box_table(boxes)
+        for i, b in enumerate(boxes):
+            rz, t = rng.uniform(-0.3, 0.3), rng.normal(size=3)
+            lo, hi = A.box_bounds(b)
+            old[i] = (lo, hi, tuple(t), np.cos(rz), np.sin(rz))
+            for f in unmoved.dtype.names:
+                new[i][f] = unmoved[i][f]
+            new[i]["tx"], new[i]["ty"], new[i]["tz"], new[i]["rc"], new[i]["rs"] = t[0], t[1], t[2], np.cos(rz), np.sin(rz)
+        old_d = torch.from_numpy(old.view(np.uint8)).to(dev)
+        new_d = torch.from_numpy(new.view(np.uint8)).to(dev)
+        aff = _lib.VnAffine(*A.compose_affine(True, 0.4, 1.03, (0.1, 0.2, 0.05)))
+        c, s = float(np.cos(0.4)), float(np.sin(0.4))
+
+        def three():
+            st = _lib.raw_stream()
+            _lib.call("vn_augment_points", pts.data_ptr(), n, 0, old_d.data_ptr(), g, 1.0, 0.0, 1.0, dst.data_ptr(), st)
+            _lib.call("vn_augment_points", dst.data_ptr(), n, 1, None, 0, c, s, 1.0, dst.data_ptr(), st)
+            _lib.call("vn_augment_points", dst.data_ptr(), n, 2, None, 0, 1.0, 0.0, 1.03, dst.data_ptr(), st)
+
+        def one():
+            _lib.call("vn_augment_compose", pts.data_ptr(), n, new_d.data_ptr(), g, ctypes.byref(aff), dst.data_ptr(), _lib.raw_stream())
+
+        t3, t1 = [], []
+        for rnd in range(9):
+            t3.append(train_of_launches(three, 200))
+            t1.append(train_of_launches(one, 200))
+        say(f"{name:10s} n = {n:6d}  {g:3d} entries: three launches {fmt(t3)} us   composed {fmt(t1)} us"
+            f"   (HBM floor of one pass {32.0 * n / HBM * 1e6:5.2f} us)")
+
+say("== pipeline stage per batch (2 car frames, 6 cars + DontCare each): augment=True vs augment=ComposeRecipe(), interleaved ==")
+collates["compose"] = D.DeviceCollate(dev, "Car", augment=A.ComposeRecipe())
+host2 = {True: [], "compose": []}
+busy2 = {True: [], "compose": []}
+np.random.seed(0)
+for rnd in range(12):
+    for flag in (True, "compose"):
+        c = collates[flag]
+        for _ in range(3):
+            one_batch(c)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(40):
+            one_batch(c)
+        torch.cuda.synchronize()
+        host2[flag].append((time.perf_counter() - t0) / 40 * 1e3)
+        alone = []
+        for _ in range(10):
+            torch.cuda.synchronize()
+            s, e, _ = one_batch(c)
+            torch.cuda.synchronize()
+            alone.append(s.elapsed_time(e))
+        busy2[flag].append(float(np.median(alone)))
+for flag in (True, "compose"):
+    say(f"augment={str(flag):8s}: wall per batch, back to back, ms {fmt(host2[flag])};  one batch alone on the pipeline stream, ms {fmt(busy2[flag])}"
+        "   (median [min, max] of 12 rounds)")
+lab = frames[0][1]
+np.random.seed(1)
+ts = []
+for _ in range(200):
+    t0 = time.perf_counter()
+    p = A.draw_compose(lab, A.ComposeRecipe())
+    A.compose_labels(lab, p)
+    ts.append(time.perf_counter() - t0)
+say(f"host draw_compose + compose_labels, one sample (6 cars + DontCare): {np.median(ts) * 1e3:6.3f} ms")
 if "--out" in sys.argv:
     path = sys.argv[sys.argv.index("--out") + 1]
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)

@@ -158,6 +158,16 @@ __device__ __forceinline__ int vn_block_count(bool keep) {
     return total;
 }
 
+// The point-in-rotated-box test of gtsample.hip and of augment.hip's composed pass, one copy: Box = vnGtBox or a struct
+// that begins with its eight fields (vnObjectMove).  float64 exactly as written, inclusive; a NaN anywhere fails.
+template <typename Box>
+__device__ __forceinline__ bool vn_gt_inside(double px, double py, double pz, const Box &q) {
+    const double dx = px - q.x, dy = py - q.y;
+    const double u = dx * q.c + dy * q.s;
+    const double v = -(dx * q.s) + dy * q.c;
+    return fabs(u) <= q.hl && fabs(v) <= q.hw && pz >= q.z0 && pz <= q.z1;
+}
+
 // Buffer descriptor from values the compiler can PROVE wave-uniform (cdna_hip_programming.md T20): without
 // the readfirstlane of the pointer halves and the size, hipcc wraps every buffer_load ... lds that uses the
 // descriptor in a waterfall loop (v_readfirstlane x4 + s_and_saveexec + loop), ~15 instructions and a

@@ -12,7 +12,7 @@
 // anywhere fails a comparison, so a NaN point is in no box and a box with a NaN field or hl < 0 holds nothing.  c and s
 // come from the host.  There is no float32 prefilter: every decision is the float64 one.
 // One thread per point, 16-byte loads and stores, the table (<= 8 KB) staged once per workgroup in LDS and read at
-// wave-uniform addresses (an LDS broadcast).
+// wave-uniform addresses (an LDS broadcast).  The test itself is vn_gt_inside of common.h, shared with augment.hip.
 // vn_gt_paste is three launches, the shape of fov.hip: flags + per-workgroup counts (wave ballot + popcount), a
 // one-workgroup exclusive scan of the counts, the order-preserving compaction together with the append and the NaN
 // fill; the count, scan and rank helpers are the shared ones of common.h.  No workgroup ever waits on another one.
@@ -26,13 +26,6 @@ __device__ __forceinline__ void stage_table(vnGtBox *tab, const vnGtBox *__restr
     const uint4 *src = reinterpret_cast<const uint4 *>(boxes);
     uint4 *dst = reinterpret_cast<uint4 *>(tab);
     for (int w = threadIdx.x; w < n_boxes * 4; w += 256) dst[w] = src[w];
-}
-
-__device__ __forceinline__ bool gt_inside(double px, double py, double pz, const vnGtBox &q) {
-    const double dx = px - q.x, dy = py - q.y;
-    const double u = dx * q.c + dy * q.s;
-    const double v = -(dx * q.s) + dy * q.c;
-    return fabs(u) <= q.hl && fabs(v) <= q.hw && pz >= q.z0 && pz <= q.z1;
 }
 
 // COUNTS: every thread walks the whole table (a point inside two boxes counts for both) and the per-box counts are
@@ -53,14 +46,14 @@ __global__ void __launch_bounds__(256) k_gt_index(const float4 *__restrict__ pts
     int first = -1;
     if (COUNTS) {
         for (int b = 0; b < n_boxes; ++b) {                             // uniform trip count: the ballot sees all 64 lanes
-            const bool in = gt_inside(px, py, pz, tab[b]);
+            const bool in = vn_gt_inside(px, py, pz, tab[b]);
             if (in && first < 0) first = b;
             const unsigned long long m = __ballot(in);
             if ((threadIdx.x & 63) == 0 && m) atomicAdd(&cnt[b], __popcll(m));
         }
     } else {
         for (int b = 0; b < n_boxes; ++b)
-            if (gt_inside(px, py, pz, tab[b])) { first = b; break; }
+            if (vn_gt_inside(px, py, pz, tab[b])) { first = b; break; }
     }
     if (live) out_index[i] = first;
     if (COUNTS) {
@@ -83,7 +76,7 @@ __global__ void __launch_bounds__(256) k_gt_flags(const float4 *__restrict__ pts
         if (keep) {
             const double px = (double)p.x, py = (double)p.y, pz = (double)p.z;
             for (int b = 0; b < n_boxes; ++b)
-                if (gt_inside(px, py, pz, tab[b])) { keep = false; break; }      // the first hit ends the walk
+                if (vn_gt_inside(px, py, pz, tab[b])) { keep = false; break; }      // the first hit ends the walk
         }
         flags[i] = keep ? 1 : 0;
     }

@@ -141,6 +141,15 @@ VN_AUGMENT_BOXES, VN_AUGMENT_ROTATE, VN_AUGMENT_SCALE = 0, 1, 2       # vn_augme
 VN_AUGMENT_MAX_BOXES = 128
 
 
+class VnObjectMove(ctypes.Structure):   # vnObjectMove (vn_augment_compose): one entry of the device move table, 128 bytes
+    _fields_ = [(n, ctypes.c_double) for n in ("x", "y", "z0", "z1", "hl", "hw", "c", "s", "tx", "ty", "tz", "rc", "rs")] + \
+               [("pad", ctypes.c_double * 3)]
+
+
+class VnAffine(ctypes.Structure):   # vnAffine (vn_augment_compose): the global stages composed on the host, 64 bytes
+    _fields_ = [(n, ctypes.c_double) for n in ("a00", "a01", "a10", "a11", "sz", "bx", "by", "bz")]
+
+
 class VnGtBox(ctypes.Structure):   # vnGtBox (vn_points_in_boxes, vn_gt_paste): one entry of the device box table, 64 bytes
     _fields_ = [(n, ctypes.c_double) for n in ("x", "y", "z0", "z1", "hl", "hw", "c", "s")]
 
@@ -173,6 +182,7 @@ SIGNATURES = {
     "vn_fov_crop_workspace_bytes": (c_sz, [c_i64]),
     "vn_fov_crop": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "vn_augment_points": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i32, ctypes.c_double, ctypes.c_double, c_f32, c_vp, c_vp]),
+    "vn_augment_compose": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_vp, c_vp, c_vp]),
     "vn_points_in_boxes": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_vp, c_vp, c_vp]),
     "vn_gt_paste_workspace_bytes": (c_sz, [c_i64]),
     "vn_gt_paste": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_sz, c_vp]),

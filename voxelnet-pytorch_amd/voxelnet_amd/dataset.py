@@ -15,6 +15,8 @@ stage of this pipeline, not of the dataset: copy -> [field-of-view crop] -> augm
 augment=True)` / `DeviceBatcher(..., augment=True)` draw the parameters per sample on the host (augment.py, after the
 sample's shuffle), move the points on the device (csrc/augment.hip) and hand the model the moved label lines.  The
 dataset itself runs in DataLoader workers, which must not touch the GPU: `KITTIDataset(augment=True)` still raises.
+`augment=augment.ComposeRecipe(...)` selects the composed recipe instead (per-object noise, flip, global rotation, scaling,
+translation for every sample; one launch, `vn_augment_compose`), drawn and launched at the same two places.
 
 Ground-truth database sampling (gtsample.py; SECOND's "GT-paste", no counterpart in the reference) is the stage in front
 of the augmentation: copy -> [field-of-view crop] -> paste -> augment -> voxelize.  `DeviceCollate(..., gt_sampler=s)` /
@@ -97,6 +99,9 @@ class DeviceCollate:
         augment: the reference's pcl_augmentation (dataset.py:122-219) per sample — drawn from np.random after the
         sample's shuffle, applied to the (cropped) cloud on the device in front of the voxelizer; the batch's `label`
         element then holds the MOVED label lines (augment.augment_labels), its raw-lidar element the host cloud as shuffled.
+        An `augment.ComposeRecipe` instance instead of True: the composed recipe (object noise, flip, rotation, scaling,
+        translation for EVERY sample — augment.draw_compose / compose_labels / vn_augment_compose), drawn and launched at
+        the same two places.  True and False are exactly what they were; anything else raises ValueError.
         fov_calib_dir: RAW sweeps — crop every cloud to the camera field of view on the device before it is voxelized
         (the reference does this offline, preprocess_data.py:42-154, and trains on the rewritten .bin files):
         `<fov_calib_dir>/<tag>.txt` is the sample's KITTI object calibration file, the image size is the sample's image's
@@ -120,18 +125,25 @@ class DeviceCollate:
         self.grid = grid_config("Car" if target == "Car" else "Pedestrian")    # utils.py:24-33 ('Car' else ped/cyc)
         self.shuffle_points = shuffle_points
         self.fov_calib_dir, self.image_shape = fov_calib_dir, tuple(image_shape)
-        self.augment = bool(augment)
+        self.recipe = None
+        if isinstance(augment, (bool, np.bool_)):
+            self.augment = bool(augment)
+        else:
+            from .augment import ComposeRecipe
+            if not isinstance(augment, ComposeRecipe):
+                raise ValueError(f"augment={augment!r}: expected True, False or an augment.ComposeRecipe")
+            self.augment, self.recipe = False, augment
         self.gt_sampler = gt_sampler
         self.stream = pipeline_stream(self.device)      # (shared with the target generator: see voxelize.pipeline_stream)
 
     def launch(self, parts):
         """enqueue the copies and the voxelization of one batch on the pipeline's stream; returns a handle"""
         handles = []
-        if self.augment:
+        if self.augment or self.recipe is not None:
             from . import augment as A
         if self.gt_sampler is not None:
             from . import gtsample as G
-        if self.augment or self.gt_sampler is not None:
+        if self.augment or self.recipe is not None or self.gt_sampler is not None:
             parts = list(parts)
         mode = self._shuffle_mode
         if mode in ("index", "device"):
@@ -155,6 +167,9 @@ class DeviceCollate:
                 if self.augment:
                     params = A.draw_augmentation(p[3])                         # dataset.py:122-219, host: O(boxes)
                     parts[b] = (p[0], p[1], p[2], A.augment_labels(p[3], params), *p[4:])
+                elif self.recipe is not None:
+                    params = A.draw_compose(p[3], self.recipe)                 # the composed recipe, host: O(boxes^2)
+                    parts[b] = (p[0], p[1], p[2], A.compose_labels(p[3], params), *p[4:])
                 host = torch.from_numpy(np.ascontiguousarray(pcl[:, :4], dtype=np.float32)).pin_memory()
                 pts = host.to(self.device, non_blocking=True)
                 if mode == "index":
@@ -181,6 +196,9 @@ class DeviceCollate:
                     # in place, behind the copy / the crop on this stream; `keep` = the staged box table, referenced
                     # by the handle until the batch is consumed, like `host`
                     pts, keep = A.enqueue_augment_points(pts, params, out=pts)
+                    host = (host, keep)
+                elif self.recipe is not None:
+                    pts, keep = A.enqueue_compose_points(pts, params, out=pts)          # the same place, one launch
                     host = (host, keep)
                 handles.append((voxelize_device_async(pts, self.grid, b, coord_cols=4), pts, host))
         return parts, handles
