@@ -942,6 +942,50 @@ int vn_rpn_loss_spec_fwd_bwd_rows(const float *prob, const float *delta, const f
                                   void *d_rows, vnDtype d_dtype, int64_t d_stride, int32_t split, vnStream stream,
                                   const vnLossSpec *spec);
 
+/* ---- rotated-IoU regression loss (csrc/iou_loss.hip) ---------------------------------------------
+ * A second regression term beside the smooth-L1 one, on the boxes the regression channels DECODE to.  For every anchor
+ * (b, y, x, a), a in {0, 1}, j = (y*W + x)*2 + a, A = anchors[j] = (x, y, z, h, w, l, r) float64 (device; the table
+ * vn_rpn_targets and vn_rpn_predict take):
+ *   decode(d, A): diag = sqrt(A.w^2 + A.l^2)
+ *                 (d0*diag + A.x, d1*diag + A.y, d2*A.h + A.z, exp(d3)*A.h, exp(d4)*A.w, exp(d5)*A.l, d6 + A.r)
+ *   P = decode(delta[b, a*7 : a*7+7, y, x], A)      delta   (B,14,H,W) fp32, the module's output
+ *   G = decode(targets[b, y, x, a*7 : a*7+7], A)    targets (B,H,W,14) fp32;  m = pos[b, y, x, a], pos (B,H,W,2) fp32
+ *   IoU = the iou_bev (metric VN_IOU_BEV) or iou_3d (VN_IOU_3D) of "detection scoring" below: vn_box_iou_rotated(P, G)
+ *   kind VN_IOU_LOSS_IOU:   L = 1 - IoU
+ *   kind VN_IOU_LOSS_DIOU:  L = 1 - IoU + rho2 / c2
+ *        bev: rho2 = (Gx-Px)^2 + (Gy-Py)^2;  c2 = ex^2 + ey^2, ex / ey the extents of the axis-aligned rectangle (lidar
+ *             axes) around the 8 footprint corners of P and G
+ *        3d:  rho2 += ((Gz + Gh/2) - (Pz + Ph/2))^2;  c2 += ez^2, ez = max(Pz+Ph, Gz+Gh) - min(Pz, Gz)
+ *   out2[0] = loss = sum_b (1/P_b) * sum over sample b of m * L,  P_b = max(1, sum pos[b])
+ *   out2[1] = mean_iou = (sum m * IoU) / max(1, sum m) over the whole batch (a diagnostic)
+ *   d_delta (B,14,H,W) fp32, or NULL for the forward alone = d loss / d delta, times *g when g (a device scalar) is not
+ *   NULL.  The derivative runs through the decode (dPx/dd0 = diag, dPh/dd3 = Ph, ...); G is a constant.  EVERY element is
+ *   written — zeros where m == 0 — so the buffer need not be cleared.
+ * Every float32 input is widened exactly to float64 and all arithmetic is float64 without contraction; only d_delta and
+ * out2 are rounded to fp32.  Edge rules:
+ *   - a pair scores IoU 0, L = 1 and gradient 0 in BOTH kinds (the distance term is skipped as well) when a decoded
+ *     field of P or G is not finite, a size (h, w, l) is not > 0, or a denominator — the sum of the two areas (bev) or
+ *     volumes (3d), which bounds area + area - I from above — is <= 0 or not finite;
+ *   - the distance term alone is skipped (0, gradient 0) when rho2 or c2 is not finite or c2 <= 0;
+ *   - nothing is ever NaN for a finite g and finite pos;
+ *   - disjoint boxes (IoU == 0; in 3d also overlapping footprints without z overlap) of kind IOU have gradient exactly 0;
+ *   - IoU is piecewise smooth; where it is not (coincident edges, P == G, touching boxes, a tie between two corners for
+ *     a side of the enclosing rectangle) d_delta is one of the one-sided derivatives, and finite;
+ *   - no work is done where m == 0; the sums take m as a weight, as the smooth-L1 term takes pos.
+ * Three launches (normaliser partial sums, the pass over the sites, a one-workgroup finish), sums added in one fixed
+ * order: bit-identical from run to run and between the forward-only and the full call.  Asynchronous.
+ * VN_EINVAL (before anything is launched or any pointer is read): B, H or W <= 0 or B*H*W >= 2^31, an unknown kind or
+ * metric, a NULL delta / pos / targets / anchors / workspace / out2; VN_EWORKSPACE: workspace_bytes below
+ * vn_rpn_iou_loss_workspace_bytes(B, H, W) (0 for sizes the call refuses).  Not part of vn_net_step. */
+#define VN_IOU_LOSS_IOU 0
+#define VN_IOU_LOSS_DIOU 1      /* kind */
+#define VN_IOU_BEV 0
+#define VN_IOU_3D 1             /* metric: the values vn_box_iou_rotated uses */
+size_t vn_rpn_iou_loss_workspace_bytes(int32_t B, int32_t H, int32_t W);
+int vn_rpn_iou_loss(const float *delta, const float *pos, const float *targets, const double *anchors /*[H*W*2,7]*/,
+                    int32_t B, int32_t H, int32_t W, int32_t kind, int32_t metric, const float *g /*device scalar, NULL = 1*/,
+                    void *workspace, size_t workspace_bytes, float *out2, float *d_delta /*NULL: forward only*/, vnStream stream);
+
 /* ---- optimizer tail (voxelnet/train.py:153-154 with the optimizer of train.py:130-132) ---------------------
  * torch.nn.utils.clip_grad_norm_(parameters, max_norm) followed by an update rule, in two launches.  The clip is the
  * same code under both rules (vn_clip_sgd here, vn_clip_adamw below):

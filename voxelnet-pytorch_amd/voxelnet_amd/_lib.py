@@ -112,6 +112,8 @@ class VnAdamChunkEma(ctypes.Structure):   # vnAdamChunkEma (vn_clip_adamw_ema), 
 
 
 VN_LOSS_BCE, VN_LOSS_FOCAL = 0, 1       # vnLossSpec.cls_kind
+VN_IOU_LOSS_IOU, VN_IOU_LOSS_DIOU = 0, 1       # vn_rpn_iou_loss' `kind`
+VN_IOU_BEV, VN_IOU_3D = 0, 1                   # vn_rpn_iou_loss' `metric` (vn_box_iou_rotated's values)
 
 
 class VnLossSpec(ctypes.Structure):   # vnLossSpec (vn_rpn_loss_spec_*, vnStep.loss_spec): all zero = the reference's objective
@@ -299,6 +301,8 @@ SIGNATURES = {
                                          c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, _P(VnLossSpec)]),
     "vn_rpn_loss_spec_fwd_bwd_rows": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_f32, c_f32, c_f32, c_vp, c_sz,
                                               c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_vp, _P(VnLossSpec)]),
+    "vn_rpn_iou_loss_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32]),
+    "vn_rpn_iou_loss": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_sz, c_vp, c_vp, c_vp]),
     "vn_rpn_targets_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32]),
     "vn_rpn_targets": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, c_f32, ctypes.c_double, c_vp, c_vp, c_vp,
                                c_vp, c_sz, c_vp]),

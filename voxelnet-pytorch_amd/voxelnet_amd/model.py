@@ -882,6 +882,12 @@ _DetectorFn._backward_native = staticmethod(_detector_backward_native)
 _LOSS_SPECS = {}
 
 
+def _iou_check(kind, metric, weight):
+    if kind is not None:          # (the default path does not import the module)
+        from .iou_loss import check_spec
+        check_spec(kind, metric, weight)
+
+
 def loss_spec(cls_loss="bce", focal_alpha=0.25, focal_gamma=2.0, yaw_loss="diff"):
     """-> _lib.VnLossSpec (include/voxelnet_hip.h), checked here on the host: ValueError for what the library
     would answer with VN_EINVAL, before anything is launched.  ("bce", "diff") is all zero: the reference's objective.
@@ -968,13 +974,18 @@ class RPN3D(nn.Module):
     # the loss's objective.  Class-level defaults: a model pickled before these attributes existed loads
     # without them in its __dict__ and still reads the reference's objective here.
     cls_loss, focal_alpha, focal_gamma, yaw_loss = "bce", 0.25, 2.0, "diff"
+    # the rotated-IoU regression term (voxelnet_amd/iou_loss.py): None = off, nothing new is launched
+    iou_loss, iou_weight, iou_metric = None, 1.0, "3d"
+    last_iou = None          # the latest (L_iou, mean_iou) pair: detached device scalars, no synchronisation
 
     def __init__(self, cls_name="Car", alpha=ALPHA, beta=BETA, sigma=SIGMA, *, cls_loss="bce", focal_alpha=0.25, focal_gamma=2.0,
-                 yaw_loss="diff"):
+                 yaw_loss="diff", iou_loss=None, iou_weight=1.0, iou_metric="3d"):
         super().__init__()
         self.cls_name, self.alpha, self.beta, self.sigma = cls_name, alpha, beta, sigma
         loss_spec(cls_loss, focal_alpha, focal_gamma, yaw_loss)      # (ValueError here, not at the first step)
         self.cls_loss, self.focal_alpha, self.focal_gamma, self.yaw_loss = cls_loss, focal_alpha, focal_gamma, yaw_loss
+        _iou_check(iou_loss, iou_metric, iou_weight)
+        self.iou_loss, self.iou_weight, self.iou_metric = iou_loss, iou_weight, iou_metric
         self.feature_net = FeatureLearningNet(cls_name)
         self.middle_rpn = MiddleConvNet(cls_name)
         self.rpn_output_shape = self.middle_rpn.output_shape
@@ -992,7 +1003,7 @@ class RPN3D(nn.Module):
     # gradient buffer, device-side target / decode helpers).  They are rebuilt on demand and must not travel with
     # `torch.save(model)` (the reference's checkpoint format, train.py:24/27) or `copy.deepcopy(model)`.
     _RUNTIME_KEYS = ("_side", "_tgt_stream", "_ws_pool", "_flat_grads", "_targets", "_decoder", "_nbt", "_flat_param_list", "_net_ctx",
-                     "_named_param_list", "_anchor_t", "_bucket_views", "_mg_cache", "_step_sc", "_nbt_table")
+                     "_named_param_list", "_anchor_t", "_bucket_views", "_mg_cache", "_step_sc", "_nbt_table", "last_iou")
 
     def __getstate__(self):
         d = self.__dict__.copy()
@@ -1212,17 +1223,40 @@ class RPN3D(nn.Module):
         """the vnLossSpec of cls_loss / focal_alpha / focal_gamma / yaw_loss as they are now (they may be set after construction)"""
         return loss_spec(self.cls_loss, self.focal_alpha, self.focal_gamma, self.yaw_loss)
 
+    def _iou_spec(self):
+        """None, or the checked (kind, metric, weight) of iou_loss / iou_metric / iou_weight as they are now (like cls_loss
+        they may be set after construction)"""
+        if self.iou_loss is None:
+            return None
+        _iou_check(self.iou_loss, self.iou_metric, self.iou_weight)
+        return self.iou_loss, self.iou_metric, float(self.iou_weight)
+
     def loss(self, prob_out, delta_out, pos_equal_one, neg_equal_one, targets):
         """model.py:310-352 -> (loss, cls_loss, reg_loss, cls_pos_loss_rec, cls_neg_loss_rec), fused (csrc/loss.hip); with
-        cls_loss="focal" / yaw_loss="sin" the objective of DESIGN.md 1e, same five outputs."""
+        cls_loss="focal" / yaw_loss="sin" the objective of DESIGN.md 1e, same five outputs.  With iou_loss set,
+        iou_weight * L_iou (the anchors are the target generator's) is added to loss and to reg_loss and
+        the pair (L_iou, mean_iou) is kept, detached, as self.last_iou."""
         dev = prob_out.device
+        spec, iou = self._loss_spec(), self._iou_spec()
 
         def f32(a):
             if torch.is_tensor(a) and a.dtype == torch.float32 and a.device == dev and a.is_contiguous():
                 return a
             return (a if torch.is_tensor(a) else torch.from_numpy(np.asarray(a))).to(dev).float().contiguous()
-        return _LossFn.apply(prob_out, delta_out, f32(pos_equal_one), f32(neg_equal_one), f32(targets),
-                             float(self.alpha), float(self.beta), float(self.sigma), self._loss_spec())
+        pos, tgt = f32(pos_equal_one), f32(targets)
+        out = _LossFn.apply(prob_out, delta_out, pos, f32(neg_equal_one), tgt,
+                            float(self.alpha), float(self.beta), float(self.sigma), spec)
+        if iou is None:
+            return out
+        from .iou_loss import rpn_iou_loss
+        gen = self._target_generator(dev)
+        if gen.n_anchors != delta_out.shape[2] * delta_out.shape[3] * 2:
+            raise _lib.VoxelnetHipError(f"iou_loss: the target generator's anchor grid {tuple(gen.shape)} is not the "
+                                        f"regression map's {tuple(delta_out.shape[2:])}")
+        l_iou, mean_iou = rpn_iou_loss(delta_out, pos, tgt, gen._anchors_dev, iou[0], iou[1])
+        self.last_iou = (l_iou.detach(), mean_iou)
+        term = iou[2] * l_iou
+        return (out[0] + term, out[1], out[2] + term) + tuple(out[3:])
 
     # ---- one library call per train step (vn_net_step) ------------------------------------------------------------------
     def _step_scratch(self, dev, K, T, B, mode, hf, wf):
@@ -1256,7 +1290,7 @@ class RPN3D(nn.Module):
         from .optim import ClipAdamW, ClipSGD
         red = self.grad_reducer
         return (self._native_ok(mode) and self.training and self.direct_grads and self.overlap_wgrad and self.sparse_first_layer
-                and torch.is_grad_enabled() and self.target_fn is None and E.SECTIONS is None
+                and torch.is_grad_enabled() and self.target_fn is None and E.SECTIONS is None and self.iou_loss is None
                 and not (int(self.grad_storage) & 16)
                 and (red is None or (red.comm_stream is not None and HEADS_W in _grad_views(self)))
                 and (optimizer is None or isinstance(optimizer, (ClipSGD, ClipAdamW))))
@@ -1272,10 +1306,12 @@ class RPN3D(nn.Module):
         update and optimizer.step() follows on the same stream, after the reducer's exchange) or None (no update).  With a
         weight average attached to the optimizer (optim.attach_ema) a ClipSGD steps after the call too, same parameters.
         Whatever the fused call does not cover — per-layer orchestration, eval mode, target_fn, gradient accumulation, a
-        reducer without a communication stream, bench.py's per-section timer — takes the separate calls, same results."""
+        reducer without a communication stream, bench.py's per-section timer, the rotated-IoU term (iou_loss set: it is
+        not part of vnStep) — takes the separate calls, same results."""
         from .optim import ClipSGD
         mode = _mode()
         spec = self._loss_spec()            # (checked before anything is launched)
+        self._iou_spec()
         fused = self._step_fused_ok(mode, optimizer)
         plist = self._flat_params() if fused else None
         if fused and (not self._all_need_grad(plist) or any(p.grad is not None for p in plist)):
