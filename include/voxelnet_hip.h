@@ -1104,6 +1104,39 @@ int vn_rpn_targets(const double *anchors, int32_t n_anchors, const double *gt, c
                    double anchor_h, float *pos, float *neg, float *targets, void *workspace, size_t workspace_bytes,
                    vnStream stream);
 
+/* ---- RPN training targets by a real IoU (csrc/targets_iou.hip; rules and the reason: DESIGN.md section 1h) ----
+ * vn_rpn_targets above keeps the reference's assignment, whose anchor rectangles have zero extent and whose union
+ * term depends on where the anchor lies relative to the line y = x.  vn_rpn_targets_iou takes the same anchors, gt,
+ * gt_count, thresholds and output maps (no gt_standup: nothing is prepared on the host) and assigns by IoU(n,k) of
+ * anchor n and box k, float64 throughout, the two thresholds being the float arguments widened to double:
+ *   VN_ASSIGN_STANDUP: the axis-aligned hulls of the two rotated footprints — box (x, y, w, l, r) has the hull
+ *                      x +- hx, y +- hy, hx = (l|cos r| + w|sin r|)/2, hy = (l|sin r| + w|cos r|)/2, area 2hx * 2hy (no
+ *                      "+1"); iw, ih = the hulls' overlap along x, y, written from the centres: iw = min(hx_n + hx_k -
+ *                      |x_k - x_n|, 2 min(hx_n, hx_k)), so that anchors which all contain a box's hull along an axis (or
+ *                      lie inside it) tie exactly instead of by rounding; IoU = iw*ih / (area_n + area_k - iw*ih); 0
+ *                      when iw <= 0 or ih <= 0 (and for a non-finite result).
+ *   VN_ASSIGN_ROTATED: iou_bev of the detection scoring below for the pair (anchor, box): 0, never NaN, for a box with a
+ *                      non-finite field or h, w or l <= 0.
+ * m_n = max_k IoU(n,k), k_n = the smallest k that attains it;  M_k = max_n IoU(n,k), n_k = the smallest n that attains it.
+ *   matched[n] = k_n when m_n >= pos_iou; else the smallest k with n_k == n and M_k > 0 (a box whose best anchor stays
+ *                below pos_iou still gets that one anchor); else -1.        [B,n_anchors] int32, or NULL
+ *   pos = matched >= 0;  neg = m_n < neg_iou and not pos: the two are exclusive, unlike vn_rpn_targets'.  Every anchor of
+ *   a sample without a box is negative.
+ *   targets: k_tg_encode's seven expressions on gt[matched[n]], float64 rounded to float32; zeros for a non-positive.
+ * Limits as vn_rpn_targets (max_gt <= VN_TARGETS_MAX_GT, B * n_anchors < 2^28); gt_count is clamped to [0, max_gt] on
+ * the device.  VN_EINVAL, before anything is launched, for a size outside the limits, a null pointer (matched
+ * excepted), an unknown iou_kind, a NaN threshold or anchor_h == 0; VN_EWORKSPACE for a workspace below the query's
+ * answer (0 for unsupported sizes).  Asynchronous on `stream`, no host synchronisation; integer atomics of
+ * order-independent results only: outputs are bit-identical from run to run. */
+#define VN_ASSIGN_STANDUP 1
+#define VN_ASSIGN_ROTATED 2
+size_t vn_rpn_targets_iou_workspace_bytes(int32_t B, int32_t n_anchors, int32_t max_gt);
+int vn_rpn_targets_iou(const double *anchors, int32_t n_anchors, const double *gt /*[B,max_gt,7]*/,
+                       const int32_t *gt_count /*device [B]*/, int32_t B, int32_t max_gt, int32_t iou_kind,
+                       float pos_iou, float neg_iou, double anchor_h, float *pos, float *neg, float *targets,
+                       int32_t *matched /*[B,n_anchors] ground-truth index or -1; may be NULL*/, void *workspace,
+                       size_t workspace_bytes, vnStream stream);
+
 /* ---- inference tail (voxelnet/model.py:364-395 RPN3D.predict: utils.deltas_to_boxes_3d utils.py:476-489,
  * filter_boxes model.py:28-57, utils.nms utils.py:492-553) ----------------------------------------------
  * probs (B,2,h,w) and deltas (B,14,h,w): the module's fp32 NCHW outputs, read as the flat (B, n_anchors) and
@@ -1247,6 +1280,28 @@ int vn_rpn_detect(const float *probs, const float *deltas, const double *anchors
                   float score_thres, int32_t pre_top_k, int32_t mode, double nms_thres, int32_t post_top_k,
                   double anchor_h, float *boxes, float *scores, int32_t *counts, void *workspace, size_t workspace_bytes,
                   vnStream stream);
+
+/* The same two entry points with the layout in which the maps are read as an argument:
+ *   VN_DETECT_FLAT: the reference's reshape without a permute, as above — candidate j is scored by flat element j of
+ *                   probs[b] and decoded from flat elements 7j..7j+6 of deltas[b].  What the old entry points do; they call
+ *                   these with VN_DETECT_FLAT and stay bit-identical.
+ *   VN_DETECT_SITE: the layout the loss trains (vn_rpn_loss_*, vn_rpn_iou_loss) — anchor n = 2*s + a at site s = iy*W + ix
+ *                   with rotation a is scored by probs[b,a,s] and decoded from deltas[b,7a+k,s], k = 0..6 (S = n_anchors/2
+ *                   sites; n_anchors must be even, else VN_EINVAL).  Equal, bit for bit, to VN_DETECT_FLAT on contiguous
+ *                   channels-last copies of the two maps.
+ * Everything else is unchanged: the key (score, index n) and its tie rule, the decoding arithmetic, the NMS and the
+ * gather, the limits, and the workspace sizes (the *_workspace_bytes queries above serve both layouts).  sel_idx is
+ * the anchor index n in both layouts: the index of anchors, pos, targets and matched. */
+#define VN_DETECT_FLAT 0
+#define VN_DETECT_SITE 1
+int vn_rpn_select_decode_layout(const float *probs, const float *deltas, const double *anchors, int32_t B, int32_t n_anchors,
+                                float score_thres, int32_t pre_top_k, double anchor_h, float *sel_boxes, float *sel_scores,
+                                int32_t *sel_idx, int32_t *sel_counts, void *workspace, size_t workspace_bytes, vnStream stream,
+                                int32_t layout);
+int vn_rpn_detect_layout(const float *probs, const float *deltas, const double *anchors, int32_t B, int32_t n_anchors,
+                         float score_thres, int32_t pre_top_k, int32_t mode, double nms_thres, int32_t post_top_k,
+                         double anchor_h, float *boxes, float *scores, int32_t *counts, void *workspace, size_t workspace_bytes,
+                         vnStream stream, int32_t layout);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,166 @@
+"""Time the three target assigners and the two detection layouts, alternated inside one process.
+
+1. Assignment on the full Car grid (70,400 anchors), B = 2, with 8 and with 128 boxes per frame: us per call (every launch
+   of the call: vn_rpn_targets' three, vn_rpn_targets_iou's memset + three) for
+     reference   vn_rpn_targets (the reference's assignment; its stand-up rectangles are made on the host beforehand)
+     standup     vn_rpn_targets_iou, VN_ASSIGN_STANDUP
+     rotated     vn_rpn_targets_iou, VN_ASSIGN_ROTATED
+   and, from the same run, the encoder's forward (RPN3D.feature_net on the benchmark's two Car frames, bf16 mode) — the
+   assigner runs on the targets stream beside it, off the step's dependency chain.
+2. The evaluation tail at predict.EVAL_DECODE (pre-NMS 1024, rotated NMS at 0.1, cap 20) on random full-grid maps, B = 2:
+     flat            vn_rpn_detect
+     site            vn_rpn_detect_layout, VN_DETECT_SITE
+     flat + 2 transposes   the two channels-last copies (torch permute + contiguous), then vn_rpn_detect: what the site
+                           layout replaces
+Method of tools/bench_loss.py: per arm and round --round-launches calls back to back between two device events, the arms
+alternated round by round; reported: median [min, max] over the rounds.  No threshold is set on these numbers.
+usage: python tools/bench_assign.py [--rounds 20] [--round-launches 50] [--out FILE]"""
+import argparse
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "voxelnet-pytorch_amd")]
+import numpy as np
+import torch
+from voxelnet_amd import _lib, synth
+from voxelnet_amd import model as M
+from voxelnet_amd import targets as T
+from voxelnet_amd.config import grid_config
+from voxelnet_amd.predict import EVAL_DECODE, NMS_MODES, BoxDecoder
+from voxelnet_amd.voxelize import voxelize_device
+
+dev = "cuda:0"
+lines = []
+
+
+def say(s):
+    print(s, flush=True)
+    lines.append(s)
+
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--rounds", type=int, default=20)
+ap.add_argument("--round-launches", type=int, default=50)
+ap.add_argument("--out")
+args = ap.parse_args()
+if not torch.cuda.is_available():
+    sys.exit("bench_assign.py needs cuda:0 (there is no CPU path to measure)")
+if args.rounds < 5 or args.rounds * args.round_launches < 50:
+    sys.exit("at least 5 rounds and 50 timed launches per arm")
+lib = _lib.load()
+st = _lib.raw_stream()
+B = 2
+cfg = T.CLASS_CFG["Car"]
+anchors = torch.from_numpy(np.ascontiguousarray(T.generate_anchors("Car").reshape(-1, 7))).to(dev)
+N = anchors.shape[0]
+
+
+def boxes_of(n, seed):
+    """n cars inside the range, the sizes and yaws of synth.synth_labels"""
+    rng = np.random.default_rng(seed)
+    return np.stack([rng.uniform(4, 66, n), rng.uniform(-36, 36, n), cfg["z"] + rng.uniform(-0.2, 0.2, n),
+                     cfg["h"] * rng.uniform(0.9, 1.1, n), cfg["w"] * rng.uniform(0.9, 1.1, n), cfg["l"] * rng.uniform(0.9, 1.1, n),
+                     rng.uniform(-1.5, 1.5, n)], axis=1)
+
+
+def assigner(kind, G):
+    frames = [boxes_of(G, 10 * G + b) for b in range(B)]
+    gt = torch.from_numpy(np.stack(frames)).to(dev)
+    g2 = torch.from_numpy(np.stack([T.gt_standup_boxes(f) for f in frames])).to(dev)
+    cnt = torch.full((B,), G, dtype=torch.int32, device=dev)
+    pos, neg = (torch.empty((B, N), dtype=torch.float32, device=dev) for _ in range(2))
+    tgt = torch.empty((B, N, 7), dtype=torch.float32, device=dev)
+    keep = [gt, g2, cnt, pos, neg, tgt]
+    if kind == "reference":
+        nb = lib.vn_rpn_targets_workspace_bytes(B, N, G)
+        ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+        a = (anchors.data_ptr(), N, gt.data_ptr(), g2.data_ptr(), cnt.data_ptr(), B, G, cfg["pos_iou"], cfg["neg_iou"], cfg["h"],
+             pos.data_ptr(), neg.data_ptr(), tgt.data_ptr(), ws.data_ptr(), nb, st)
+        name = "vn_rpn_targets"
+    else:
+        nb = lib.vn_rpn_targets_iou_workspace_bytes(B, N, G)
+        ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+        a = (anchors.data_ptr(), N, gt.data_ptr(), cnt.data_ptr(), B, G, T.ASSIGN_KINDS[kind], cfg["pos_iou"], cfg["neg_iou"],
+             cfg["h"], pos.data_ptr(), neg.data_ptr(), tgt.data_ptr(), None, ws.data_ptr(), nb, st)
+        name = "vn_rpn_targets_iou"
+    keep.append(ws)
+    return (lambda: _lib.call(name, *a)), keep
+
+
+arms = []
+for G in (8, 128):
+    for kind in ("reference", "standup", "rotated"):
+        run, keep = assigner(kind, G)
+        arms.append((f"assign {kind}", f"{G} boxes", run, keep))
+
+# the encoder's forward on the benchmark's two Car frames
+M.set_precision("bf16")
+model = M.RPN3D("Car").to(dev).eval()
+grid = grid_config("Car")
+feats, coords = [], []
+for b, cloud in enumerate(synth.workload_frames(1, batch=B)):
+    f, c, _ = voxelize_device(torch.from_numpy(cloud).to(dev), grid, b, coord_cols=4)
+    feats.append(f)
+    coords.append(c)
+
+
+def encoder():
+    with torch.no_grad():
+        model.feature_net(feats, coords)
+
+
+arms.append(("encoder forward", f"K = {sum(f.shape[0] for f in feats)}", encoder, None))
+
+# the detection tail
+rng = np.random.default_rng(5)
+probs = torch.from_numpy(rng.random((B, 2, 200, 176)).astype(np.float32)).to(dev)
+deltas = torch.from_numpy((rng.standard_normal((B, 14, 200, 176)) * 0.3).astype(np.float32)).to(dev)
+dec = BoxDecoder("Car", dev)
+pre, post, thres, nms_thres = EVAL_DECODE["pre_nms_top_k"], 20, EVAL_DECODE["score_thres"], EVAL_DECODE["nms_thres"]
+mode = NMS_MODES[EVAL_DECODE["nms"]]
+nb = lib.vn_rpn_detect_workspace_bytes(B, N, pre)
+dws = torch.empty(nb, dtype=torch.uint8, device=dev)
+ob = torch.zeros((B, post, 7), dtype=torch.float32, device=dev)
+osc = torch.zeros((B, post), dtype=torch.float32, device=dev)
+oc = torch.zeros(B, dtype=torch.int32, device=dev)
+
+
+def detect(p, d, layout):
+    _lib.call("vn_rpn_detect_layout", p.data_ptr(), d.data_ptr(), dec._anchors_dev.data_ptr(), B, N, thres, pre, mode, nms_thres, post,
+              dec.anchor_h, ob.data_ptr(), osc.data_ptr(), oc.data_ptr(), dws.data_ptr(), nb, st, layout)
+
+
+def flat_with_transposes():
+    detect(probs.permute(0, 2, 3, 1).contiguous(), deltas.permute(0, 2, 3, 1).contiguous(), _lib.VN_DETECT_FLAT)
+
+
+arms.append(("detect flat", f"pre {pre}", lambda: detect(probs, deltas, _lib.VN_DETECT_FLAT), None))
+arms.append(("detect site", f"pre {pre}", lambda: detect(probs, deltas, _lib.VN_DETECT_SITE), None))
+arms.append(("detect flat + 2 transposes", f"pre {pre}", flat_with_transposes, None))
+
+for _, _, run, _ in arms:                              # warm-up: code objects, the caches
+    for _ in range(10):
+        run()
+torch.cuda.synchronize()
+us = {(a, b): [] for a, b, *_ in arms}
+for _ in range(args.rounds):
+    for a, b, run, _ in arms:
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        s.record()
+        for _ in range(args.round_launches):
+            run()
+        e.record()
+        torch.cuda.synchronize()
+        us[(a, b)].append(s.elapsed_time(e) / args.round_launches * 1e3)
+
+say(f"== target assignment (full Car grid, {N} anchors, B = {B}) and the evaluation tail: {args.rounds} alternated rounds of "
+    f"{args.round_launches} calls per arm; us per call, median [min, max] over the rounds ==")
+for a, b, *_ in arms:
+    v = us[(a, b)]
+    say(f"{a:28s} {b:12s} {statistics.median(v):9.2f} [{min(v):8.2f}, {max(v):8.2f}]")
+if args.out:
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    open(args.out, "w").write("\n".join(lines) + "\n")

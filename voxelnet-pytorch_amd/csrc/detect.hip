@@ -19,6 +19,9 @@
 //                 keeps); full rows come from L2 for the near pairs only.  512 threads = 2 waves per SIMD: the clipping
 //                 (~130 VGPRs, common.h box_iou_pair) does not spill.
 //   k_dt_gather   the kept rows in vn_rpn_predict's output format.
+// Layout: k_dt_filter and the decode of k_dt_select are templates on how the maps are read —
+// VN_DETECT_FLAT, the reference's reshape without a permute, or VN_DETECT_SITE, anchor n = 2 * site + a from probs[b, a, site]
+// and deltas[b, 7a .. 7a+6, site], the layout the loss trains.  The index in the key, in sel_idx and into `anchors` is n.
 // Equal scores: the larger flat index first (predict.hip, oracle/predict.py); -0.0 and +0.0 are one score; a NaN score
 // fails `p >= thres` and is never a candidate.
 #include "common.h"
@@ -46,6 +49,9 @@ __device__ __forceinline__ uint64_t dt_key(float p, int j) {
     return ((uint64_t)u << 32) | (uint32_t)j;
 }
 
+// SITE (VN_DETECT_SITE): flat element j = a * S + s of probs[b] is anchor n = 2 * s + a (S = N / 2 sites,
+// rotation a); the threads still walk the map in memory order, only the index in the key changes
+template <bool SITE>
 __global__ void __launch_bounds__(DT_FILTER_THREADS) k_dt_filter(const float *__restrict__ probs, int N, float thres,
                                                                  int32_t *__restrict__ count, uint64_t *__restrict__ cand_key) {
     const int b = blockIdx.y;
@@ -54,10 +60,13 @@ __global__ void __launch_bounds__(DT_FILTER_THREADS) k_dt_filter(const float *__
     const float p = probs[(size_t)b * N + j];
     if (p >= thres) {                                   // model.py:34; false for a NaN
         const int slot = atomicAdd(count + b, 1);        // order irrelevant: the keys are unique
-        cand_key[(size_t)b * N + slot] = dt_key(p, j);
+        const int S = N >> 1;
+        const int n = SITE ? (j >= S ? 2 * (j - S) + 1 : 2 * j) : j;
+        cand_key[(size_t)b * N + slot] = dt_key(p, n);
     }
 }
 
+template <bool SITE>
 __global__ void __launch_bounds__(DT_SEL_THREADS) k_dt_select(const float *__restrict__ probs, const float *__restrict__ deltas,
                                                               const double *__restrict__ anchors, int N,
                                                               const int32_t *__restrict__ count,
@@ -166,7 +175,13 @@ __global__ void __launch_bounds__(DT_SEL_THREADS) k_dt_select(const float *__res
     for (int t = tid; t < n_sel; t += DT_SEL_THREADS) {
         const int j = (int)(uint32_t)(skey[t] & 0xffffffffull);
         if (j >= N) continue;
-        const float *d = deltas + ((size_t)b * N + j) * 7;
+        // FLAT: seven consecutive elements; SITE: anchor j = 2 * s + a reads channels 7a .. 7a+6 at site s (stride S)
+        const int S = N >> 1;
+        const size_t d0 = SITE ? (size_t)b * N * 7 + (size_t)(j & 1) * 7 * S + (j >> 1) : ((size_t)b * N + j) * 7;
+        const size_t ds = SITE ? (size_t)S : 1;
+        float d[7];
+#pragma unroll
+        for (int k = 0; k < 7; ++k) d[k] = deltas[d0 + k * ds];
         const double *a = anchors + (size_t)j * 7;
         const double diag = sqrt(a[4] * a[4] + a[5] * a[5]);
         float *o = sel_boxes + ((size_t)b * pre_k + t) * 7;
@@ -177,7 +192,7 @@ __global__ void __launch_bounds__(DT_SEL_THREADS) k_dt_select(const float *__res
         o[4] = (float)((double)expf(d[4]) * a[4]);
         o[5] = (float)((double)expf(d[5]) * a[5]);
         o[6] = (float)((double)d[6] + a[6]);
-        sel_scores[(size_t)b * pre_k + t] = probs[(size_t)b * N + j];
+        sel_scores[(size_t)b * pre_k + t] = probs[(size_t)b * N + (SITE ? (size_t)(j & 1) * S + (j >> 1) : (size_t)j)];
         sel_idx[(size_t)b * pre_k + t] = j;
     }
     if (tid == 0) sel_counts[b] = n_sel;
@@ -337,16 +352,28 @@ inline bool dt_finite(double v) { return v - v == 0.0; }
 // workspace of vn_rpn_select_decode: [candidate counts | candidate keys]
 inline size_t dt_sel_cnt_bytes(int32_t B) { return vn_align((size_t)B * sizeof(int32_t)); }
 
+inline bool dt_layout_ok(int32_t layout, int32_t N) {
+    return layout == VN_DETECT_FLAT || (layout == VN_DETECT_SITE && N % 2 == 0);
+}
+
 int dt_select(const float *probs, const float *deltas, const double *anchors, int32_t B, int32_t N, float score_thres, int32_t pre_k,
-              double anchor_h, float *sel_boxes, float *sel_scores, int32_t *sel_idx, int32_t *sel_counts, char *ws, hipStream_t st) {
+              double anchor_h, float *sel_boxes, float *sel_scores, int32_t *sel_idx, int32_t *sel_counts, char *ws, hipStream_t st,
+              int32_t layout) {
     int32_t *cnt = reinterpret_cast<int32_t *>(ws);
     uint64_t *keys = reinterpret_cast<uint64_t *>(ws + dt_sel_cnt_bytes(B));
     VN_HIP(hipMemsetAsync(cnt, 0, (size_t)B * sizeof(int32_t), st));
     const dim3 grid((unsigned)((N + DT_FILTER_THREADS - 1) / DT_FILTER_THREADS), (unsigned)B);
-    k_dt_filter<<<grid, DT_FILTER_THREADS, 0, st>>>(probs, N, score_thres, cnt, keys);
-    VN_LAUNCH_STATUS();
-    k_dt_select<<<B, DT_SEL_THREADS, 0, st>>>(probs, deltas, anchors, N, cnt, keys, pre_k, anchor_h, sel_boxes, sel_scores, sel_idx,
-                                             sel_counts);
+    if (layout == VN_DETECT_SITE) {
+        k_dt_filter<true><<<grid, DT_FILTER_THREADS, 0, st>>>(probs, N, score_thres, cnt, keys);
+        VN_LAUNCH_STATUS();
+        k_dt_select<true><<<B, DT_SEL_THREADS, 0, st>>>(probs, deltas, anchors, N, cnt, keys, pre_k, anchor_h, sel_boxes, sel_scores,
+                                                       sel_idx, sel_counts);
+    } else {
+        k_dt_filter<false><<<grid, DT_FILTER_THREADS, 0, st>>>(probs, N, score_thres, cnt, keys);
+        VN_LAUNCH_STATUS();
+        k_dt_select<false><<<B, DT_SEL_THREADS, 0, st>>>(probs, deltas, anchors, N, cnt, keys, pre_k, anchor_h, sel_boxes, sel_scores,
+                                                        sel_idx, sel_counts);
+    }
     VN_LAUNCH_STATUS();
     return VN_OK;
 }
@@ -369,14 +396,22 @@ extern "C" size_t vn_rpn_select_decode_workspace_bytes(int32_t B, int32_t n_anch
     return dt_sel_cnt_bytes(B) + vn_align((size_t)B * n_anchors * sizeof(uint64_t));
 }
 
+extern "C" int vn_rpn_select_decode_layout(const float *probs, const float *deltas, const double *anchors, int32_t B,
+                                           int32_t n_anchors, float score_thres, int32_t pre_top_k, double anchor_h, float *sel_boxes,
+                                           float *sel_scores, int32_t *sel_idx, int32_t *sel_counts, void *workspace,
+                                           size_t workspace_bytes, vnStream stream, int32_t layout) {
+    VN_CHECK_ARG(probs && deltas && anchors && sel_boxes && sel_scores && sel_idx && sel_counts && workspace);
+    VN_CHECK_ARG(dt_select_ok(B, n_anchors, pre_top_k) && dt_layout_ok(layout, n_anchors));
+    if (workspace_bytes < vn_rpn_select_decode_workspace_bytes(B, n_anchors, pre_top_k)) return VN_EWORKSPACE;
+    return dt_select(probs, deltas, anchors, B, n_anchors, score_thres, pre_top_k, anchor_h, sel_boxes, sel_scores, sel_idx, sel_counts,
+                     static_cast<char *>(workspace), vn_stream(stream), layout);
+}
+
 extern "C" int vn_rpn_select_decode(const float *probs, const float *deltas, const double *anchors, int32_t B, int32_t n_anchors,
                                     float score_thres, int32_t pre_top_k, double anchor_h, float *sel_boxes, float *sel_scores,
                                     int32_t *sel_idx, int32_t *sel_counts, void *workspace, size_t workspace_bytes, vnStream stream) {
-    VN_CHECK_ARG(probs && deltas && anchors && sel_boxes && sel_scores && sel_idx && sel_counts && workspace);
-    VN_CHECK_ARG(dt_select_ok(B, n_anchors, pre_top_k));
-    if (workspace_bytes < vn_rpn_select_decode_workspace_bytes(B, n_anchors, pre_top_k)) return VN_EWORKSPACE;
-    return dt_select(probs, deltas, anchors, B, n_anchors, score_thres, pre_top_k, anchor_h, sel_boxes, sel_scores, sel_idx, sel_counts,
-                     static_cast<char *>(workspace), vn_stream(stream));
+    return vn_rpn_select_decode_layout(probs, deltas, anchors, B, n_anchors, score_thres, pre_top_k, anchor_h, sel_boxes, sel_scores,
+                                       sel_idx, sel_counts, workspace, workspace_bytes, stream, VN_DETECT_FLAT);
 }
 
 extern "C" size_t vn_box_nms_workspace_bytes(int32_t B, int32_t K) {
@@ -404,12 +439,12 @@ extern "C" size_t vn_rpn_detect_workspace_bytes(int32_t B, int32_t n_anchors, in
            vn_box_nms_workspace_bytes(B, pre_top_k);
 }
 
-extern "C" int vn_rpn_detect(const float *probs, const float *deltas, const double *anchors, int32_t B, int32_t n_anchors,
-                             float score_thres, int32_t pre_top_k, int32_t mode, double nms_thres, int32_t post_top_k,
-                             double anchor_h, float *boxes, float *scores, int32_t *counts, void *workspace, size_t workspace_bytes,
-                             vnStream stream) {
+extern "C" int vn_rpn_detect_layout(const float *probs, const float *deltas, const double *anchors, int32_t B, int32_t n_anchors,
+                                    float score_thres, int32_t pre_top_k, int32_t mode, double nms_thres, int32_t post_top_k,
+                                    double anchor_h, float *boxes, float *scores, int32_t *counts, void *workspace,
+                                    size_t workspace_bytes, vnStream stream, int32_t layout) {
     VN_CHECK_ARG(probs && deltas && anchors && boxes && scores && counts && workspace);
-    VN_CHECK_ARG(dt_select_ok(B, n_anchors, pre_top_k) && dt_nms_ok(B, pre_top_k, post_top_k));
+    VN_CHECK_ARG(dt_select_ok(B, n_anchors, pre_top_k) && dt_nms_ok(B, pre_top_k, post_top_k) && dt_layout_ok(layout, n_anchors));
     VN_CHECK_ARG((mode == VN_NMS_STANDUP || mode == VN_NMS_ROTATED) && dt_finite(nms_thres));
     if (workspace_bytes < vn_rpn_detect_workspace_bytes(B, n_anchors, pre_top_k)) return VN_EWORKSPACE;
     hipStream_t st = vn_stream(stream);
@@ -423,11 +458,19 @@ extern "C" int vn_rpn_detect(const float *probs, const float *deltas, const doub
     int32_t *keep_idx = reinterpret_cast<int32_t *>(p);   p += vn_align((size_t)B * DT_MAX_POST * sizeof(int32_t));
     int32_t *keep_counts = reinterpret_cast<int32_t *>(p); p += vn_align((size_t)B * sizeof(int32_t));
     int rc = dt_select(probs, deltas, anchors, B, n_anchors, score_thres, pre_top_k, anchor_h, sel_boxes, sel_scores, sel_idx,
-                       sel_counts, ws, st);
+                       sel_counts, ws, st, layout);
     if (rc != VN_OK) return rc;
     rc = dt_nms(sel_boxes, sel_counts, B, pre_top_k, mode, nms_thres, post_top_k, keep_idx, keep_counts, p, st);
     if (rc != VN_OK) return rc;
     k_dt_gather<<<B, 64, 0, st>>>(sel_boxes, sel_scores, pre_top_k, keep_idx, keep_counts, post_top_k, boxes, scores, counts);
     VN_LAUNCH_STATUS();
     return VN_OK;
+}
+
+extern "C" int vn_rpn_detect(const float *probs, const float *deltas, const double *anchors, int32_t B, int32_t n_anchors,
+                             float score_thres, int32_t pre_top_k, int32_t mode, double nms_thres, int32_t post_top_k,
+                             double anchor_h, float *boxes, float *scores, int32_t *counts, void *workspace, size_t workspace_bytes,
+                             vnStream stream) {
+    return vn_rpn_detect_layout(probs, deltas, anchors, B, n_anchors, score_thres, pre_top_k, mode, nms_thres, post_top_k, anchor_h,
+                                boxes, scores, counts, workspace, workspace_bytes, stream, VN_DETECT_FLAT);
 }

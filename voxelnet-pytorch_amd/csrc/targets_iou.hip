@@ -1,0 +1,227 @@
+// RPN training targets by a REAL IoU — beside targets.hip, which keeps the reference's assignment
+// with its zero-extent anchor rectangles and its (y1 - x1 + 1) union term.  Same inputs minus the host-made gt_standup,
+// same three output maps, plus the matched ground-truth index of every anchor.
+//
+// Rules (include/voxelnet_hip.h states them in full).  IoU(n,k) in float64, one of
+//   VN_ASSIGN_STANDUP  the axis-aligned hulls x +- (l|cos r| + w|sin r|)/2, y +- (l|sin r| + w|cos r|)/2 of the two rotated
+//                      footprints, areas without "+1", 0 when the hulls do not overlap (overlap written from the centres);
+//   VN_ASSIGN_ROTATED  common.h box_iou_pair's iou_bev of (anchor, box): 0 for a box that fails box_ok.
+// m_n = max_k IoU(n,k) at its smallest k = k_n;  M_k = max_n IoU(n,k) at its smallest n = n_k.
+// matched[n] = k_n when m_n >= pos_iou, else the smallest k with n_k == n and M_k > 0, else -1;  pos = matched >= 0;
+// neg = m_n < neg_iou and not pos (every anchor of a sample without a box).
+//
+// Launches: one memset (per-box maxima and arg-max words), k_ti_pairs twice, k_ti_encode.
+//   k_ti_pairs phase 0  one thread per anchor, the sample's boxes in LDS: every IoU once, m_n / k_n to the workspace, and
+//                       M_k by an integer atomicMax on the IoU's float64 bits (a non-negative double orders as its bits).
+//              phase 1  THE SAME CODE OBJECT again (phase is an argument: the IoUs come out bit for bit as in phase 0):
+//                       an anchor whose IoU with box k equals M_k enters n_k by an atomicMax on ~n.  Only boxes with
+//                       0 < M_k < pos_iou are visited: with M_k >= pos_iou the anchor n_k is positive through m_n already.
+//   Integer atomics of an order-independent result: deterministic from run to run; no floating-point atomics.
+//   Rotated kind: a pair whose centres are further apart than the two half-diagonals together has disjoint footprints, the
+//   pair function returns exactly 0 for it, and it is skipped without clipping (k_dt_nms's reject): ~1,000 of the 70,400
+//   anchors reach the float64 clipping per box.
+//   k_ti_encode         matched, pos, neg and the seven regression targets (k_tg_encode's expressions) of every anchor.
+#include "common.h"
+
+namespace {
+
+constexpr int TI_THREADS = 256;
+constexpr int TI_MAX_GT = VN_TARGETS_MAX_GT;
+
+// the axis-aligned hull of the rotated footprint of (x, y, ., ., w, l, r) as (x, y, half width hx, half height hy, area)
+__device__ __forceinline__ void ti_hull(const double (&q)[7], double (&h)[5]) {
+    const double c = fabs(cos(q[6])), s = fabs(sin(q[6]));
+    h[0] = q[0]; h[1] = q[1];
+    h[2] = (q[5] * c + q[4] * s) / 2;
+    h[3] = (q[5] * s + q[4] * c) / 2;
+    h[4] = (2.0 * h[2]) * (2.0 * h[3]);
+}
+
+// The overlap of [xa - ha, xa + ha] and [xg - hg, xg + hg] written from the centres: min(ha + hg - |xg - xa|, 2 min(ha, hg)).
+// Where one interval contains the other the second term is taken, which does not depend on the position: the anchors of a
+// row that all contain a box's hull along x (or lie inside it) get THE SAME IoU bit for bit, not values that differ by the
+// rounding of x +- ha, and the smallest index wins the tie in every implementation that writes the overlap this way.
+__device__ __forceinline__ double ti_standup_iou(const double (&a)[5], const double *__restrict__ g) {
+    const double iw = fmin((a[2] + g[2]) - fabs(g[0] - a[0]), 2.0 * fmin(a[2], g[2]));
+    const double ih = fmin((a[3] + g[3]) - fabs(g[1] - a[1]), 2.0 * fmin(a[3], g[3]));
+    if (!(iw > 0.0) || !(ih > 0.0)) return 0.0;
+    const double inter = iw * ih;
+    const double v = inter / ((a[4] + g[4]) - inter);
+    return v > 0.0 ? v : 0.0;          // (a NaN from infinite extents is 0)
+}
+
+template <int KIND>
+__global__ void __launch_bounds__(TI_THREADS) k_ti_pairs(const double *__restrict__ anchors, int N, const double *__restrict__ gt,
+                                                         const int32_t *__restrict__ counts, int max_gt, int phase, double pos_iou,
+                                                         double *__restrict__ best_iou, int32_t *__restrict__ best_k,
+                                                         unsigned long long *__restrict__ box_max, uint32_t *__restrict__ box_arg) {
+    __shared__ double sg[TI_MAX_GT][7];          // the boxes
+    __shared__ double sd[TI_MAX_GT][5];          // stand-up: ti_hull's five; rotated: [0] = half-diagonal, < 0 for an invalid box
+    __shared__ unsigned long long smax[TI_MAX_GT];          // phase 1: M_k's bits, 0 for a box that is not visited
+    const int b = blockIdx.y, G = min(max(counts[b], 0), max_gt);
+    for (int k = threadIdx.x; k < G; k += TI_THREADS) {
+        double q[7];
+#pragma unroll
+        for (int j = 0; j < 7; ++j) { q[j] = gt[((size_t)b * max_gt + k) * 7 + j]; sg[k][j] = q[j]; }
+        if (KIND == VN_ASSIGN_STANDUP) {
+            double h[5];
+            ti_hull(q, h);
+#pragma unroll
+            for (int j = 0; j < 5; ++j) sd[k][j] = h[j];
+        } else {
+            sd[k][0] = box_ok(q) ? 0.5 * sqrt(q[4] * q[4] + q[5] * q[5]) * 1.000001 : -1.0;
+        }
+        unsigned long long mk = 0;
+        if (phase == 1) {
+            mk = box_max[(size_t)b * max_gt + k];
+            if (!(__longlong_as_double((long long)mk) < pos_iou)) mk = 0;          // n_k is positive through m_n already
+        }
+        smax[k] = mk;
+    }
+    __syncthreads();
+    const int n = blockIdx.x * TI_THREADS + threadIdx.x;
+    if (n >= N) return;
+    double a[7];
+#pragma unroll
+    for (int j = 0; j < 7; ++j) a[j] = anchors[(size_t)n * 7 + j];
+    double ah[5] = {0.0, 0.0, 0.0, 0.0, 0.0}, hd_a = -1.0;
+    if (KIND == VN_ASSIGN_STANDUP) {
+        ti_hull(a, ah);
+    } else {
+        hd_a = box_ok(a) ? 0.5 * sqrt(a[4] * a[4] + a[5] * a[5]) * 1.000001 : -1.0;
+    }
+    double m = 0.0;
+    int kn = 0;
+#pragma unroll 1
+    for (int k = 0; k < G; ++k) {
+        if (phase == 1 && smax[k] == 0) continue;
+        double v = 0.0;
+        if (KIND == VN_ASSIGN_STANDUP) {
+            v = ti_standup_iou(ah, sd[k]);
+        } else {
+            const double hd = sd[k][0];
+            if (hd_a < 0.0 || hd < 0.0) continue;          // an invalid box: IoU 0
+            const double dx = sg[k][0] - a[0], dy = sg[k][1] - a[1], r = hd + hd_a;
+            if (dx * dx + dy * dy > r * r) continue;          // disjoint footprints: IoU exactly 0
+            double q[7], v3;
+#pragma unroll
+            for (int j = 0; j < 7; ++j) q[j] = sg[k][j];
+            box_iou_pair(a, q, v, v3);
+        }
+        if (!(v > 0.0)) continue;
+        const unsigned long long bits = (unsigned long long)__double_as_longlong(v);
+        if (phase == 0) {
+            if (v > m) { m = v; kn = k; }          // strict: the smallest k of the maximum
+            atomicMax(box_max + (size_t)b * max_gt + k, bits);
+        } else if (bits == smax[k]) {
+            atomicMax(box_arg + (size_t)b * max_gt + k, ~(uint32_t)n);          // the smallest n of the maximum
+        }
+    }
+    if (phase == 0) {
+        best_iou[(size_t)b * N + n] = m;
+        best_k[(size_t)b * N + n] = kn;
+    }
+}
+
+__global__ void __launch_bounds__(TI_THREADS) k_ti_encode(const double *__restrict__ anchors, int N, const double *__restrict__ gt,
+                                                          const int32_t *__restrict__ counts, int max_gt,
+                                                          const double *__restrict__ best_iou, const int32_t *__restrict__ best_k,
+                                                          const unsigned long long *__restrict__ box_max,
+                                                          const uint32_t *__restrict__ box_arg, double pos_iou, double neg_iou,
+                                                          double anchor_h, float *__restrict__ pos, float *__restrict__ neg,
+                                                          float *__restrict__ targets, int32_t *__restrict__ matched) {
+    __shared__ int garg[TI_MAX_GT];          // n_k of the boxes with 0 < M_k < pos_iou, else -1
+    const int b = blockIdx.y, G = min(max(counts[b], 0), max_gt);
+    for (int k = threadIdx.x; k < G; k += TI_THREADS) {
+        const double mk = __longlong_as_double((long long)box_max[(size_t)b * max_gt + k]);
+        garg[k] = (mk > 0.0 && mk < pos_iou) ? (int)~box_arg[(size_t)b * max_gt + k] : -1;
+    }
+    __syncthreads();
+    const int n = blockIdx.x * TI_THREADS + threadIdx.x;
+    if (n >= N) return;
+    const size_t o = (size_t)b * N + n;
+    const double m = best_iou[o];
+    int box = -1;
+    if (G > 0) {
+        if (m >= pos_iou) {
+            box = best_k[o];
+        } else {
+            for (int k = 0; k < G; ++k)
+                if (garg[k] == n) { box = k; break; }
+        }
+    }
+    pos[o] = box >= 0 ? 1.f : 0.f;
+    neg[o] = (box < 0 && (G == 0 || m < neg_iou)) ? 1.f : 0.f;
+    if (matched) matched[o] = box;
+    float t[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (box >= 0) {
+        const double *a = anchors + (size_t)n * 7;
+        const double *g = gt + ((size_t)b * max_gt + box) * 7;
+        const double diag = sqrt(a[4] * a[4] + a[5] * a[5]);      // utils.py:390-392, as k_tg_encode
+        t[0] = (float)((g[0] - a[0]) / diag);
+        t[1] = (float)((g[1] - a[1]) / diag);
+        t[2] = (float)((g[2] - a[2]) / anchor_h);
+        t[3] = (float)log(g[3] / a[3]);
+        t[4] = (float)log(g[4] / a[4]);
+        t[5] = (float)log(g[5] / a[5]);
+        t[6] = (float)(g[6] - a[6]);
+    }
+#pragma unroll
+    for (int j = 0; j < 7; ++j) targets[o * 7 + j] = t[j];
+}
+
+inline bool ti_args_ok(int32_t B, int32_t N, int32_t max_gt) {
+    return B > 0 && N > 0 && max_gt > 0 && max_gt <= TI_MAX_GT && (int64_t)B * N < (1ll << 31) / 8;
+}
+inline size_t ti_best_iou_bytes(int32_t B, int32_t N) { return vn_align((size_t)B * N * sizeof(double)); }
+inline size_t ti_best_k_bytes(int32_t B, int32_t N) { return vn_align((size_t)B * N * sizeof(int32_t)); }
+inline size_t ti_box_max_bytes(int32_t B, int32_t max_gt) { return vn_align((size_t)B * max_gt * sizeof(unsigned long long)); }
+inline size_t ti_box_arg_bytes(int32_t B, int32_t max_gt) { return vn_align((size_t)B * max_gt * sizeof(uint32_t)); }
+
+template <int KIND>
+int ti_launch_pairs(dim3 grid, hipStream_t st, const double *anchors, int N, const double *gt, const int32_t *counts, int max_gt,
+                    double pos_iou, double *best_iou, int32_t *best_k, unsigned long long *box_max, uint32_t *box_arg) {
+    for (int phase = 0; phase < 2; ++phase) {
+        k_ti_pairs<KIND><<<grid, TI_THREADS, 0, st>>>(anchors, N, gt, counts, max_gt, phase, pos_iou, best_iou, best_k, box_max, box_arg);
+        VN_LAUNCH_STATUS();
+    }
+    return VN_OK;
+}
+
+}  // namespace
+
+// workspace: [m_n | k_n | M_k bits | ~n_k]; the last two are adjacent so that one memset clears both
+extern "C" size_t vn_rpn_targets_iou_workspace_bytes(int32_t B, int32_t n_anchors, int32_t max_gt) {
+    if (!ti_args_ok(B, n_anchors, max_gt)) return 0;
+    return ti_best_iou_bytes(B, n_anchors) + ti_best_k_bytes(B, n_anchors) + ti_box_max_bytes(B, max_gt) + ti_box_arg_bytes(B, max_gt);
+}
+
+extern "C" int vn_rpn_targets_iou(const double *anchors, int32_t n_anchors, const double *gt, const int32_t *gt_count, int32_t B,
+                                  int32_t max_gt, int32_t iou_kind, float pos_iou, float neg_iou, double anchor_h, float *pos,
+                                  float *neg, float *targets, int32_t *matched, void *workspace, size_t workspace_bytes,
+                                  vnStream stream) {
+    VN_CHECK_ARG(anchors && gt && gt_count && pos && neg && targets && workspace && ti_args_ok(B, n_anchors, max_gt) &&
+                 anchor_h != 0.0);
+    VN_CHECK_ARG(iou_kind == VN_ASSIGN_STANDUP || iou_kind == VN_ASSIGN_ROTATED);
+    VN_CHECK_ARG(pos_iou == pos_iou && neg_iou == neg_iou);          // a NaN threshold
+    if (workspace_bytes < vn_rpn_targets_iou_workspace_bytes(B, n_anchors, max_gt)) return VN_EWORKSPACE;
+    hipStream_t st = vn_stream(stream);
+    char *p = static_cast<char *>(workspace);
+    double *best_iou = reinterpret_cast<double *>(p);                          p += ti_best_iou_bytes(B, n_anchors);
+    int32_t *best_k = reinterpret_cast<int32_t *>(p);                          p += ti_best_k_bytes(B, n_anchors);
+    unsigned long long *box_max = reinterpret_cast<unsigned long long *>(p);   p += ti_box_max_bytes(B, max_gt);
+    uint32_t *box_arg = reinterpret_cast<uint32_t *>(p);
+    VN_HIP(hipMemsetAsync(box_max, 0, ti_box_max_bytes(B, max_gt) + ti_box_arg_bytes(B, max_gt), st));
+    const dim3 grid((unsigned)((n_anchors + TI_THREADS - 1) / TI_THREADS), (unsigned)B);
+    const double pd = (double)pos_iou, nd = (double)neg_iou;
+    const int rc = iou_kind == VN_ASSIGN_STANDUP
+                       ? ti_launch_pairs<VN_ASSIGN_STANDUP>(grid, st, anchors, n_anchors, gt, gt_count, max_gt, pd, best_iou, best_k,
+                                                            box_max, box_arg)
+                       : ti_launch_pairs<VN_ASSIGN_ROTATED>(grid, st, anchors, n_anchors, gt, gt_count, max_gt, pd, best_iou, best_k,
+                                                            box_max, box_arg);
+    if (rc != VN_OK) return rc;
+    k_ti_encode<<<grid, TI_THREADS, 0, st>>>(anchors, n_anchors, gt, gt_count, max_gt, best_iou, best_k, box_max, box_arg, pd, nd,
+                                            anchor_h, pos, neg, targets, matched);
+    VN_LAUNCH_STATUS();
+    return VN_OK;
+}

@@ -162,6 +162,8 @@ VN_EVAL_MAX_TOPK, VN_EVAL_MAX_DIFF = 32, 8
 VN_EVAL_BBOX, VN_EVAL_MAX_DC, VN_EVAL_IMAGE_ROW = 2, 64, 12       # vn_eval_match_image's third metric; vn_boxes_to_image's row
 VN_NMS_STANDUP, VN_NMS_ROTATED = 0, 1       # vn_box_nms' / vn_rpn_detect's `mode`
 VN_DETECT_MAX_PRE, VN_PREDICT_MAX_TOPK = 4096, 64
+VN_DETECT_FLAT, VN_DETECT_SITE = 0, 1       # vn_rpn_select_decode_layout's / vn_rpn_detect_layout's `layout`
+VN_ASSIGN_STANDUP, VN_ASSIGN_ROTATED = 1, 2       # vn_rpn_targets_iou's `iou_kind`
 
 
 # name -> (restype, argtypes); mirrors include/voxelnet_hip.h one to one
@@ -306,6 +308,9 @@ SIGNATURES = {
     "vn_rpn_targets_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32]),
     "vn_rpn_targets": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, c_f32, ctypes.c_double, c_vp, c_vp, c_vp,
                                c_vp, c_sz, c_vp]),
+    "vn_rpn_targets_iou_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32]),
+    "vn_rpn_targets_iou": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_f32, c_f32, ctypes.c_double, c_vp, c_vp, c_vp,
+                                   c_vp, c_vp, c_sz, c_vp]),
     "vn_rpn_predict_workspace_bytes": (c_sz, [c_i32, c_i32]),
     "vn_rpn_predict": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, ctypes.c_double, c_i32, ctypes.c_double, c_vp, c_vp, c_vp,
                                c_vp, c_sz, c_vp]),
@@ -323,6 +328,10 @@ SIGNATURES = {
     "vn_rpn_detect_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32]),
     "vn_rpn_detect": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, c_i32, c_i32, ctypes.c_double, c_i32, ctypes.c_double, c_vp, c_vp,
                               c_vp, c_vp, c_sz, c_vp]),
+    "vn_rpn_select_decode_layout": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, c_i32, ctypes.c_double, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                            c_sz, c_vp, c_i32]),
+    "vn_rpn_detect_layout": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, c_i32, c_i32, ctypes.c_double, c_i32, ctypes.c_double, c_vp,
+                                     c_vp, c_vp, c_vp, c_sz, c_vp, c_i32]),
     "vn_clip_sgd_workspace_bytes": (c_sz, [c_i32]),
     "vn_clip_sgd": (c_i32, [c_vp, c_i32, c_f32, c_f32, c_i32, c_vp, c_sz, c_vp, c_vp]),
     "vn_clip_adamw_workspace_bytes": (c_sz, [c_i32]),

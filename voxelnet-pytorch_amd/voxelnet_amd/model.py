@@ -977,10 +977,17 @@ class RPN3D(nn.Module):
     # the rotated-IoU regression term (voxelnet_amd/iou_loss.py): None = off, nothing new is launched
     iou_loss, iou_weight, iou_metric = None, 1.0, "3d"
     last_iou = None          # the latest (L_iou, mean_iou) pair: detached device scalars, no synchronisation
+    # how anchors are assigned to ground truths (targets.TargetGenerator(assign=)): "reference" keeps the
+    # reference's assignment, "standup" / "rotated" assign by a real IoU
+    target_assign = "reference"
 
     def __init__(self, cls_name="Car", alpha=ALPHA, beta=BETA, sigma=SIGMA, *, cls_loss="bce", focal_alpha=0.25, focal_gamma=2.0,
-                 yaw_loss="diff", iou_loss=None, iou_weight=1.0, iou_metric="3d"):
+                 yaw_loss="diff", iou_loss=None, iou_weight=1.0, iou_metric="3d", target_assign="reference"):
         super().__init__()
+        from .targets import ASSIGN_KINDS
+        if target_assign not in ASSIGN_KINDS:
+            raise ValueError(f"target_assign must be one of {sorted(ASSIGN_KINDS)}, not {target_assign!r}")
+        self.target_assign = target_assign
         self.cls_name, self.alpha, self.beta, self.sigma = cls_name, alpha, beta, sigma
         loss_spec(cls_loss, focal_alpha, focal_gamma, yaw_loss)      # (ValueError here, not at the first step)
         self.cls_loss, self.focal_alpha, self.focal_gamma, self.yaw_loss = cls_loss, focal_alpha, focal_gamma, yaw_loss
@@ -1063,8 +1070,8 @@ class RPN3D(nn.Module):
     def _target_generator(self, device):
         from .targets import TargetGenerator
         gen = self.__dict__.get("_targets")
-        if gen is None or gen.device != torch.device(device):
-            gen = TargetGenerator(self.cls_name, device)
+        if gen is None or gen.device != torch.device(device) or gen.assign != self.target_assign:
+            gen = TargetGenerator(self.cls_name, device, assign=self.target_assign)
             # the maps the network EMITS, not rpn_output_shape: for Pedestrian / Cyclist that attribute repeats the anchor
             # grid (100 x 120, as the reference has it) while block 1 does not stride and the maps are 200 x 240
             g, s = grid_config(self.cls_name), self.middle_rpn._block1_stride
@@ -1076,14 +1083,15 @@ class RPN3D(nn.Module):
             self.anchors = gen.anchors
         return gen
 
-    def predict(self, data, probs, deltas, summary=False, visual=False):
+    def predict(self, data, probs, deltas, summary=False, visual=False, decode=None):
         """model.py:364-441 without the drawing branches: -> (tag, ret_box_3d_score), one array per sample of
         [cls_name, x, y, z, h, w, l, r, score] rows (strings, as np.concatenate makes them at model.py:389-394).
-        Decoding, score filter and NMS run on the device (voxelnet_amd/predict.py, csrc/predict.hip)."""
+        Decoding, score filter and NMS run on the device (voxelnet_amd/predict.py, csrc/predict.hip).  decode: a dict of
+        BoxDecoder keyword arguments (None: the reference's tail; predict.TRAINED_DECODE for a model trained here)."""
         if summary or visual:
             raise NotImplementedError("the summary / visual branches of RPN3D.predict draw with OpenCV (model.py:396-439): "
                                       "outside the accelerated path")
-        ret_box_3d, ret_score = self._box_decoder(probs.device)(probs, deltas)
+        ret_box_3d, ret_score = self._box_decoder(probs.device)(probs, deltas, **dict(decode or {}))
         out = []
         for boxes_3d, scores in zip(ret_box_3d, ret_score):
             out.append(np.concatenate([np.tile(self.cls_name, len(boxes_3d))[:, np.newaxis], boxes_3d,

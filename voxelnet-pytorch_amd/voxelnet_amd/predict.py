@@ -6,7 +6,12 @@ maps never leave HBM; only the <= NMS_POST_TOPK kept boxes per sample come back.
 For evaluation the same tail with the three steps an average precision needs (csrc/detect.hip): a
 pre-NMS top-K in the thousands, a greedy NMS on stand-up rectangles or on the rotated footprints, a post-NMS cap —
 `decode_device(..., nms=, pre_nms_top_k=)` through `vn_rpn_detect`, and its two halves on their own:
-`BoxDecoder.candidates_device` (`vn_rpn_select_decode`) and `nms_device` (`vn_box_nms`)."""
+`BoxDecoder.candidates_device` (`vn_rpn_select_decode`) and `nms_device` (`vn_box_nms`).
+
+`layout=`: "flat" reads the maps as the reference's reshape without a permute does; "site" reads
+them as the loss trains them — anchor (site, rotation a) is scored by probs[b, a, site] and decoded from
+deltas[b, 7a .. 7a+6, site] — through `vn_rpn_detect_layout` / `vn_rpn_select_decode_layout`.  A model trained by this
+package's loss has to be decoded with layout="site": `TRAINED_DECODE`."""
 import ctypes
 
 import numpy as np
@@ -19,12 +24,21 @@ SCORE_THRES, NMS_THRES, NMS_POST_TOPK = 0.96, 0.1, 20          # config.py:95-98
 NMS_MODES = {"standup": _lib.VN_NMS_STANDUP, "rotated": _lib.VN_NMS_ROTATED}
 # A starting point for RPN3D.evaluate(decode=...), NOT tuned: there is no trained checkpoint here to tune it on.
 EVAL_DECODE = dict(score_thres=0.1, nms="rotated", nms_thres=0.1, pre_nms_top_k=1024)
+LAYOUTS = {"flat": _lib.VN_DETECT_FLAT, "site": _lib.VN_DETECT_SITE}
+# EVAL_DECODE in the layout the loss trains: RPN3D.evaluate(decode=TRAINED_DECODE) for a model trained here
+TRAINED_DECODE = dict(EVAL_DECODE, layout="site")
 
 
 def _nms_mode(nms):
     if nms not in NMS_MODES:
         raise ValueError(f"nms must be one of {sorted(NMS_MODES)}, not {nms!r}")
     return NMS_MODES[nms]
+
+
+def _layout(layout):
+    if layout not in LAYOUTS:
+        raise ValueError(f"layout must be one of {sorted(LAYOUTS)}, not {layout!r}")
+    return LAYOUTS[layout]
 
 
 def _check_range(name, v, hi):
@@ -61,8 +75,10 @@ def nms_device(boxes, counts, mode="rotated", nms_thres=NMS_THRES, top_k=NMS_POS
 
 
 class BoxDecoder:
-    def __init__(self, cls_name="Car", device="cuda:0", anchors=None):
+    def __init__(self, cls_name="Car", device="cuda:0", anchors=None, layout="flat"):
+        _layout(layout)
         self.cls_name = cls_name
+        self.layout = layout          # the default of every call; each takes layout= of its own
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise _lib.VoxelnetHipError("BoxDecoder needs a HIP device (no CPU path)")
@@ -81,7 +97,7 @@ class BoxDecoder:
         return probs, deltas
 
     def decode_device(self, probs, deltas, score_thres=SCORE_THRES, nms_thres=NMS_THRES, top_k=NMS_POST_TOPK, nms="standup",
-                      pre_nms_top_k=None):
+                      pre_nms_top_k=None, layout=None):
         """probs (B,2,h,w), deltas (B,14,h,w) fp32 device tensors -> (boxes (B,top_k,7) f32, scores (B,top_k) f32, counts (B,)
         int32) ON THE DEVICE, enqueued on the current stream without any host synchronisation: per sample the first
         counts[b] rows are the kept detections in descending score, the rest is zero.  What evaluate.DetectionEvaluator
@@ -89,12 +105,14 @@ class BoxDecoder:
         nms="standup", pre_nms_top_k=None is the reference's tail (vn_rpn_predict: the top_k best candidates enter a
         stand-up-rectangle NMS).  Anything else goes through vn_rpn_detect: the pre_nms_top_k (default top_k) best
         candidates enter the NMS, on stand-up rectangles or, nms="rotated", on the rotated footprints; top_k caps what
-        it keeps."""
+        it keeps.  layout (None: the decoder's): "site" always goes through vn_rpn_detect_layout, with nms="standup",
+        pre_nms_top_k=None too (the reference's tail read in the layout the loss trains)."""
         mode = _nms_mode(nms)
+        lay = _layout(self.layout if layout is None else layout)
         probs, deltas = self._maps(probs, deltas, "predict")
         B, N = probs.shape[0], self.n_anchors
         dev = probs.device
-        if pre_nms_top_k is not None or mode != _lib.VN_NMS_STANDUP:
+        if pre_nms_top_k is not None or mode != _lib.VN_NMS_STANDUP or lay != _lib.VN_DETECT_FLAT:
             top_k = _check_range("top_k", top_k, _lib.VN_PREDICT_MAX_TOPK)
             pre = _check_range("pre_nms_top_k", top_k if pre_nms_top_k is None else pre_nms_top_k, _lib.VN_DETECT_MAX_PRE)
             if not np.isfinite(nms_thres):
@@ -102,7 +120,7 @@ class BoxDecoder:
         boxes = torch.zeros((B, top_k, 7), dtype=torch.float32, device=dev)
         scores = torch.zeros((B, top_k), dtype=torch.float32, device=dev)
         counts = torch.zeros(B, dtype=torch.int32, device=dev)
-        if pre_nms_top_k is None and mode == _lib.VN_NMS_STANDUP:
+        if pre_nms_top_k is None and mode == _lib.VN_NMS_STANDUP and lay == _lib.VN_DETECT_FLAT:
             nbytes = _lib.load().vn_rpn_predict_workspace_bytes(B, N)
             ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
             with _lib.on_device(dev):
@@ -113,15 +131,22 @@ class BoxDecoder:
         nbytes = _lib.load().vn_rpn_detect_workspace_bytes(B, N, pre)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         with _lib.on_device(dev):
-            _lib.call("vn_rpn_detect", probs.data_ptr(), deltas.data_ptr(), self._anchors_dev.data_ptr(), B, N, float(score_thres),
-                      pre, mode, float(nms_thres), top_k, self.anchor_h, boxes.data_ptr(), scores.data_ptr(), counts.data_ptr(),
-                      ws.data_ptr(), nbytes, _lib.raw_stream())
+            if lay == _lib.VN_DETECT_FLAT:
+                _lib.call("vn_rpn_detect", probs.data_ptr(), deltas.data_ptr(), self._anchors_dev.data_ptr(), B, N,
+                          float(score_thres), pre, mode, float(nms_thres), top_k, self.anchor_h, boxes.data_ptr(), scores.data_ptr(),
+                          counts.data_ptr(), ws.data_ptr(), nbytes, _lib.raw_stream())
+            else:
+                _lib.call("vn_rpn_detect_layout", probs.data_ptr(), deltas.data_ptr(), self._anchors_dev.data_ptr(), B, N,
+                          float(score_thres), pre, mode, float(nms_thres), top_k, self.anchor_h, boxes.data_ptr(), scores.data_ptr(),
+                          counts.data_ptr(), ws.data_ptr(), nbytes, _lib.raw_stream(), lay)
         return boxes, scores, counts
 
-    def candidates_device(self, probs, deltas, score_thres, pre_nms_top_k):
+    def candidates_device(self, probs, deltas, score_thres, pre_nms_top_k, layout=None):
         """The first half of the tail on its own (vn_rpn_select_decode): per sample the min(M, pre_nms_top_k) best of the M
         candidates with p >= score_thres, decoded, in descending (score, flat index) order -> (boxes (B,pre,7) f32, scores
-        (B,pre) f32, flat anchor indices (B,pre) int32, counts (B,) int32) on the device; rows past the count are zero."""
+        (B,pre) f32, flat anchor indices (B,pre) int32, counts (B,) int32) on the device; rows past the count are zero.
+        layout "site" (vn_rpn_select_decode_layout): the index is the anchor index n = 2 * site + rotation of the target maps."""
+        lay = _layout(self.layout if layout is None else layout)
         probs, deltas = self._maps(probs, deltas, "candidates")
         pre = _check_range("pre_nms_top_k", pre_nms_top_k, _lib.VN_DETECT_MAX_PRE)
         B, N = probs.shape[0], self.n_anchors
@@ -133,15 +158,20 @@ class BoxDecoder:
         nbytes = _lib.load().vn_rpn_select_decode_workspace_bytes(B, N, pre)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         with _lib.on_device(dev):
-            _lib.call("vn_rpn_select_decode", probs.data_ptr(), deltas.data_ptr(), self._anchors_dev.data_ptr(), B, N,
-                      float(score_thres), pre, self.anchor_h, boxes.data_ptr(), scores.data_ptr(), idx.data_ptr(), counts.data_ptr(),
-                      ws.data_ptr(), nbytes, _lib.raw_stream())
+            if lay == _lib.VN_DETECT_FLAT:
+                _lib.call("vn_rpn_select_decode", probs.data_ptr(), deltas.data_ptr(), self._anchors_dev.data_ptr(), B, N,
+                          float(score_thres), pre, self.anchor_h, boxes.data_ptr(), scores.data_ptr(), idx.data_ptr(),
+                          counts.data_ptr(), ws.data_ptr(), nbytes, _lib.raw_stream())
+            else:
+                _lib.call("vn_rpn_select_decode_layout", probs.data_ptr(), deltas.data_ptr(), self._anchors_dev.data_ptr(), B, N,
+                          float(score_thres), pre, self.anchor_h, boxes.data_ptr(), scores.data_ptr(), idx.data_ptr(),
+                          counts.data_ptr(), ws.data_ptr(), nbytes, _lib.raw_stream(), lay)
         return boxes, scores, idx, counts
 
     def __call__(self, probs, deltas, score_thres=SCORE_THRES, nms_thres=NMS_THRES, top_k=NMS_POST_TOPK, nms="standup",
-                 pre_nms_top_k=None):
+                 pre_nms_top_k=None, layout=None):
         """probs (B,2,h,w), deltas (B,14,h,w) fp32 device tensors -> ([boxes (n_i,7) f32 numpy], [scores (n_i,) f32 numpy])"""
-        boxes, scores, counts = self.decode_device(probs, deltas, score_thres, nms_thres, top_k, nms, pre_nms_top_k)
+        boxes, scores, counts = self.decode_device(probs, deltas, score_thres, nms_thres, top_k, nms, pre_nms_top_k, layout)
         B = boxes.shape[0]
         cnt = counts.cpu().numpy()
         bh, sh = boxes.cpu().numpy(), scores.cpu().numpy()

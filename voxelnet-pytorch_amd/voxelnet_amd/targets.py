@@ -6,7 +6,11 @@ Host side (O(number of boxes) NumPy, as in the reference): KITTI label lines -> 
 stand-up rectangles (utils.py:230-252, 283-330).  Device side: 70,400 anchors x boxes IoU with the reference's
 conventions and quirks, the positive / negative assignment and the regression encoding.  Outputs stay on the device
 in the layouts `RPN3D.loss` takes — no float64 host arrays, no six host-to-device copies per step (model.py:327-332).
-There is no CPU fallback: the HIP library must be present."""
+There is no CPU fallback: the HIP library must be present.
+
+`TargetGenerator(assign=)`: "reference" is that assignment, quirks included; "standup" and "rotated" assign by a real IoU
+(csrc/targets_iou.hip, `vn_rpn_targets_iou`) — what a model that is to be evaluated has to be
+trained with."""
 import ctypes
 import os
 
@@ -16,6 +20,7 @@ import torch
 from . import _lib
 
 MAX_GT = 128     # VN_TARGETS_MAX_GT (include/voxelnet_hip.h)
+ASSIGN_KINDS = {"reference": None, "standup": _lib.VN_ASSIGN_STANDUP, "rotated": _lib.VN_ASSIGN_ROTATED}
 
 # voxelnet/config.py:36-92 (anchor geometry, IoU thresholds) and :99-111 (mean KITTI calibration)
 CLASS_CFG = {
@@ -110,11 +115,21 @@ _LABEL_CACHE = os.environ.get("VN_LABEL_CACHE", "1") != "0"
 
 class TargetGenerator:
     """Device-resident anchors of one class + the launch: `gen(labels)` -> (pos_equal_one (B,h,w,2), neg_equal_one
-    (B,h,w,2), targets (B,h,w,14)) float32 tensors on `device`, the arrays of utils.generate_targets (utils.py:473)."""
+    (B,h,w,2), targets (B,h,w,14)) float32 tensors on `device`, the arrays of utils.generate_targets (utils.py:473).
+    assign: "reference" — the reference's assignment (vn_rpn_targets); "standup" / "rotated" — by the IoU of the stand-up
+    hulls / of the rotated footprints (vn_rpn_targets_iou), pos and neg then exclusive.  pos_iou /
+    neg_iou: the two thresholds (default: the class's)."""
 
-    def __init__(self, cls_name="Car", device="cuda:0", anchors=None):
+    def __init__(self, cls_name="Car", device="cuda:0", anchors=None, assign="reference", pos_iou=None, neg_iou=None):
+        if assign not in ASSIGN_KINDS:
+            raise ValueError(f"assign must be one of {sorted(ASSIGN_KINDS)}, not {assign!r}")
         self.cls_name = cls_name
         self.cfg = CLASS_CFG[cls_name]
+        self.assign = assign
+        self.pos_iou = float(self.cfg["pos_iou"] if pos_iou is None else pos_iou)
+        self.neg_iou = float(self.cfg["neg_iou"] if neg_iou is None else neg_iou)
+        if np.isnan(self.pos_iou) or np.isnan(self.neg_iou):
+            raise ValueError("pos_iou / neg_iou must not be NaN")
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise _lib.VoxelnetHipError("TargetGenerator needs a HIP device (no CPU path)")
@@ -125,8 +140,40 @@ class TargetGenerator:
         self._parsed = {}          # (label lines, coordinate) -> (G, 7) float64 boxes
         self._standup = {}         # id-free cache of gt_standup_boxes, keyed by the boxes' bytes
 
-    def from_boxes(self, gt_boxes):
-        """gt_boxes: list of (G_i, 7) float64 lidar boxes per sample"""
+    def _from_boxes_iou(self, gt_boxes, return_matched):
+        """assign = "standup" / "rotated": everything per box happens on the device too (no stand-up rectangles here)"""
+        B = len(gt_boxes)
+        G = max([b.shape[0] for b in gt_boxes] + [1])
+        if G > MAX_GT:
+            raise _lib.VoxelnetHipError(f"{G} ground-truth boxes in one sample; vn_rpn_targets_iou takes at most {MAX_GT}")
+        gt = np.zeros((B, G, 7), dtype=np.float64)
+        cnt = np.zeros(B, dtype=np.int32)
+        for b, boxes in enumerate(gt_boxes):
+            cnt[b] = boxes.shape[0]
+            gt[b, :boxes.shape[0]] = boxes
+        dev, N = self.device, self.n_anchors
+        gt_d, cnt_d = (torch.from_numpy(a).pin_memory().to(dev, non_blocking=True) for a in (gt, cnt))
+        pos = torch.empty((B, *self.shape, 2), dtype=torch.float32, device=dev)
+        neg = torch.empty((B, *self.shape, 2), dtype=torch.float32, device=dev)
+        tgt = torch.empty((B, *self.shape, 14), dtype=torch.float32, device=dev)
+        matched = torch.empty((B, *self.shape, 2), dtype=torch.int32, device=dev) if return_matched else None
+        nbytes = _lib.load().vn_rpn_targets_iou_workspace_bytes(B, N, G)
+        if nbytes == 0:
+            raise _lib.VoxelnetHipError("vn_rpn_targets_iou_workspace_bytes: unsupported sizes")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        with _lib.on_device(dev):
+            _lib.call("vn_rpn_targets_iou", self._anchors_dev.data_ptr(), N, gt_d.data_ptr(), cnt_d.data_ptr(), B, G,
+                      ASSIGN_KINDS[self.assign], self.pos_iou, self.neg_iou, float(self.cfg["h"]), pos.data_ptr(), neg.data_ptr(),
+                      tgt.data_ptr(), matched.data_ptr() if return_matched else None, ws.data_ptr(), nbytes, _lib.raw_stream())
+        return (pos, neg, tgt, matched) if return_matched else (pos, neg, tgt)
+
+    def from_boxes(self, gt_boxes, return_matched=False):
+        """gt_boxes: list of (G_i, 7) float64 lidar boxes per sample.  return_matched (assign "standup" / "rotated" only): a
+        fourth tensor (B,h,w,2) int32, every anchor's ground-truth index or -1"""
+        if self.assign != "reference":
+            return self._from_boxes_iou(gt_boxes, return_matched)
+        if return_matched:
+            raise ValueError('return_matched needs assign="standup" or "rotated": the reference assignment reports no index')
         B = len(gt_boxes)
         G = max([b.shape[0] for b in gt_boxes] + [1])
         if G > MAX_GT:
@@ -161,7 +208,7 @@ class TargetGenerator:
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         with _lib.on_device(dev):
             _lib.call("vn_rpn_targets", self._anchors_dev.data_ptr(), N, gt_d.data_ptr(), g2_d.data_ptr(), cnt_d.data_ptr(),
-                      B, G, float(self.cfg["pos_iou"]), float(self.cfg["neg_iou"]), float(self.cfg["h"]), pos.data_ptr(),
+                      B, G, self.pos_iou, self.neg_iou, float(self.cfg["h"]), pos.data_ptr(),
                       neg.data_ptr(), tgt.data_ptr(), ws.data_ptr(), nbytes,
                       _lib.raw_stream())
         return pos, neg, tgt
