@@ -986,6 +986,55 @@ int vn_rpn_iou_loss(const float *delta, const float *pos, const float *targets, 
                     int32_t B, int32_t H, int32_t W, int32_t kind, int32_t metric, const float *g /*device scalar, NULL = 1*/,
                     void *workspace, size_t workspace_bytes, float *out2, float *d_delta /*NULL: forward only*/, vnStream stream);
 
+/* ---- direction-classifier head (csrc/dir_head.hip) ----------------------------------------------
+ * A Conv2d(768, 2, 1) on the concatenation the two heads read: one logit per anchor n = 2*s + a (site s, rotation a)
+ * in the site layout of prob, dir[b][a][s]; z > 0 means heading bin 1, z == 0 bin 0.  With pi = the double nearest pi:
+ *   wrap_pi(x) = x - floor(x / pi) * pi;   bin(theta) = int(floor((theta - dir_offset) / pi)) & 1   (float64)
+ * Rows (cat_rows, d_cat) are VN_BF16 or VN_F32 with a stride in elements >= 768; the base must be 16-byte aligned and the
+ * stride a multiple of 16 bytes; w and d_w are [2][768] fp32, w 16-byte aligned.  A split ([hi|lo], VN_F32X3S) or any
+ * other row dtype is VN_EINVAL.  B * S rows, B > 0, S > 0, B * S < 2^31.  All four entry points are asynchronous on
+ * `stream`, without host synchronisation; none is part of vn_net_step.
+ *
+ * vn_dir_head_fwd: logits[b][c][s] = bias[c] + sum_k cat_rows[b*S + s][k] * w[c][k] (bias NULL: 0).  fp32 FMAs, 24 per
+ * lane in channel order, then a butterfly over 32 lanes: |error| <= 768 * 2^-24 * sum_k |x_k w_k| (+ the bias' rounding).
+ *
+ * vn_dir_head_bwd: a row whose two d_logits entries are both zero (+0 or -0) is SKIPPED — nothing of it is read or
+ * written, its d_cat row included.  The other rows m are listed in row order; with g_c = d_logits[b][c][s]:
+ *   d_cat[m][k] = round(d_cat[m][k] + g_0 w[0][k] + g_1 w[1][k])     accumulates; float64 arithmetic, ONE rounding to
+ *                                                                    the stored type
+ *   d_w[c][k]   = sum_m g_c * cat_rows[m][k];   d_bias[c] = sum_m g_c          (written, not accumulated; 0 without rows)
+ * The sums are float64 partials per workgroup over the list in list order, added in index order by a last pass and
+ * rounded to fp32 once: no atomics, bit-identical from run to run.  Five launches (count, scan, list, rows, final).
+ * VN_EWORKSPACE: workspace_bytes below vn_dir_head_bwd_workspace_bytes(B, S) (0 for sizes the call refuses).
+ *
+ * vn_rpn_dir_loss (argument order of vn_rpn_iou_loss): logits (B,2,H*W), pos (B,H,W,2), targets (B,H,W,14) fp32, anchors
+ * (H*W*2, 7) float64.  theta = (double)targets[b,s,7a+6] + anchors[2s+a][6], t = bin(theta), z = logits[b][a][s]:
+ *   out2[0] = L_dir = sum_b (1/P_b) sum m * (max(z,0) - z t + log1p(exp(-|z|))),  m = pos[b,s,a],  P_b = max(1, sum pos[b])
+ *   out2[1] = acc   = (sum m * [(z > 0) == t]) / max(1, sum m)                     (a diagnostic)
+ *   d_logits (B,2,H*W) or NULL: m * (sigmoid(z) - t) / P_b, and exactly +0.0f where m == 0 (what vn_dir_head_bwd skips);
+ *   every element is written.  float64 arithmetic; slab sums added in one fixed order; the scalars are the same bit for
+ *   bit with and without d_logits.  VN_EINVAL also for a dir_offset that is not finite; VN_EWORKSPACE as above.
+ *
+ * vn_boxes_rectify_yaw: boxes (B,K,7) in place, idx (B,K) the anchor index n as vn_rpn_select_decode_layout writes it
+ * with VN_DETECT_SITE, counts (B), dir_logits (B,2,n_anchors/2).  For the first min(counts[b], K) rows of sample b:
+ *   boxes[b][k][6] = wrap_pi(r - dir_offset) + dir_offset + pi * [dir_logits[b][n & 1][n >> 1] > 0]      (float64)
+ * Nothing else is written; a row whose idx is not in [0, n_anchors) is left as it is.  Both operations turn the box by
+ * a multiple of pi: the footprint, every IoU and a suppression's outcome stay.  VN_EINVAL: B, K or n_anchors <= 0, an
+ * odd n_anchors, a dir_offset that is not finite, a NULL pointer. */
+int vn_dir_head_fwd(const void *cat_rows, int32_t dtype, int64_t cat_stride, const float *w /*[2][768]*/,
+                    const float *bias /*[2] or NULL*/, int32_t B, int64_t S, float *logits /*[B][2][S]*/, vnStream stream);
+size_t vn_dir_head_bwd_workspace_bytes(int32_t B, int64_t S);
+int vn_dir_head_bwd(const float *d_logits /*[B][2][S]*/, const void *cat_rows, int32_t dtype, int64_t cat_stride,
+                    const float *w /*[2][768]*/, int32_t B, int64_t S, void *d_cat, int32_t d_cat_dtype, int64_t d_cat_stride,
+                    float *d_w /*[2][768]*/, float *d_bias /*[2]*/, void *workspace, size_t workspace_bytes, vnStream stream);
+size_t vn_rpn_dir_loss_workspace_bytes(int32_t B, int32_t H, int32_t W);
+int vn_rpn_dir_loss(const float *logits, const float *pos, const float *targets, const double *anchors /*[H*W*2,7]*/,
+                    int32_t B, int32_t H, int32_t W, double dir_offset, void *workspace, size_t workspace_bytes,
+                    float *out2, float *d_logits /*NULL: forward only*/, vnStream stream);
+int vn_boxes_rectify_yaw(float *boxes /*[B][K][7]*/, const int32_t *idx /*[B][K]*/, const int32_t *counts /*[B]*/,
+                         const float *dir_logits /*[B][2][n_anchors/2]*/, int32_t B, int32_t K, int32_t n_anchors,
+                         double dir_offset, vnStream stream);
+
 /* ---- optimizer tail (voxelnet/train.py:153-154 with the optimizer of train.py:130-132) ---------------------
  * torch.nn.utils.clip_grad_norm_(parameters, max_norm) followed by an update rule, in two launches.  The clip is the
  * same code under both rules (vn_clip_sgd here, vn_clip_adamw below):

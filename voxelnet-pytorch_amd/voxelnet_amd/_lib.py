@@ -305,6 +305,12 @@ SIGNATURES = {
                                               c_vp, c_vp, c_vp, c_vp, c_i32, c_i64, c_i32, c_vp, _P(VnLossSpec)]),
     "vn_rpn_iou_loss_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32]),
     "vn_rpn_iou_loss": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_sz, c_vp, c_vp, c_vp]),
+    "vn_dir_head_fwd": (c_i32, [c_vp, c_i32, c_i64, c_vp, c_vp, c_i32, c_i64, c_vp, c_vp]),
+    "vn_dir_head_bwd_workspace_bytes": (c_sz, [c_i32, c_i64]),
+    "vn_dir_head_bwd": (c_i32, [c_vp, c_vp, c_i32, c_i64, c_vp, c_i32, c_i64, c_vp, c_i32, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "vn_rpn_dir_loss_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32]),
+    "vn_rpn_dir_loss": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, ctypes.c_double, c_vp, c_sz, c_vp, c_vp, c_vp]),
+    "vn_boxes_rectify_yaw": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, ctypes.c_double, c_vp]),
     "vn_rpn_targets_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32]),
     "vn_rpn_targets": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, c_f32, ctypes.c_double, c_vp, c_vp, c_vp,
                                c_vp, c_sz, c_vp]),

@@ -16,6 +16,7 @@ torch.autograd.Functions below.  There is no CPU path: CPU tensors raise.
 """
 import contextlib
 import ctypes
+import math
 import os
 
 import numpy as np
@@ -412,6 +413,19 @@ def _detached(P):
     return {k: {kk: vv.detach() for kk, vv in v.items()} for k, v in P.items()}
 
 
+def _dir_grads(ctx, G):
+    """the direction head's two gradients behind a Function's other outputs: () without the head, (None, None) when its
+    logits had no gradient"""
+    if not ctx.dir_head:
+        return ()
+    g = G.get("dir_head")
+    return (None, None) if g is None else (g["weight"], g["bias"])
+
+
+def _dir_params(mid):
+    return [mid.dir_conv.conv.weight, mid.dir_conv.conv.bias]
+
+
 class _MiddleFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, mod, training, *flat):
@@ -419,6 +433,9 @@ class _MiddleFn(torch.autograd.Function):
         mode = _mode()
         names, P, Bf, _ = _collect_middle(mod)
         P = _detached(P)
+        dirp = None
+        if getattr(mod, "dir_conv", None) is not None:       # (the direction head's two parameters travel last)
+            dirp, flat = tuple(f.detach() for f in flat[-2:]), flat[:-2]
         P["heads"] = _heads_params([f.detach() for f in flat])
         with _lib.on_device(x.device):
             B, D, H, W, C = x.shape
@@ -429,27 +446,31 @@ class _MiddleFn(torch.autograd.Function):
                 dense = E.new_rows(B, (D, H, W), 128, torch.bfloat16, E.is_split(mode), x.device)
                 _lib.call("vn_cast_rows", xc.data_ptr(), _lib.VN_F32, 128, B * D * H * W, 128, dense.ptr(),
                           _lib.VN_BF16, dense.t.shape[-1], dense.lo_off, E.stream())
-            prob, reg, st = N.middle_forward(dense, P, Bf, mod._block1_stride, training, mode)
+            out = N.middle_forward(dense, P, Bf, mod._block1_stride, training, mode, dir_head=dirp)
+        st = out[-1]
         ctx.st, ctx.P, ctx.names = st, P, names
         ctx.need_dx = x.requires_grad
         ctx.training = bool(training)
-        return prob, reg
+        ctx.dir_head = dirp is not None
+        return out[:-1]
 
     @staticmethod
-    def backward(ctx, d_prob, d_reg):
+    def backward(ctx, d_prob, d_reg, d_dir=None):
         _need_training(ctx.training)
         with _lib.on_device(d_prob.device):
-            G, d_dense = N.middle_backward(ctx.st, d_prob.float(), d_reg.float(), ctx.P, need_dx=ctx.need_dx)
+            G, d_dense = N.middle_backward(ctx.st, d_prob.float(), d_reg.float(), ctx.P, need_dx=ctx.need_dx, d_dir=d_dir)
             dx = None
             if d_dense is not None:
                 dx = d_dense.t if d_dense.t.dtype == torch.float32 else d_dense.t.float()
-        return (dx, None, None) + tuple(_middle_grads_flat(ctx.names, G))
+        return (dx, None, None) + tuple(_middle_grads_flat(ctx.names, G)) + _dir_grads(ctx, G)
 
 
 class MiddleConvNet(nn.Module):
     """model.py:202-281.  forward(x (B,D,H,W,128)) -> (sigmoid(probs) (B,2,h,w), reg (B,14,h,w))."""
 
-    def __init__(self, cls_name="Car"):
+    last_dir_logits = None   # the direction head's latest logits (DESIGN.md 1i; dir_conv is registered by dir_head=True only)
+
+    def __init__(self, cls_name="Car", dir_head=False):
         super().__init__()
         g = grid_config(cls_name)
         self._block1_stride = g.block1_stride
@@ -469,6 +490,8 @@ class MiddleConvNet(nn.Module):
         self.deconv3 = DeConv2d(256, 256, 4, (4, 4), (0, 0))
         self.prob_conv = ConvMD(2, 768, 2, 1, (1, 1), (0, 0), bn=False, activation=False)
         self.reg_conv = ConvMD(2, 768, 14, 1, (1, 1), (0, 0), bn=False, activation=False)
+        if dir_head:
+            self.dir_conv = ConvMD(2, 768, 2, 1, (1, 1), (0, 0), bn=False, activation=False)
         # config.py FEATURE_HEIGHT/WIDTH: car 200x176; ped/cyc 100x120 (although the network emits 200x240,
         # SURVEY.md §8a a8 — kept as the reference has it)
         self.output_shape = [g.H // 2, g.W // 2]
@@ -477,6 +500,7 @@ class MiddleConvNet(nn.Module):
         d = self.__dict__.copy()
         d.pop("_native_arrays", None)
         d.pop("_nbt", None)
+        d.pop("last_dir_logits", None)
         return d
 
     def _tick(self):
@@ -489,7 +513,12 @@ class MiddleConvNet(nn.Module):
 
     def forward(self, x):
         _, _, _, flat = _collect_middle(self)
-        prob, reg = _MiddleFn.apply(x, self, self.training, *flat)
+        if getattr(self, "dir_conv", None) is not None:       # (same two outputs; the head's logits are kept as last_dir_logits)
+            if E.X3["on"]:
+                raise ValueError("dir_head: the fp32x3 mode is not supported with the direction head (DESIGN.md 1i)")
+            prob, reg, self.last_dir_logits = _MiddleFn.apply(x, self, self.training, *flat, *_dir_params(self))
+        else:
+            prob, reg = _MiddleFn.apply(x, self, self.training, *flat)
         self._tick()
         return prob, reg
 
@@ -595,6 +624,10 @@ class _DetectorFn(torch.autograd.Function):
         # requires grad stands for them, and the backward assigns / adds the gradients to .grad itself (what the direct_grads
         # mode did anyway): wrapping and unwrapping 104 inputs and their AccumulateGrad edges cost ~0.4 ms of host time a step
         ctx.anchor = len(flat) == 1
+        dirp = None
+        if rpn.dir_head and not ctx.anchor:       # (the direction head's two parameters travel last)
+            dirp, flat = tuple(f.detach() for f in flat[-2:]), flat[:-2]
+        ctx.dir_head = dirp is not None
         if ctx.anchor:
             flat = rpn._flat_params()
             vparams = flat[:nv]
@@ -688,14 +721,15 @@ class _DetectorFn(torch.autograd.Function):
                     _lib.call("vn_cast_rows", vw.data_ptr(), _lib.VN_F32, 128, vw.shape[0], 128, vw_rows.data_ptr(),
                               _lib.VN_BF16, 128, 0, E.stream())
                 sparse = (coord, vw_rows)
-            prob, reg, st = N.middle_forward(dense, P, Bf, mid._block1_stride, training, mode, sparse=sparse)
+            out = N.middle_forward(dense, P, Bf, mid._block1_stride, training, mode, sparse=sparse, dir_head=dirp)
+        st = out[-1]
         ctx.saved = (feature, coord, stats, wst, vparams, st, P, names)
         ctx.reducer = rpn.grad_reducer
         ctx.training = bool(training)
-        return prob, reg
+        return out[:-1]
 
     @staticmethod
-    def backward(ctx, d_prob, d_reg):
+    def backward(ctx, d_prob, d_reg, d_dir=None):
         _need_training(ctx.training)
         feature, coord, stats, wst, vparams, st, P, names = ctx.saved
         red = ctx.reducer
@@ -717,13 +751,13 @@ class _DetectorFn(torch.autograd.Function):
                 red.grad_ready(f"middle_rpn.{name}.batch_norm.weight", g["gamma"])
                 red.grad_ready(f"middle_rpn.{name}.batch_norm.bias", g["beta"])
         with _lib.on_device(d_prob.device):
-            G, d_dense = N.middle_backward(st, d_prob.float(), d_reg.float(), P, need_dx=True, on_grads=on_grads)
+            G, d_dense = N.middle_backward(st, d_prob.float(), d_reg.float(), P, need_dx=True, on_grads=on_grads, d_dir=d_dir)
             d_vw = d_dense if torch.is_tensor(d_dense) else gather_rows(d_dense, coord, feature.shape[0], 128)
             vg = featnet_backward(feature, wst, stats, d_vw, vparams, training=ctx.training)
             if red is not None:
                 for key, g in zip(VFE_KEYS, vg):
                     red.grad_ready(key, g)
-        return (None, None, None, None, None) + tuple(vg) + tuple(_middle_grads_flat(names, G))
+        return (None, None, None, None, None) + tuple(vg) + tuple(_middle_grads_flat(names, G)) + _dir_grads(ctx, G)
 
 
 def _detector_backward_segments(cfg, arr, heads, dp, dr, prob, dense, coord, vw_rows, K, ws, ws_bytes, garr, dhw, dhb, d_in,
@@ -980,9 +1014,14 @@ class RPN3D(nn.Module):
     # how anchors are assigned to ground truths (targets.TargetGenerator(assign=)): "reference" keeps the
     # reference's assignment, "standup" / "rotated" assign by a real IoU
     target_assign = "reference"
+    # the direction-classifier head (voxelnet_amd/dir_head.py): False = nothing is registered or launched
+    dir_head, dir_weight, dir_offset = False, 0.2, math.pi / 4
+    last_dir = None          # the latest (L_dir, acc) pair: detached device scalars, no synchronisation
+    last_dir_logits = None   # the head's logits (B,2,h,w) of the latest detect(), with the autograd graph in training
 
     def __init__(self, cls_name="Car", alpha=ALPHA, beta=BETA, sigma=SIGMA, *, cls_loss="bce", focal_alpha=0.25, focal_gamma=2.0,
-                 yaw_loss="diff", iou_loss=None, iou_weight=1.0, iou_metric="3d", target_assign="reference"):
+                 yaw_loss="diff", iou_loss=None, iou_weight=1.0, iou_metric="3d", target_assign="reference", dir_head=False,
+                 dir_weight=0.2, dir_offset=math.pi / 4):
         super().__init__()
         from .targets import ASSIGN_KINDS
         if target_assign not in ASSIGN_KINDS:
@@ -993,8 +1032,13 @@ class RPN3D(nn.Module):
         self.cls_loss, self.focal_alpha, self.focal_gamma, self.yaw_loss = cls_loss, focal_alpha, focal_gamma, yaw_loss
         _iou_check(iou_loss, iou_metric, iou_weight)
         self.iou_loss, self.iou_weight, self.iou_metric = iou_loss, iou_weight, iou_metric
+        self.dir_head = bool(dir_head)
+        if self.dir_head:
+            from .dir_head import check_spec
+            check_spec(dir_weight, dir_offset)
+            self.dir_weight, self.dir_offset = dir_weight, dir_offset
         self.feature_net = FeatureLearningNet(cls_name)
-        self.middle_rpn = MiddleConvNet(cls_name)
+        self.middle_rpn = MiddleConvNet(cls_name, dir_head=self.dir_head)
         self.rpn_output_shape = self.middle_rpn.output_shape
         self.anchors = None      # model.py:295 utils.generate_anchors(): built with the first target generation
         self.target_fn = None    # callable(label, rpn_output_shape) -> (pos, neg, targets)
@@ -1010,7 +1054,8 @@ class RPN3D(nn.Module):
     # gradient buffer, device-side target / decode helpers).  They are rebuilt on demand and must not travel with
     # `torch.save(model)` (the reference's checkpoint format, train.py:24/27) or `copy.deepcopy(model)`.
     _RUNTIME_KEYS = ("_side", "_tgt_stream", "_ws_pool", "_flat_grads", "_targets", "_decoder", "_nbt", "_flat_param_list", "_net_ctx",
-                     "_named_param_list", "_anchor_t", "_bucket_views", "_mg_cache", "_step_sc", "_nbt_table", "last_iou")
+                     "_named_param_list", "_anchor_t", "_bucket_views", "_mg_cache", "_step_sc", "_nbt_table", "last_iou", "last_dir",
+                     "last_dir_logits")
 
     def __getstate__(self):
         d = self.__dict__.copy()
@@ -1070,8 +1115,10 @@ class RPN3D(nn.Module):
     def _target_generator(self, device):
         from .targets import TargetGenerator
         gen = self.__dict__.get("_targets")
-        if gen is None or gen.device != torch.device(device) or gen.assign != self.target_assign:
-            gen = TargetGenerator(self.cls_name, device, assign=self.target_assign)
+        if (gen is None or gen.device != torch.device(device) or gen.assign != self.target_assign
+                or gen.keep_heading != bool(self.dir_head)):
+            # (with the direction head the labels keep their heading: its target is the bin of the box's yaw)
+            gen = TargetGenerator(self.cls_name, device, assign=self.target_assign, keep_heading=bool(self.dir_head))
             # the maps the network EMITS, not rpn_output_shape: for Pedestrian / Cyclist that attribute repeats the anchor
             # grid (100 x 120, as the reference has it) while block 1 does not stride and the maps are 200 x 240
             g, s = grid_config(self.cls_name), self.middle_rpn._block1_stride
@@ -1091,12 +1138,26 @@ class RPN3D(nn.Module):
         if summary or visual:
             raise NotImplementedError("the summary / visual branches of RPN3D.predict draw with OpenCV (model.py:396-439): "
                                       "outside the accelerated path")
-        ret_box_3d, ret_score = self._box_decoder(probs.device)(probs, deltas, **dict(decode or {}))
+        dec = self._box_decoder(probs.device)
+        ret_box_3d, ret_score = dec(probs, deltas, **self._dir_decode(dict(decode or {}), dec))
         out = []
         for boxes_3d, scores in zip(ret_box_3d, ret_score):
             out.append(np.concatenate([np.tile(self.cls_name, len(boxes_3d))[:, np.newaxis], boxes_3d,
                                        scores[:, np.newaxis]], axis=-1))
         return data[0], out
+
+    def _dir_decode(self, kw, dec=None):
+        """`kw` (BoxDecoder keyword arguments) with the direction head's logits of the latest detect() and its offset added
+        when the head is on; the decode then has to read the maps by site (predict.TRAINED_DECODE)"""
+        if not self.dir_head:
+            return kw
+        layout = kw.get("layout", dec.layout if dec is not None else "flat")
+        if layout != "site":
+            raise ValueError(f"dir_head: the direction head's logits are laid out by site; decode with layout='site' "
+                             f"(predict.TRAINED_DECODE), not {layout!r}")
+        if self.last_dir_logits is None:
+            raise _lib.VoxelnetHipError("dir_head: no logits yet — decode after detect() / forward()")
+        return dict(kw, dir_logits=self.last_dir_logits.detach(), dir_offset=float(self.dir_offset))
 
     def _box_decoder(self, device):
         from .predict import BoxDecoder
@@ -1139,13 +1200,15 @@ class RPN3D(nn.Module):
             raise ValueError("evaluate: the post-NMS cap is evaluator.top_k; `decode` may not set top_k")
         if ema is not None and ema.model is not self:
             raise ValueError("evaluate: `ema` averages another module")
+        if self.dir_head and kw.get("layout", dec.layout) != "site":
+            raise ValueError("evaluate: with dir_head the decode must read the maps by site: decode=predict.TRAINED_DECODE")
         was_training = self.training
         self.eval()
         try:
             with torch.no_grad(), (ema.applied() if ema is not None else contextlib.nullcontext()):
                 for x in batches:
                     prob, delta = self.detect(_parts_to(x[2], device), _parts_to(x[4], device))
-                    det = dec.decode_device(prob, delta, top_k=evaluator.top_k, **kw)
+                    det = dec.decode_device(prob, delta, top_k=evaluator.top_k, **self._dir_decode(kw, dec))
                     if calib_of is None:
                         evaluator.update(*det, x[1])
                     else:
@@ -1205,6 +1268,9 @@ class RPN3D(nn.Module):
         bs = len(voxel_features)
         feature, coord = _batch_cat(voxel_features, torch.float32), _batch_cat(voxel_coordinates, torch.int64)
         flat = self._flat_params()
+        if self.dir_head:
+            self._dir_check(_mode())
+            flat = flat + _dir_params(self.middle_rpn)
         if (self._native_ok(_mode()) and self.training and self.direct_grads and torch.is_grad_enabled() and feature.is_cuda
                 and self._all_need_grad(flat)):
             prob, reg = _DetectorFn.apply(feature, coord, bs, self, self.training, self._anchor(feature.device))
@@ -1213,16 +1279,29 @@ class RPN3D(nn.Module):
                 # (an autograd Function's needs_input_grad follows requires_grad, not the grad mode: without this, an eval
                 # forward under no_grad — the validation / predict call — left the native executor for the per-layer path)
                 flat = [p.detach() for p in flat]
-            prob, reg = _DetectorFn.apply(feature, coord, bs, self, self.training, *flat)
+            out = _DetectorFn.apply(feature, coord, bs, self, self.training, *flat)
+            prob, reg = out[0], out[1]
+            if self.dir_head:
+                self.last_dir_logits = out[2]
         self._tick()
         return prob, reg
+
+    def _dir_check(self, mode):
+        """ValueError for what the direction head does not run with (out of scope): the fp32x3 mode, and a
+        gradient reducer, whose bucket plan does not know the head's two parameters"""
+        if mode == "fp32x3" or E.X3["on"]:
+            raise ValueError("dir_head: the fp32x3 mode is not supported with the direction head; use 'bf16' or 'fp32'")
+        if self.grad_reducer is not None:
+            raise ValueError("dir_head: a grad_reducer is not supported with the direction head: the DDP bucket plan does not "
+                             "know its two parameters")
 
     def _native_ok(self, mode):
         """ONE predicate for "this call runs on the native executor" (csrc/runtime.hip: grids whose depth folds to 2 —
         D = 9 ... 12 —, bf16 / fp32 modes), used by detect() to pick the one-tensor call and by _DetectorFn.forward to pick the
-        path: every other configuration (bf16x3, other depths, native_executor = False) trains through the per-layer
-        orchestration with the 104 parameters as autograd inputs."""
-        return bool(self.native_executor) and not E.is_split(mode) and 9 <= self.feature_net._grid.D <= 12
+        path: every other configuration (bf16x3, other depths, native_executor = False, dir_head = True: the direction head
+        rides on the per-layer orchestration) trains through the per-layer orchestration with the 104
+        parameters (and the head's two) as autograd inputs."""
+        return bool(self.native_executor) and not self.dir_head and not E.is_split(mode) and 9 <= self.feature_net._grid.D <= 12
 
     def _all_need_grad(self, flat):
         return all(p.requires_grad for p in flat)
@@ -1243,7 +1322,9 @@ class RPN3D(nn.Module):
         """model.py:310-352 -> (loss, cls_loss, reg_loss, cls_pos_loss_rec, cls_neg_loss_rec), fused (csrc/loss.hip); with
         cls_loss="focal" / yaw_loss="sin" the objective of DESIGN.md 1e, same five outputs.  With iou_loss set,
         iou_weight * L_iou (the anchors are the target generator's) is added to loss and to reg_loss and
-        the pair (L_iou, mean_iou) is kept, detached, as self.last_iou."""
+        the pair (L_iou, mean_iou) is kept, detached, as self.last_iou.  With dir_head on, dir_weight * L_dir (DESIGN.md 1i;
+        the logits are last_dir_logits of the detect() before) is added to loss and to cls_loss, and (L_dir, acc) is kept,
+        detached, as self.last_dir."""
         dev = prob_out.device
         spec, iou = self._loss_spec(), self._iou_spec()
 
@@ -1254,17 +1335,29 @@ class RPN3D(nn.Module):
         pos, tgt = f32(pos_equal_one), f32(targets)
         out = _LossFn.apply(prob_out, delta_out, pos, f32(neg_equal_one), tgt,
                             float(self.alpha), float(self.beta), float(self.sigma), spec)
-        if iou is None:
+        if iou is None and not self.dir_head:
             return out
-        from .iou_loss import rpn_iou_loss
         gen = self._target_generator(dev)
         if gen.n_anchors != delta_out.shape[2] * delta_out.shape[3] * 2:
-            raise _lib.VoxelnetHipError(f"iou_loss: the target generator's anchor grid {tuple(gen.shape)} is not the "
+            raise _lib.VoxelnetHipError(f"iou_loss / dir_head: the target generator's anchor grid {tuple(gen.shape)} is not the "
                                         f"regression map's {tuple(delta_out.shape[2:])}")
-        l_iou, mean_iou = rpn_iou_loss(delta_out, pos, tgt, gen._anchors_dev, iou[0], iou[1])
-        self.last_iou = (l_iou.detach(), mean_iou)
-        term = iou[2] * l_iou
-        return (out[0] + term, out[1], out[2] + term) + tuple(out[3:])
+        if iou is not None:
+            from .iou_loss import rpn_iou_loss
+            l_iou, mean_iou = rpn_iou_loss(delta_out, pos, tgt, gen._anchors_dev, iou[0], iou[1])
+            self.last_iou = (l_iou.detach(), mean_iou)
+            term = iou[2] * l_iou
+            out = (out[0] + term, out[1], out[2] + term) + tuple(out[3:])
+        if self.dir_head:
+            from .dir_head import check_spec, rpn_dir_loss
+            check_spec(self.dir_weight, self.dir_offset)
+            logits = self.last_dir_logits
+            if logits is None or logits.shape[0] != delta_out.shape[0] or tuple(logits.shape[2:]) != tuple(delta_out.shape[2:]):
+                raise _lib.VoxelnetHipError("dir_head: loss() needs the logits of the detect() that produced these maps")
+            l_dir, acc = rpn_dir_loss(logits, pos, tgt, gen._anchors_dev, float(self.dir_offset))
+            self.last_dir = (l_dir.detach(), acc)
+            term = float(self.dir_weight) * l_dir
+            out = (out[0] + term, out[1] + term) + tuple(out[2:])
+        return out
 
     # ---- one library call per train step (vn_net_step) ------------------------------------------------------------------
     def _step_scratch(self, dev, K, T, B, mode, hf, wf):
@@ -1315,7 +1408,8 @@ class RPN3D(nn.Module):
         weight average attached to the optimizer (optim.attach_ema) a ClipSGD steps after the call too, same parameters.
         Whatever the fused call does not cover — per-layer orchestration, eval mode, target_fn, gradient accumulation, a
         reducer without a communication stream, bench.py's per-section timer, the rotated-IoU term (iou_loss set: it is
-        not part of vnStep) — takes the separate calls, same results."""
+        not part of vnStep), the direction head (dir_head=True: it runs on the per-layer orchestration, outside
+        the native executor) — takes the separate calls, same results."""
         from .optim import ClipSGD
         mode = _mode()
         spec = self._loss_spec()            # (checked before anything is launched)

@@ -44,12 +44,21 @@ class MiddleState:
     pass
 
 
-def middle_forward(dense, P, Bf, block1_stride, training, mode, sparse=None):
+def _dir_rows(rows, mode, what):
+    """the (B*hf*wf, 768) row matrix of the concatenation (or of its gradient) for the direction head's kernels"""
+    if E.is_split(mode) or rows.lo_off:
+        raise ValueError(f"dir_head: {what} in a split [hi|lo] row format is not supported (DESIGN.md 1i)")
+    return rows.t.view(-1, rows.t.shape[-1])
+
+
+def middle_forward(dense, P, Bf, block1_stride, training, mode, sparse=None, dir_head=None):
     """dense: Rows (B,D,H,W,128[hi|lo]).  P[name] = {weight,bias,gamma,beta}; Bf[name] =
     {running_mean,running_var}; P['heads'] = {weight (16,768,1,1), bias (16)}.
     sparse = (coord (K,4) int64, vw_rows (K,128) operand dtype): the occupied sites of `dense`; the first
     Conv3d then runs in its sparse form (engine.first_layer_forward_sparse) and middle_backward returns the
     (K,128) voxel gradient instead of a dense grid gradient.
+    dir_head = (weight (2,768[,1,1]), bias (2)) fp32: the direction head runs on the concatenation after the
+    heads, its logits (B,2,h,w) fp32 are a third output in front of the state, and the state keeps the concatenation.
     Returns prob (B,2,h,w) after sigmoid, reg (B,14,h,w) fp32 NCHW, and the saved state."""
     specs = dict(layer_table(block1_stride))
     st = MiddleState()
@@ -100,17 +109,24 @@ def middle_forward(dense, P, Bf, block1_stride, training, mode, sparse=None):
     st.prob = prob.detach()     # an alias, NOT the returned tensor: saving an autograd.Function's own output on its ctx is a
                                 # reference cycle that only the cyclic GC frees (720 MB of dense grid per step piled up)
     st.fmap = (hf, wf)
+    if dir_head is not None:
+        from .dir_head import dir_head_forward
+        st.cat, st.dir_w = cat, dir_head[0]
+        logits = dir_head_forward(_dir_rows(cat, mode, "the concatenation"), dir_head[0], dir_head[1], B).view(B, 2, hf, wf)
+        return prob, reg, logits, st
     return prob, reg, st
 
 
-def middle_backward(st, d_prob, d_reg, P, need_dx=True, on_grads=None):
+def middle_backward(st, d_prob, d_reg, P, need_dx=True, on_grads=None, d_dir=None):
     """-> ({name: {weight,bias,gamma,beta}}, d_dense Rows (plain f32/bf16) or None).
-    on_grads(layer_name, grads): called as soon as a layer's parameter gradients exist (DDP bucketing)."""
+    on_grads(layer_name, grads): called as soon as a layer's parameter gradients exist (DDP bucketing).
+    d_dir (B,2,h,w) fp32, for a forward that ran the direction head: its backward adds to the concatenation's gradient at
+    the rows where d_dir is not zero, right after the heads' data gradient wrote it; G["dir_head"] = {weight, bias}."""
     with E._x3_as_saved(st):
-        return _middle_backward(st, d_prob, d_reg, P, need_dx, on_grads)
+        return _middle_backward(st, d_prob, d_reg, P, need_dx, on_grads, d_dir)
 
 
-def _middle_backward(st, d_prob, d_reg, P, need_dx=True, on_grads=None):
+def _middle_backward(st, d_prob, d_reg, P, need_dx=True, on_grads=None, d_dir=None):
     mode = st.mode
     split = E.is_split(mode)
     L = st.layers
@@ -125,6 +141,11 @@ def _middle_backward(st, d_prob, d_reg, P, need_dx=True, on_grads=None):
     G["heads"], d_cat = E.layer_backward(L["heads"], d_rows, P["heads"], mode)
     if on_grads is not None:
         on_grads("heads", G["heads"])
+    if d_dir is not None:
+        from .dir_head import dir_head_backward
+        dw, db = dir_head_backward(d_dir.contiguous().float().view(B, 2, hf * wf), _dir_rows(st.cat, mode, "the concatenation"),
+                                   st.dir_w, _dir_rows(d_cat, mode, "the concatenation's gradient"))
+        G["dir_head"] = {"weight": dw.view_as(st.dir_w), "bias": db}
 
     def dslice(off):
         return Rows(d_cat.t[..., off:off + 256], 256)

@@ -11,8 +11,13 @@ pre-NMS top-K in the thousands, a greedy NMS on stand-up rectangles or on the ro
 `layout=`: "flat" reads the maps as the reference's reshape without a permute does; "site" reads
 them as the loss trains them — anchor (site, rotation a) is scored by probs[b, a, site] and decoded from
 deltas[b, 7a .. 7a+6, site] — through `vn_rpn_detect_layout` / `vn_rpn_select_decode_layout`.  A model trained by this
-package's loss has to be decoded with layout="site": `TRAINED_DECODE`."""
+package's loss has to be decoded with layout="site": `TRAINED_DECODE`.
+
+`dir_logits=`: the direction head's map (B,2,h,w) turns every detection's yaw into the half-plane its
+anchor's logit names (`dir_head.rectify_yaw`); the tail is then composed from the public pieces — candidates, the yaw
+rectification, `nms_device`, a gather of the kept rows — and needs layout="site"."""
 import ctypes
+import math
 
 import numpy as np
 import torch
@@ -96,8 +101,38 @@ class BoxDecoder:
             raise ValueError(f"maps of {probs[0].numel()} / {deltas[0].numel()} elements do not match {N} anchors")
         return probs, deltas
 
+    def _decode_dir(self, probs, deltas, score_thres, nms_thres, top_k, nms, pre_nms_top_k, layout, dir_logits, dir_offset):
+        """decode_device with the direction head's logits: vn_rpn_select_decode_layout -> vn_boxes_rectify_yaw -> vn_box_nms ->
+        a gather of the kept rows.  The yaw changes by multiples of pi only, so the candidates, the kept set and the scores
+        are those of the fused tail (vn_rpn_detect_layout) on the same maps."""
+        from .dir_head import rectify_yaw
+        _nms_mode(nms)
+        lay = self.layout if layout is None else layout
+        if _layout(lay) != _lib.VN_DETECT_SITE:
+            raise ValueError(f"dir_logits: the direction head's logits are laid out by site; layout must be 'site', not {lay!r}")
+        top_k = _check_range("top_k", top_k, _lib.VN_PREDICT_MAX_TOPK)
+        pre = _check_range("pre_nms_top_k", top_k if pre_nms_top_k is None else pre_nms_top_k, _lib.VN_DETECT_MAX_PRE)
+        if not np.isfinite(nms_thres):
+            raise ValueError("nms_thres must be finite")
+        if not (torch.is_tensor(dir_logits) and dir_logits.is_cuda):
+            raise _lib.VoxelnetHipError("predict: dir_logits must be a HIP tensor (no CPU path)")
+        B = probs.shape[0]
+        if dir_logits.shape[0] != B or dir_logits.numel() != B * self.n_anchors:
+            raise ValueError(f"dir_logits {tuple(dir_logits.shape)} does not match {B} samples of {self.n_anchors} anchors")
+        dl = dir_logits.detach().float().contiguous().view(B, 2, self.n_anchors // 2)
+        cb, cs, idx, cc = self.candidates_device(probs, deltas, score_thres, pre, layout="site")
+        rectify_yaw(cb, idx, cc, dl, self.n_anchors, dir_offset)
+        keep, kc = nms_device(cb, cc, nms, nms_thres, top_k)
+        live = (keep >= 0) & (torch.arange(top_k, device=keep.device)[None, :] < kc[:, None])
+        rows = keep.clamp(min=0).long()
+        boxes = torch.gather(cb, 1, rows[:, :, None].expand(B, top_k, 7))
+        scores = torch.gather(cs, 1, rows)
+        boxes = torch.where(live[:, :, None], boxes, torch.zeros_like(boxes))          # rows past the count are zero
+        scores = torch.where(live, scores, torch.zeros_like(scores))
+        return boxes, scores, kc
+
     def decode_device(self, probs, deltas, score_thres=SCORE_THRES, nms_thres=NMS_THRES, top_k=NMS_POST_TOPK, nms="standup",
-                      pre_nms_top_k=None, layout=None):
+                      pre_nms_top_k=None, layout=None, dir_logits=None, dir_offset=math.pi / 4):
         """probs (B,2,h,w), deltas (B,14,h,w) fp32 device tensors -> (boxes (B,top_k,7) f32, scores (B,top_k) f32, counts (B,)
         int32) ON THE DEVICE, enqueued on the current stream without any host synchronisation: per sample the first
         counts[b] rows are the kept detections in descending score, the rest is zero.  What evaluate.DetectionEvaluator
@@ -106,7 +141,12 @@ class BoxDecoder:
         stand-up-rectangle NMS).  Anything else goes through vn_rpn_detect: the pre_nms_top_k (default top_k) best
         candidates enter the NMS, on stand-up rectangles or, nms="rotated", on the rotated footprints; top_k caps what
         it keeps.  layout (None: the decoder's): "site" always goes through vn_rpn_detect_layout, with nms="standup",
-        pre_nms_top_k=None too (the reference's tail read in the layout the loss trains)."""
+        pre_nms_top_k=None too (the reference's tail read in the layout the loss trains).
+        dir_logits (None: every path above exactly as it is): the direction head's (B,2,h,w) map, layout "site" only — column 6
+        becomes wrap_pi(r - dir_offset) + dir_offset + pi * [logit > 0] through the composed tail; apart from that
+        column the kept set and the scores are the ones of the call without it."""
+        if dir_logits is not None:
+            return self._decode_dir(probs, deltas, score_thres, nms_thres, top_k, nms, pre_nms_top_k, layout, dir_logits, dir_offset)
         mode = _nms_mode(nms)
         lay = _layout(self.layout if layout is None else layout)
         probs, deltas = self._maps(probs, deltas, "predict")
@@ -141,12 +181,15 @@ class BoxDecoder:
                           counts.data_ptr(), ws.data_ptr(), nbytes, _lib.raw_stream(), lay)
         return boxes, scores, counts
 
-    def candidates_device(self, probs, deltas, score_thres, pre_nms_top_k, layout=None):
+    def candidates_device(self, probs, deltas, score_thres, pre_nms_top_k, layout=None, dir_logits=None, dir_offset=math.pi / 4):
         """The first half of the tail on its own (vn_rpn_select_decode): per sample the min(M, pre_nms_top_k) best of the M
         candidates with p >= score_thres, decoded, in descending (score, flat index) order -> (boxes (B,pre,7) f32, scores
         (B,pre) f32, flat anchor indices (B,pre) int32, counts (B,) int32) on the device; rows past the count are zero.
-        layout "site" (vn_rpn_select_decode_layout): the index is the anchor index n = 2 * site + rotation of the target maps."""
+        layout "site" (vn_rpn_select_decode_layout): the index is the anchor index n = 2 * site + rotation of the target maps.
+        dir_logits (layout "site" only): the candidates' yaw is rectified by the direction head's map (dir_head.rectify_yaw)."""
         lay = _layout(self.layout if layout is None else layout)
+        if dir_logits is not None and lay != _lib.VN_DETECT_SITE:
+            raise ValueError("dir_logits: the direction head's logits are laid out by site; layout must be 'site'")
         probs, deltas = self._maps(probs, deltas, "candidates")
         pre = _check_range("pre_nms_top_k", pre_nms_top_k, _lib.VN_DETECT_MAX_PRE)
         B, N = probs.shape[0], self.n_anchors
@@ -166,12 +209,20 @@ class BoxDecoder:
                 _lib.call("vn_rpn_select_decode_layout", probs.data_ptr(), deltas.data_ptr(), self._anchors_dev.data_ptr(), B, N,
                           float(score_thres), pre, self.anchor_h, boxes.data_ptr(), scores.data_ptr(), idx.data_ptr(),
                           counts.data_ptr(), ws.data_ptr(), nbytes, _lib.raw_stream(), lay)
+        if dir_logits is not None:
+            from .dir_head import rectify_yaw
+            if not (torch.is_tensor(dir_logits) and dir_logits.is_cuda):
+                raise _lib.VoxelnetHipError("candidates: dir_logits must be a HIP tensor (no CPU path)")
+            if dir_logits.shape[0] != B or dir_logits.numel() != B * N:
+                raise ValueError(f"dir_logits {tuple(dir_logits.shape)} does not match {B} samples of {N} anchors")
+            rectify_yaw(boxes, idx, counts, dir_logits.detach().float().contiguous().view(B, 2, N // 2), N, dir_offset)
         return boxes, scores, idx, counts
 
     def __call__(self, probs, deltas, score_thres=SCORE_THRES, nms_thres=NMS_THRES, top_k=NMS_POST_TOPK, nms="standup",
-                 pre_nms_top_k=None, layout=None):
+                 pre_nms_top_k=None, layout=None, dir_logits=None, dir_offset=math.pi / 4):
         """probs (B,2,h,w), deltas (B,14,h,w) fp32 device tensors -> ([boxes (n_i,7) f32 numpy], [scores (n_i,) f32 numpy])"""
-        boxes, scores, counts = self.decode_device(probs, deltas, score_thres, nms_thres, top_k, nms, pre_nms_top_k, layout)
+        boxes, scores, counts = self.decode_device(probs, deltas, score_thres, nms_thres, top_k, nms, pre_nms_top_k, layout,
+                                                   dir_logits, dir_offset)
         B = boxes.shape[0]
         cnt = counts.cpu().numpy()
         bh, sh = boxes.cpu().numpy(), scores.cpu().numpy()

@@ -64,9 +64,16 @@ def _limit_angle(angle):
     return np.pi / 2 if abs(angle + np.pi / 2) < 5 / 180 * np.pi else angle
 
 
-def label_to_gt_box_3d(labels, cls_name="Car", coordinate="lidar"):
+def _wrap_angle(angle):
+    """into (-pi, pi]: the heading kept (what _limit_angle folds away), as evaluate.py reads a label's rotation_y"""
+    return angle - 2.0 * np.pi * np.ceil((angle - np.pi) / (2.0 * np.pi))
+
+
+def label_to_gt_box_3d(labels, cls_name="Car", coordinate="lidar", keep_heading=False):
     """utils.py:178-210 (+ camera_to_lidar_box, :163-174): label lines of every sample -> list of (G_i, 7) float64
-    boxes (x, y, z, h, w, l, r), in lidar coordinates by the mean calibration unless coordinate == 'camera'."""
+    boxes (x, y, z, h, w, l, r), in lidar coordinates by the mean calibration unless coordinate == 'camera'.
+    keep_heading: r = -ry - pi/2 wrapped into (-pi, pi] instead of the reference's fold into [-pi/2, pi/2), which
+    forgets which way the object faces — what a direction head is supervised by."""
     accept = CLASS_CFG[cls_name]["accept"] if cls_name in CLASS_CFG else ()
     r_inv, t_inv = _R_RECT_0_INV, _T_VELO_2_CAM_INV
     out = []
@@ -79,7 +86,7 @@ def label_to_gt_box_3d(labels, cls_name="Car", coordinate="lidar"):
             h, w, l, x, y, z, ry = (float(v) for v in f[-7:])
             if coordinate == "lidar":
                 p = np.matmul(t_inv, np.matmul(r_inv, np.array([x, y, z, 1])))
-                rows.append([p[0], p[1], p[2], h, w, l, _limit_angle(-ry - np.pi / 2)])
+                rows.append([p[0], p[1], p[2], h, w, l, (_wrap_angle if keep_heading else _limit_angle)(-ry - np.pi / 2)])
             else:
                 rows.append([x, y, z, h, w, l, ry])
         out.append(np.array(rows, dtype=np.float64).reshape(-1, 7))
@@ -118,14 +125,17 @@ class TargetGenerator:
     (B,h,w,2), targets (B,h,w,14)) float32 tensors on `device`, the arrays of utils.generate_targets (utils.py:473).
     assign: "reference" — the reference's assignment (vn_rpn_targets); "standup" / "rotated" — by the IoU of the stand-up
     hulls / of the rotated footprints (vn_rpn_targets_iou), pos and neg then exclusive.  pos_iou /
-    neg_iou: the two thresholds (default: the class's)."""
+    neg_iou: the two thresholds (default: the class's).  keep_heading: label lines are parsed with their heading
+    (label_to_gt_box_3d), so that targets[..., 7a+6] + the anchor's yaw is the box's yaw and not its fold into [-pi/2, pi/2)."""
 
-    def __init__(self, cls_name="Car", device="cuda:0", anchors=None, assign="reference", pos_iou=None, neg_iou=None):
+    def __init__(self, cls_name="Car", device="cuda:0", anchors=None, assign="reference", pos_iou=None, neg_iou=None,
+                 keep_heading=False):
         if assign not in ASSIGN_KINDS:
             raise ValueError(f"assign must be one of {sorted(ASSIGN_KINDS)}, not {assign!r}")
         self.cls_name = cls_name
         self.cfg = CLASS_CFG[cls_name]
         self.assign = assign
+        self.keep_heading = bool(keep_heading)
         self.pos_iou = float(self.cfg["pos_iou"] if pos_iou is None else pos_iou)
         self.neg_iou = float(self.cfg["neg_iou"] if neg_iou is None else neg_iou)
         if np.isnan(self.pos_iou) or np.isnan(self.neg_iou):
@@ -226,7 +236,7 @@ class TargetGenerator:
             if hit is None:
                 if len(self._parsed) >= 8192:
                     self._parsed.clear()
-                hit = label_to_gt_box_3d([label], self.cls_name, coordinate)[0]
+                hit = label_to_gt_box_3d([label], self.cls_name, coordinate, self.keep_heading)[0]
                 hit.setflags(write=False)
                 self._parsed[key] = hit
             boxes.append(hit)
