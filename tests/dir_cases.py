@@ -75,6 +75,14 @@ def loss_case(shape, seed=23):
     if shape == LOSS_SHAPES[0]:
         pos[-1] = 0.0
     pos[0, 0, 0, :] = 1.0                                     # both rotations are among the positives
+    assert int(pos.sum()) >= len(HAND_LOGITS)
+    return _loss_inputs(pos, anchors, rng)
+
+
+def _loss_inputs(pos, anchors, rng, hand=HAND_LOGITS):
+    """targets and logits for the given positives: YAWS in turn as the matched headings, the `hand` logits at the first
+    positives in the logits' layout"""
+    B, h, w, _ = pos.shape
     targets = (rng.standard_normal((B, h, w, 14)) * 0.3).astype(np.float32)
     k = 0
     for idx in np.argwhere(pos != 0):
@@ -84,14 +92,34 @@ def loss_case(shape, seed=23):
     logits = (rng.standard_normal((B, 2, h * w)) * 2.0).astype(np.float32)
     logits[np.abs(logits) < 1e-2] = 0.5
     p = np.argwhere(R.site_layout(pos) != 0)
-    assert len(p) >= len(HAND_LOGITS)
-    for (b, a, s), z in zip(p, HAND_LOGITS):
+    for (b, a, s), z in zip(p, hand):
         logits[b, a, s] = z
     out = {"logits": logits, "pos": pos, "targets": targets, "anchors": anchors}
     for v in out.values():
         v.setflags(write=False)
-    out["n_exact_zero"] = 1
+    out["n_exact_zero"] = sum(z == 0.0 for z in hand[:len(p)])
     return out
+
+
+# The two loops of the loss' scaffold (csrc/rpn_common.h) that no LOSS_SHAPES entry reaches: tests/iou_loss_ref.py's
+# SEAM_CASES, shapes and planted flat elements of pos (2 * global site + rotation) alike; the reasons are stated there.
+SEAM_CASES = {
+    (1, 33, 63): (0, 4095, 4096, 4157),
+    (2, 129, 255): (0, 2 * 255, 2 * 256 + 1, 2 * 32894 + 1, 2 * 32895, 2 * 40000, 2 * 65535, 2 * 65536 + 1, 2 * 65789 + 1),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def seam_case(shape, seed=37):
+    """loss_case's dict for a SEAM_CASES shape: the positives exactly the planted elements; the Car anchors' two rotations
+    at every site (the loss reads the yaw column only; (2,129,255) is wider than the Car grid)"""
+    B, h, w = shape
+    rng = np.random.default_rng(seed + h * w)
+    anchors = np.ascontiguousarray(np.broadcast_to(ot.generate_anchors("Car")[:1, :1], (h, w, 2, 7)))
+    pos = np.zeros(B * h * w * 2, dtype=np.float32)
+    pos[list(SEAM_CASES[shape])] = 1.0
+    # HAND_LOGITS from its second entry: the four positives of (1,33,63) then hold the exact 0, and both offsets see hits and misses
+    return _loss_inputs(pos.reshape(B, h, w, 2), anchors, rng, HAND_LOGITS[1:])
 
 
 def rectify_case(seed=29):

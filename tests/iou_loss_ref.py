@@ -144,13 +144,18 @@ def small_anchors(H, W):
     return a
 
 
-def generic_inputs(B, H, W, seed, empty_last=False):
+def generic_inputs(B, H, W, seed, empty_last=False, flat=None):
     """-> delta (B,14,H,W), pos (B,H,W,2), targets (B,H,W,14) float32: pos Bernoulli 0.1, targets uniform in +-0.3, delta at
-    the positives = target + uniform +-0.2 (yaw +-0.5), randn * 0.2 elsewhere.  empty_last: no positive in the last sample"""
+    the positives = target + uniform +-0.2 (yaw +-0.5), randn * 0.2 elsewhere.  empty_last: no positive in the last sample;
+    flat: the positives are exactly these flat elements of pos (2 * global site + rotation) instead"""
     g = torch.Generator().manual_seed(seed)
     pos = (torch.rand((B, H, W, 2), generator=g) < 0.1).float()
     if empty_last:
         pos[-1] = 0
+    if flat is not None:
+        pos = torch.zeros(B * H * W * 2)
+        pos[list(flat)] = 1.0
+        pos = pos.view(B, H, W, 2)
     tgt = (torch.rand((B, H, W, 14), generator=g) * 0.6 - 0.3).float()
     noise = torch.rand((B, H, W, 14), generator=g) * 0.4 - 0.2
     noise[..., 6::7] = torch.rand((B, H, W, 2), generator=g) * 1.0 - 0.5
@@ -159,3 +164,24 @@ def generic_inputs(B, H, W, seed, empty_last=False):
     mask = pos.repeat_interleave(7, dim=3).permute(0, 3, 1, 2) != 0
     delta = torch.where(mask, near, far).float().contiguous()
     return delta, pos, tgt
+
+
+# The two loops of the site-term scaffold (csrc/rpn_common.h) that no shape of <= 768 sites reaches, as (B, H, W) -> the
+# flat elements of pos that are positive.
+# (1,33,63): 2,079 sites, 4,158 elements of pos > 16 x 256, so k_pos_norm's loop takes a second, partial sweep: elements
+#   4095 / 4096 are the last of the first sweep and the first of the second, 4157 the very last.  P_b = 4; 2 if the second
+#   sweep were dropped.
+# (2,129,255): 65,790 sites in 257 workgroups, so thread 0 of k_site_term_finalize adds slab rows 0 and 256.  Sites 32,894
+#   and 32,895 are the last of sample 0 and the first of sample 1 inside workgroup 128, which therefore sees two values of
+#   P_b (4 and 5); sites 255 / 256 and 65,535 / 65,536 straddle workgroups 0 / 1 and 255 / 256; 65,789 is the very last site.
+SEAM_CASES = {
+    (1, 33, 63): (0, 4095, 4096, 4157),
+    (2, 129, 255): (0, 2 * 255, 2 * 256 + 1, 2 * 32894 + 1, 2 * 32895, 2 * 40000, 2 * 65535, 2 * 65536 + 1, 2 * 65789 + 1),
+}
+
+
+def seam_inputs(shape):
+    """-> delta, pos, targets (generic_inputs' recipe, the positives exactly SEAM_CASES[shape]) and anchors (H*W*2, 7)"""
+    B, H, W = shape
+    delta, pos, tgt = generic_inputs(B, H, W, 31 + B, flat=SEAM_CASES[shape])
+    return delta, pos, tgt, torch.from_numpy(small_anchors(H, W).reshape(-1, 7).copy())

@@ -63,6 +63,33 @@ def test_loss_cases_hold_the_guard(shape, off):
         assert (z == np.float32(v)).any()
 
 
+@pytest.mark.parametrize("off", C.OFFSETS)
+@pytest.mark.parametrize("shape", list(C.SEAM_CASES))
+def test_seam_cases_hold_the_guard(shape, off):
+    """the inputs of tests/test_gpu_dir_head.py's seam test, on the reference alone: the positives are exactly where
+    dir_cases.SEAM_CASES says and reach the loops they are there for; the angles and logits keep the guard; the loss is
+    finite and not 0, with hits and misses"""
+    import iou_loss_ref
+    assert C.SEAM_CASES == iou_loss_ref.SEAM_CASES          # one set of planted positives for both terms
+    B, h, w = shape
+    flat = C.SEAM_CASES[shape]
+    c = C.seam_case(shape)
+    R.guard(c["logits"], c["pos"], c["targets"], c["anchors"], off, exact_zeros=c["n_exact_zero"])
+    assert sorted(np.flatnonzero(c["pos"].reshape(-1)).tolist()) == sorted(flat) and c["pos"].sum() == len(flat) <= 12
+    sites, per_b, last = B * h * w, h * w * 2, B * h * w * 2 - 1
+    assert {0, last} <= set(flat)
+    if B == 1:          # the normaliser's second sweep: elements at and beyond 16 x 256, fewer than another full sweep
+        assert 16 * 256 < per_b < 2 * 16 * 256 and {16 * 256 - 1, 16 * 256} <= set(flat)
+    else:               # a second slab row for finalize thread 0; a workgroup that holds the end of sample 0 and the start of sample 1
+        assert (sites + 255) // 256 == 257 and sum(f // 2 >= 256 * 256 for f in flat) >= 2
+        assert {2 * (h * w - 1) + 1, 2 * h * w} <= set(flat) and (h * w - 1) // 256 == (h * w) // 256
+        p_b = c["pos"].sum(axis=(1, 2, 3)).tolist()
+        assert p_b[0] != p_b[1] and min(p_b) >= 1
+    L, acc, grad, (hits, n) = R.loss(c["logits"], c["pos"], c["targets"], c["anchors"], off)
+    assert math.isfinite(L) and L > 0 and n == len(flat) and 0 < hits < n
+    assert np.isfinite(grad).all() and (grad[R.site_layout(c["pos"]) != 0] != 0).all()
+
+
 def test_rectify_case_holds_the_guard():
     c = C.rectify_case()
     B, K = c["idx"].shape

@@ -182,12 +182,8 @@ def _loss_call(c, off, with_grad):
     return out, d
 
 
-@pytest.mark.parametrize("off", C.OFFSETS, ids=["pi4", "zero"])
-@pytest.mark.parametrize("shape", C.LOSS_SHAPES, ids=lambda s: "x".join(str(v) for v in s))
-def test_loss_against_dir_ref(shape, off):
-    from voxelnet_amd import _lib
-    from voxelnet_amd.dir_head import rpn_dir_loss
-    c = C.loss_case(shape)
+def _check_loss(c, shape, off):
+    """the raw call, with and without the gradient, against dir_ref at the loss' bars -> (out2, d_logits, the non-positives)"""
     L, acc, grad, (hits, n) = R.loss(c["logits"], c["pos"], c["targets"], c["anchors"], off)
     out, d = _loss_call(c, off, True)
     fwd, _ = _loss_call(c, off, False)
@@ -202,6 +198,25 @@ def test_loss_against_dir_ref(shape, off):
     off_pos = _dev(R.site_layout(c["pos"]) == 0)
     assert bool((_bits(d)[off_pos] == 0).all())                                         # exactly +0.0 at every non-positive
     assert bool((d[~off_pos] != 0).all())
+    return out, d, off_pos
+
+
+@pytest.mark.parametrize("off", C.OFFSETS, ids=["pi4", "zero"])
+@pytest.mark.parametrize("shape", list(C.SEAM_CASES), ids=lambda s: "x".join(str(v) for v in s))
+def test_loss_seams_of_the_site_term_scaffold(shape, off):
+    """the two loops of csrc/rpn_common.h's scaffold that no LOSS_SHAPES entry reaches (dir_cases.SEAM_CASES, guarded on the
+    CPU by tests/test_dir_host.py): k_pos_norm's second sweep over a sample, and k_site_term_finalize's second slab row per
+    thread with a workgroup that straddles two samples.  test_loss_against_dir_ref's comparisons and bars."""
+    _check_loss(C.seam_case(shape), shape, off)
+
+
+@pytest.mark.parametrize("off", C.OFFSETS, ids=["pi4", "zero"])
+@pytest.mark.parametrize("shape", C.LOSS_SHAPES, ids=lambda s: "x".join(str(v) for v in s))
+def test_loss_against_dir_ref(shape, off):
+    from voxelnet_amd import _lib
+    from voxelnet_amd.dir_head import rpn_dir_loss
+    c = C.loss_case(shape)
+    out, d, off_pos = _check_loss(c, shape, off)
     # the autograd Function: the same scalars; the gradient scaled by the upstream one; acc carries none
     z = _dev(c["logits"]).requires_grad_(True)
     an = _dev(c["anchors"])

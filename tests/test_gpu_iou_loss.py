@@ -7,7 +7,8 @@ d_delta; see BARS below for the measured values.
 
 Shapes: the loss tests' own — (3,7,5) = 105 sites, one partial workgroup, no positive in the last sample (P_b clamps to 1);
 (2,16,24) = 768 sites, exactly three workgroups; (2,17,15) = 510 sites, two workgroups, the second partial, the sample
-boundary (site 255) inside the first.  Anchors: iou_loss_ref.small_anchors, a small Car-style grid."""
+boundary (site 255) inside the first; and the two seam shapes of iou_loss_ref.SEAM_CASES, (1,33,63) and (2,129,255), with
+a handful of planted positives.  Anchors: iou_loss_ref.small_anchors, a small Car-style grid."""
 import functools
 import math
 from dataclasses import replace
@@ -100,6 +101,43 @@ def test_scalars_and_gradient_against_the_reference(shape, combo):
         assert es <= BARS[0], (got, ref_loss, ref_iou)
         assert eg <= BARS[1]
         assert torch.isnan(dd[ins[0].numel():]).all() and bool((ws[-TAIL:] == 0xA5).all())
+
+
+@functools.lru_cache(maxsize=None)
+def _seam_reference(shape, kind, metric):
+    delta, pos, tgt, anchors = R.seam_inputs(shape)
+    d64 = delta.double().requires_grad_(True)
+    loss, mean_iou, pairs = R.loss(d64, pos, tgt, anchors, kind, metric)
+    loss.backward()
+    return loss.item(), mean_iou.item(), d64.grad, pairs
+
+
+@pytest.mark.parametrize("combo", [("iou", "bev"), ("diou", "3d")], ids=_ids)
+@pytest.mark.parametrize("shape", list(R.SEAM_CASES), ids=_ids)
+def test_seams_of_the_site_term_scaffold(shape, combo):
+    """the two loops of csrc/rpn_common.h's scaffold that no shape above reaches (iou_loss_ref.SEAM_CASES, guarded on the
+    CPU by tests/test_iou_loss_host.py): k_pos_norm's second sweep over a sample, and k_site_term_finalize's second slab row
+    per thread with a workgroup that straddles two samples.  Forward-only and forward + backward, the bars and the sentinel
+    tails of test_scalars_and_gradient_against_the_reference."""
+    kind, metric = combo
+    ins = _dev(R.seam_inputs(shape))
+    ref_loss, ref_iou, ref_grad, pairs = _seam_reference(shape, kind, metric)
+    assert len(pairs) == len(R.SEAM_CASES[shape]) and all(p[1] > 0.0 for p in pairs)
+    assert math.isfinite(ref_loss) and ref_grad.abs().max().item() > 0
+    n = ins[0].numel()
+    for forward_only in (True, False):
+        out, dd, ws = _launch(*ins, kind, metric, forward_only=forward_only)
+        torch.cuda.synchronize()
+        got = out.cpu().double().numpy()
+        es = max(abs(got[0] - ref_loss) / abs(ref_loss), abs(got[1] - ref_iou) / abs(ref_iou))
+        print(f"{shape} {kind} {metric} forward_only={forward_only}: scalars {es:.2e} (loss {got[0]:.7f} vs {ref_loss:.7f})")
+        assert torch.isfinite(out).all() and es <= BARS[0], (got, ref_loss, ref_iou)
+        assert bool((ws[-TAIL:] == 0xA5).all())
+        if not forward_only:
+            eg = (_grad_of(dd, ins[0]).cpu().double() - ref_grad).abs().max().item() / ref_grad.abs().max().item()
+            print(f"{shape} {kind} {metric}: gradient {eg:.2e} of the maximum")
+            assert torch.isfinite(dd[:n]).all() and eg <= BARS[1]
+            assert torch.isnan(dd[n:]).all()
 
 
 def _decode_np(d, A):

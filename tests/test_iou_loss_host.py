@@ -126,6 +126,32 @@ def test_reference_edge_rules():
     assert 0.1 < a.item() < 1.0 and abs(a.item() - b.item()) <= 1e-14
 
 
+@pytest.mark.parametrize("shape", list(R.SEAM_CASES), ids=lambda s: "x".join(str(v) for v in s))
+def test_seam_cases_hold_the_guard(shape):
+    """the inputs of tests/test_gpu_iou_loss.py's seam test, on the reference alone: the positives are exactly where
+    iou_loss_ref.SEAM_CASES says and reach the loops they are there for; every pair overlaps; the loss is finite and not 0"""
+    B, H, W = shape
+    flat = R.SEAM_CASES[shape]
+    delta, pos, tgt, anchors = R.seam_inputs(shape)
+    assert sorted(torch.nonzero(pos.reshape(-1)).reshape(-1).tolist()) == sorted(flat) and float(pos.sum()) == len(flat) <= 12
+    sites, per_b, last = B * H * W, H * W * 2, B * H * W * 2 - 1
+    assert {0, last} <= set(flat)
+    if B == 1:          # the normaliser's second sweep: elements at and beyond 16 x 256, fewer than another full sweep
+        assert 16 * 256 < per_b < 2 * 16 * 256 and {16 * 256 - 1, 16 * 256} <= set(flat)
+    else:               # a second slab row for finalize thread 0; a workgroup that holds the end of sample 0 and the start of sample 1
+        assert (sites + 255) // 256 == 257 and sum(f // 2 >= 256 * 256 for f in flat) >= 2
+        assert {2 * (H * W - 1) + 1, 2 * H * W} <= set(flat) and (H * W - 1) // 256 == (H * W) // 256
+        p_b = pos.sum(dim=(1, 2, 3)).tolist()
+        assert p_b[0] != p_b[1] and min(p_b) >= 1
+    for kind, metric in (("iou", "bev"), ("diou", "3d")):
+        d64 = delta.double().requires_grad_(True)
+        loss, mean_iou, pairs = R.loss(d64, pos, tgt, anchors, kind, metric)
+        loss.backward()
+        assert len(pairs) == len(flat) and all(p[1] > 0.0 for p in pairs)
+        assert math.isfinite(loss.item()) and loss.item() > 0 and 0 < mean_iou.item() < 1
+        assert torch.isfinite(d64.grad).all() and d64.grad.abs().max().item() > 0
+
+
 def test_header_declares_and_lib_binds_the_new_symbols():
     from voxelnet_amd import _lib
     lib = _lib.load()

@@ -7,7 +7,7 @@
 //                 (order-preserving map of the score's bits | flat index), slots handed out by an atomic.
 //   k_dt_select   one workgroup per sample: the pre_top_k-th largest key by radix passes (8 bits each, most significant
 //                 first) over an LDS histogram, compaction of the keys at or above it into LDS, a bitonic sort there
-//                 (<= 4096 x 8 B = 32 KB), then the decoding of the selected rows exactly as k_pr_select_nms decodes.
+//                 (<= 4096 x 8 B = 32 KB), then the decoding of the selected rows by the codec k_pr_select_nms uses (rpn_common.h).
 //                 The keys are unique, so neither the selected set nor its order depends on the atomics' order.
 //   k_dt_nms      one workgroup per sample, LAZY: the walk ends at <= 64 kept rows, so only <= 64 x K pairs are ever
 //                 evaluated (a K x K suppression matrix would be 8.4 M clippings at K = 4096).  Per kept row every
@@ -24,7 +24,7 @@
 // and deltas[b, 7a .. 7a+6, site], the layout the loss trains.  The index in the key, in sel_idx and into `anchors` is n.
 // Equal scores: the larger flat index first (predict.hip, oracle/predict.py); -0.0 and +0.0 are one score; a NaN score
 // fails `p >= thres` and is never a candidate.
-#include "common.h"
+#include "rpn_common.h"
 
 namespace {
 
@@ -171,7 +171,7 @@ __global__ void __launch_bounds__(DT_SEL_THREADS) k_dt_select(const float *__res
             __syncthreads();
         }
     }
-    // ---- decode the selected rows (utils.py:476-489), as k_pr_select_nms does
+    // ---- decode the selected rows (utils.py:476-489)
     for (int t = tid; t < n_sel; t += DT_SEL_THREADS) {
         const int j = (int)(uint32_t)(skey[t] & 0xffffffffull);
         if (j >= N) continue;
@@ -179,40 +179,16 @@ __global__ void __launch_bounds__(DT_SEL_THREADS) k_dt_select(const float *__res
         const int S = N >> 1;
         const size_t d0 = SITE ? (size_t)b * N * 7 + (size_t)(j & 1) * 7 * S + (j >> 1) : ((size_t)b * N + j) * 7;
         const size_t ds = SITE ? (size_t)S : 1;
-        float d[7];
+        float d[7], o[7];
 #pragma unroll
         for (int k = 0; k < 7; ++k) d[k] = deltas[d0 + k * ds];
-        const double *a = anchors + (size_t)j * 7;
-        const double diag = sqrt(a[4] * a[4] + a[5] * a[5]);
-        float *o = sel_boxes + ((size_t)b * pre_k + t) * 7;
-        o[0] = (float)((double)d[0] * diag + a[0]);
-        o[1] = (float)((double)d[1] * diag + a[1]);
-        o[2] = (float)((double)d[2] * anchor_h + a[2]);
-        o[3] = (float)((double)expf(d[3]) * a[3]);
-        o[4] = (float)((double)expf(d[4]) * a[4]);
-        o[5] = (float)((double)expf(d[5]) * a[5]);
-        o[6] = (float)((double)d[6] + a[6]);
+        vn_box_decode_f32(d, anchors + (size_t)j * 7, anchor_h, o);
+#pragma unroll
+        for (int k = 0; k < 7; ++k) sel_boxes[((size_t)b * pre_k + t) * 7 + k] = o[k];
         sel_scores[(size_t)b * pre_k + t] = probs[(size_t)b * N + (SITE ? (size_t)(j & 1) * S + (j >> 1) : (size_t)j)];
         sel_idx[(size_t)b * pre_k + t] = j;
     }
     if (tid == 0) sel_counts[b] = n_sel;
-}
-
-// stand-up rectangle of a float32 box (utils.py:230-252, 283-330), the arithmetic of k_pr_select_nms: float64 rotation,
-// float32 corners
-__device__ __forceinline__ void dt_standup(const float (&o)[7], float (&r)[4]) {
-    const double x = o[0], y = o[1], w = o[4], l = o[5], yaw = o[6];
-    const double c = cos(yaw), s = sin(yaw);
-    const double fx[4] = {-l / 2, -l / 2, l / 2, l / 2}, fy[4] = {w / 2, -w / 2, -w / 2, w / 2};
-    float x1 = INFINITY, y1 = INFINITY, x2 = -INFINITY, y2 = -INFINITY;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const float cx = (float)((c * fx[q] + (-s) * fy[q]) + x);
-        const float cy = (float)((s * fx[q] + c * fy[q]) + y);
-        x1 = fminf(x1, cx); x2 = fmaxf(x2, cx);
-        y1 = fminf(y1, cy); y2 = fmaxf(y2, cy);
-    }
-    r[0] = x1; r[1] = y1; r[2] = x2; r[3] = y2;
 }
 
 // the lowest alive row of the workgroup (DT_NONE: none).  Row q * DT_NMS_THREADS + tid is bit q of the thread's `alive`.
@@ -265,7 +241,7 @@ __global__ void __launch_bounds__(DT_NMS_THREADS) k_dt_nms(const float *__restri
             if (ok) alive |= 1u << q;
         } else {
             float r[4];
-            dt_standup(o, r);
+            vn_box_standup_f32(o, r);
 #pragma unroll
             for (int k = 0; k < 4; ++k) rc[(size_t)j * 4 + k] = r[k];          // read back by this thread only
             alive |= 1u << q;
@@ -289,7 +265,7 @@ __global__ void __launch_bounds__(DT_NMS_THREADS) k_dt_nms(const float *__restri
         if (MODE == VN_NMS_ROTATED) {
             xi = (double)sx[cur]; yi = (double)sy[cur]; hi = (double)shd[cur];
         } else {
-            dt_standup(oi, ri);
+            vn_box_standup_f32(oi, ri);
             ai = ((double)ri[2] - (double)ri[0]) * ((double)ri[3] - (double)ri[1]);
         }
 #pragma unroll 1

@@ -14,7 +14,7 @@
 // the backward compacts those rows in row order (common.h's ordered compaction) and touches nothing else.
 // Sums: per-workgroup partials over the list in list order, then one fixed-order pass: no atomics, bit-identical runs.
 #include <cmath>
-#include "common.h"
+#include "rpn_common.h"
 
 namespace {
 
@@ -25,7 +25,6 @@ constexpr int DH_ROWS_PER_HALF = DH_TILE / (DH_THREADS / 32);
 constexpr int DH_BWD_THREADS = 192;        // backward: 4 channels per thread
 constexpr int DH_BWD_MAX_WG = 256;         // workgroups (= partial rows) of the backward's pass over the list
 constexpr int DH_PART = 2 * DH_C + 2;      // one partial row: d_w[2][768], d_bias[2]
-constexpr int DH_NORM_CHUNKS = 16;         // workgroups per sample in the loss' normaliser pre-pass
 constexpr double DH_PI = 3.14159265358979323846;
 
 // The 24 channels of lane l (of 32) of a row, as NLOAD 16-byte loads of PER channels each: channel (j * 32 + l) * PER + e.
@@ -226,35 +225,8 @@ __global__ void __launch_bounds__(DH_THREADS) k_dir_bwd_final(const double *__re
         d_bias[o - 2 * DH_C] = (float)s;
 }
 
-// ---- loss ----
-// the sum of three doubles per thread over a 256-thread workgroup, fixed order; thread k < 3 returns sum k
-__device__ __forceinline__ double dh_block_sum3(double s0, double s1, double s2) {
-    __shared__ double red[3][DH_THREADS / 64];
-    double v[3] = {s0, s1, s2};
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o, 64);
-        if ((threadIdx.x & 63) == 0) red[k][threadIdx.x >> 6] = v[k];
-    }
-    __syncthreads();
-    double t = 0.0;
-    if (threadIdx.x < 3)
-        for (int w = 0; w < DH_THREADS / 64; ++w) t += red[threadIdx.x][w];
-    return t;
-}
-
-// part[b * DH_NORM_CHUNKS + chunk] = partial sum of pos[b]; the pass adds a sample's chunks in index order
-__global__ void __launch_bounds__(DH_THREADS) k_dir_norm(const float *__restrict__ pos, int64_t per_b, double *__restrict__ part) {
-    VN_PRIO_MAIN();
-    const int b = blockIdx.x / DH_NORM_CHUNKS, chunk = blockIdx.x % DH_NORM_CHUNKS;
-    double s = 0.0;
-    for (int64_t i = (int64_t)chunk * DH_THREADS + threadIdx.x; i < per_b; i += (int64_t)DH_NORM_CHUNKS * DH_THREADS)
-        s += (double)pos[(int64_t)b * per_b + i];
-    const double t = dh_block_sum3(s, 0.0, 0.0);
-    if (threadIdx.x == 0) part[blockIdx.x] = t;
-}
-
+// ---- loss: rpn_common.h's site-term scaffold around k_dir_loss ----
+static_assert(DH_THREADS == VN_SITE_THREADS, "k_dir_loss is launched with the scaffold's workgroup count");
 __device__ __forceinline__ int dh_bin(double theta, double off) { return (int)((long long)floor((theta - off) / DH_PI) & 1ll); }
 
 template <bool BWD>
@@ -278,9 +250,7 @@ __global__ void __launch_bounds__(DH_THREADS) k_dir_loss(const float *__restrict
                 const double z = (double)logits[((int64_t)b * 2 + a) * hw + yx];
                 const double theta = (double)tgt[site * 14 + a * 7 + 6] + anchors[(yx * 2 + a) * 7 + 6];
                 const int t = dh_bin(theta, off);
-                double pb = 0.0;
-                for (int c = 0; c < DH_NORM_CHUNKS; ++c) pb += part[(int64_t)b * DH_NORM_CHUNKS + c];
-                const double wgt = (double)m / fmax(pb, 1.0);
+                const double wgt = (double)m / fmax(vn_pos_total(part, b), 1.0);
                 s_loss += wgt * (fmax(z, 0.0) - z * (double)t + log1p(exp(-fabs(z))));
                 s_hit += ((z > 0.0) == (t == 1)) ? (double)m : 0.0;
                 s_m += (double)m;
@@ -289,23 +259,8 @@ __global__ void __launch_bounds__(DH_THREADS) k_dir_loss(const float *__restrict
             if (BWD) d_logits[((int64_t)b * 2 + a) * hw + yx] = out;
         }
     }
-    const double t = dh_block_sum3(s_loss, s_hit, s_m);
+    const double t = vn_block_sum3<DH_THREADS>(s_loss, s_hit, s_m);
     if (threadIdx.x < 3) slab[(int64_t)blockIdx.x * 3 + threadIdx.x] = t;
-}
-
-__global__ void __launch_bounds__(DH_THREADS) k_dir_loss_finalize(const double *__restrict__ slab, int nblocks, float *__restrict__ out2) {
-    VN_PRIO_MAIN();
-    double s[3] = {0.0, 0.0, 0.0};
-    for (int i = threadIdx.x; i < nblocks; i += DH_THREADS)
-        for (int k = 0; k < 3; ++k) s[k] += slab[(int64_t)i * 3 + k];
-    const double t = dh_block_sum3(s[0], s[1], s[2]);
-    __shared__ double tot[3];
-    if (threadIdx.x < 3) tot[threadIdx.x] = t;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        out2[0] = (float)tot[0];
-        out2[1] = (float)(tot[1] / fmax(tot[2], 1.0));
-    }
 }
 
 // ---- decode ----
@@ -331,7 +286,6 @@ bool dh_rows_ok(const void *p, int32_t dtype, int64_t stride) {
     return p && stride >= DH_C && stride % per16 == 0 && reinterpret_cast<uintptr_t>(p) % 16 == 0;
 }
 int dh_bwd_wgs(int64_t M) { return (int)(M < DH_BWD_MAX_WG ? M : DH_BWD_MAX_WG); }
-bool dh_map_ok(int32_t B, int32_t H, int32_t W) { return B > 0 && H > 0 && W > 0 && (int64_t)B * H * W < (1ll << 31); }
 
 }  // namespace
 
@@ -399,31 +353,28 @@ extern "C" int vn_dir_head_bwd(const float *d_logits, const void *cat_rows, int3
 }
 
 extern "C" size_t vn_rpn_dir_loss_workspace_bytes(int32_t B, int32_t H, int32_t W) {
-    if (!dh_map_ok(B, H, W)) return 0;
-    const int64_t blocks = vn_ceil_div((int64_t)B * H * W, DH_THREADS);
-    return vn_align(sizeof(double) * DH_NORM_CHUNKS * (size_t)B) + vn_align(sizeof(double) * 3 * (size_t)blocks);
+    return vn_site_map_ok(B, H, W) ? VnSiteTermWs(B, H, W).bytes() : 0;
 }
 
 extern "C" int vn_rpn_dir_loss(const float *logits, const float *pos, const float *targets, const double *anchors, int32_t B, int32_t H,
                                int32_t W, double dir_offset, void *workspace, size_t workspace_bytes, float *out2, float *d_logits,
                                vnStream stream) {
-    VN_CHECK_ARG(dh_map_ok(B, H, W));
+    VN_CHECK_ARG(vn_site_map_ok(B, H, W));
     VN_CHECK_ARG(std::isfinite(dir_offset));
     VN_CHECK_ARG(logits && pos && targets && anchors && workspace && out2);
-    if (workspace_bytes < vn_rpn_dir_loss_workspace_bytes(B, H, W)) return VN_EWORKSPACE;
+    const VnSiteTermWs ws(B, H, W);
+    if (workspace_bytes < ws.bytes()) return VN_EWORKSPACE;
     hipStream_t st = vn_stream(stream);
-    double *part = static_cast<double *>(workspace);
-    double *slab = reinterpret_cast<double *>(static_cast<char *>(workspace) + vn_align(sizeof(double) * DH_NORM_CHUNKS * (size_t)B));
+    double *part = ws.part(workspace), *slab = ws.slab(workspace);
     const int64_t hw = (int64_t)H * W;
-    const int blocks = (int)vn_ceil_div((int64_t)B * hw, DH_THREADS);
-    k_dir_norm<<<B * DH_NORM_CHUNKS, DH_THREADS, 0, st>>>(pos, hw * 2, part);
+    k_pos_norm<VN_SITE_THREADS><<<B * VN_POS_CHUNKS, VN_SITE_THREADS, 0, st>>>(pos, hw * 2, part);
     VN_LAUNCH_STATUS();
     if (d_logits)
-        k_dir_loss<true><<<blocks, DH_THREADS, 0, st>>>(logits, pos, targets, anchors, part, B, hw, dir_offset, slab, d_logits);
+        k_dir_loss<true><<<ws.blocks, DH_THREADS, 0, st>>>(logits, pos, targets, anchors, part, B, hw, dir_offset, slab, d_logits);
     else
-        k_dir_loss<false><<<blocks, DH_THREADS, 0, st>>>(logits, pos, targets, anchors, part, B, hw, dir_offset, slab, nullptr);
+        k_dir_loss<false><<<ws.blocks, DH_THREADS, 0, st>>>(logits, pos, targets, anchors, part, B, hw, dir_offset, slab, nullptr);
     VN_LAUNCH_STATUS();
-    k_dir_loss_finalize<<<1, DH_THREADS, 0, st>>>(slab, blocks, out2);
+    k_site_term_finalize<VN_SITE_THREADS><<<1, VN_SITE_THREADS, 0, st>>>(slab, ws.blocks, out2);
     VN_LAUNCH_STATUS();
     return VN_OK;
 }

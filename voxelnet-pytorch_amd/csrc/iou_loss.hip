@@ -16,45 +16,17 @@
 // dl += len / 2 on the two edges whose normal lies along the length axis, dw += len / 2 on the other two.  In P's own frame
 // the normals are the unit vectors and n.perp(mid) is E (1/2 - t_mid) on every edge (E: the edge's length).
 // Where IoU is not smooth (coincident edges, touching boxes, P == G) the clip picks one side; every term stays finite.
-// Sums: per-thread double -> per-workgroup slab rows -> one workgroup adds the rows in a fixed order (deterministic).
-#include "common.h"
+// Sums: per-thread double -> per-workgroup slab rows -> one workgroup adds the rows in a fixed order (deterministic); the
+// normaliser pre-pass, the workgroup sum, the final pass and the workspace carve are rpn_common.h's site-term scaffold.
+#include "rpn_common.h"
 
 namespace {
 
-constexpr int IOU_THREADS = 256;
-constexpr int IOU_NORM_CHUNKS = 16;   // workgroups per sample in the normaliser pre-pass
+constexpr int IOU_THREADS = VN_SITE_THREADS;
 
 struct IouGeom {
     int32_t B, H, W, kind, metric;
 };
-
-// the sum of three doubles per thread over a 256-thread workgroup, fixed order; thread k < 3 returns sum k
-__device__ __forceinline__ double iou_block_sum3(double s0, double s1, double s2) {
-    __shared__ double red[3][IOU_THREADS / 64];
-    double v[3] = {s0, s1, s2};
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o, 64);
-        if ((threadIdx.x & 63) == 0) red[k][threadIdx.x >> 6] = v[k];
-    }
-    __syncthreads();
-    double t = 0.0;
-    if (threadIdx.x < 3)
-        for (int w = 0; w < IOU_THREADS / 64; ++w) t += red[threadIdx.x][w];
-    return t;
-}
-
-// part[b*IOU_NORM_CHUNKS + chunk] = partial sum of pos[b]; the pass adds a sample's chunks in index order
-__global__ void __launch_bounds__(IOU_THREADS) k_iou_norm(const float *__restrict__ pos, int64_t per_b, double *__restrict__ part) {
-    VN_PRIO_MAIN();
-    const int b = blockIdx.x / IOU_NORM_CHUNKS, chunk = blockIdx.x % IOU_NORM_CHUNKS;
-    double s = 0.0;
-    for (int64_t i = (int64_t)chunk * IOU_THREADS + threadIdx.x; i < per_b; i += (int64_t)IOU_NORM_CHUNKS * IOU_THREADS)
-        s += (double)pos[(int64_t)b * per_b + i];
-    const double t = iou_block_sum3(s, 0.0, 0.0);
-    if (threadIdx.x == 0) part[blockIdx.x] = t;
-}
 
 // Liang-Barsky on one axis: the part of a + t d, t in [t0, t1], with |a + t d| <= h; t1 <= t0 afterwards when nothing is left
 __device__ __forceinline__ void clip_axis(double a, double d, double h, double &t0, double &t1) {
@@ -78,10 +50,9 @@ __device__ __forceinline__ void iou_pair_loss(const double (&dp)[7], const doubl
 #pragma unroll
     for (int k = 0; k < 7; ++k) grad[k] = 0.0;
     const double diag = sqrt(A[4] * A[4] + A[5] * A[5]);
-    const double P[7] = {dp[0] * diag + A[0], dp[1] * diag + A[1], dp[2] * A[3] + A[2], exp(dp[3]) * A[3], exp(dp[4]) * A[4],
-                         exp(dp[5]) * A[5], dp[6] + A[6]};
-    const double G[7] = {dg[0] * diag + A[0], dg[1] * diag + A[1], dg[2] * A[3] + A[2], exp(dg[3]) * A[3], exp(dg[4]) * A[4],
-                         exp(dg[5]) * A[5], dg[6] + A[6]};
+    double P[7], G[7];
+    vn_box_decode_f64(dp, A, diag, P);
+    vn_box_decode_f64(dg, A, diag, G);
     if (!(box_ok(P) && box_ok(G))) return;
     const double area_p = P[4] * P[5], area_g = G[4] * G[5];
     const double S = area_p + area_g, V = P[3] * area_p + G[3] * area_g;
@@ -252,9 +223,7 @@ __global__ void __launch_bounds__(IOU_THREADS) k_iou_loss(const float *__restric
                     A[j] = anchors[(yx * 2 + a) * 7 + j];
                 }
                 iou_pair_loss<BWD>(dp, dg, A, g.kind, g.metric, iou, L, grad);
-                double pb = 0.0;
-                for (int c = 0; c < IOU_NORM_CHUNKS; ++c) pb += part[(int64_t)b * IOU_NORM_CHUNKS + c];
-                const double wgt = (double)m / fmax(pb, 1.0);
+                const double wgt = (double)m / fmax(vn_pos_total(part, b), 1.0);
                 s_loss += wgt * L;
                 s_iou += (double)m * iou;
                 s_m += (double)m;
@@ -270,56 +239,36 @@ __global__ void __launch_bounds__(IOU_THREADS) k_iou_loss(const float *__restric
             }
         }
     }
-    const double t = iou_block_sum3(s_loss, s_iou, s_m);
+    const double t = vn_block_sum3<IOU_THREADS>(s_loss, s_iou, s_m);
     if (threadIdx.x < 3) slab[(int64_t)blockIdx.x * 3 + threadIdx.x] = t;
 }
-
-__global__ void __launch_bounds__(IOU_THREADS) k_iou_finalize(const double *__restrict__ slab, int nblocks, float *__restrict__ out2) {
-    VN_PRIO_MAIN();
-    double s[3] = {0.0, 0.0, 0.0};
-    for (int i = threadIdx.x; i < nblocks; i += IOU_THREADS)
-        for (int k = 0; k < 3; ++k) s[k] += slab[(int64_t)i * 3 + k];
-    const double t = iou_block_sum3(s[0], s[1], s[2]);
-    __shared__ double tot[3];
-    if (threadIdx.x < 3) tot[threadIdx.x] = t;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        out2[0] = (float)tot[0];
-        out2[1] = (float)(tot[1] / fmax(tot[2], 1.0));
-    }
-}
-
-bool iou_sizes_ok(int32_t B, int32_t H, int32_t W) { return B > 0 && H > 0 && W > 0 && (int64_t)B * H * W < (1ll << 31); }
 
 }  // namespace
 
 extern "C" size_t vn_rpn_iou_loss_workspace_bytes(int32_t B, int32_t H, int32_t W) {
-    if (!iou_sizes_ok(B, H, W)) return 0;
-    const int64_t blocks = vn_ceil_div((int64_t)B * H * W, IOU_THREADS);
-    return vn_align(sizeof(double) * IOU_NORM_CHUNKS * (size_t)B) + vn_align(sizeof(double) * 3 * (size_t)blocks);
+    return vn_site_map_ok(B, H, W) ? VnSiteTermWs(B, H, W).bytes() : 0;
 }
 
 extern "C" int vn_rpn_iou_loss(const float *delta, const float *pos, const float *targets, const double *anchors, int32_t B,
                                int32_t H, int32_t W, int32_t kind, int32_t metric, const float *g, void *workspace,
                                size_t workspace_bytes, float *out2, float *d_delta, vnStream stream) {
-    VN_CHECK_ARG(iou_sizes_ok(B, H, W));
+    VN_CHECK_ARG(vn_site_map_ok(B, H, W));
     VN_CHECK_ARG(kind == VN_IOU_LOSS_IOU || kind == VN_IOU_LOSS_DIOU);
     VN_CHECK_ARG(metric == VN_IOU_BEV || metric == VN_IOU_3D);
     VN_CHECK_ARG(delta && pos && targets && anchors && workspace && out2);
-    if (workspace_bytes < vn_rpn_iou_loss_workspace_bytes(B, H, W)) return VN_EWORKSPACE;
+    const VnSiteTermWs ws(B, H, W);
+    if (workspace_bytes < ws.bytes()) return VN_EWORKSPACE;
     hipStream_t st = vn_stream(stream);
-    double *part = static_cast<double *>(workspace);
-    double *slab = reinterpret_cast<double *>(static_cast<char *>(workspace) + vn_align(sizeof(double) * IOU_NORM_CHUNKS * (size_t)B));
-    const int blocks = (int)vn_ceil_div((int64_t)B * H * W, IOU_THREADS);
-    k_iou_norm<<<B * IOU_NORM_CHUNKS, IOU_THREADS, 0, st>>>(pos, (int64_t)H * W * 2, part);
+    double *part = ws.part(workspace), *slab = ws.slab(workspace);
+    k_pos_norm<VN_SITE_THREADS><<<B * VN_POS_CHUNKS, VN_SITE_THREADS, 0, st>>>(pos, (int64_t)H * W * 2, part);
     VN_LAUNCH_STATUS();
     const IouGeom geom{B, H, W, kind, metric};
     if (d_delta)
-        k_iou_loss<true><<<blocks, IOU_THREADS, 0, st>>>(delta, pos, targets, anchors, part, geom, g, slab, d_delta);
+        k_iou_loss<true><<<ws.blocks, IOU_THREADS, 0, st>>>(delta, pos, targets, anchors, part, geom, g, slab, d_delta);
     else
-        k_iou_loss<false><<<blocks, IOU_THREADS, 0, st>>>(delta, pos, targets, anchors, part, geom, g, slab, nullptr);
+        k_iou_loss<false><<<ws.blocks, IOU_THREADS, 0, st>>>(delta, pos, targets, anchors, part, geom, g, slab, nullptr);
     VN_LAUNCH_STATUS();
-    k_iou_finalize<<<1, IOU_THREADS, 0, st>>>(slab, blocks, out2);
+    k_site_term_finalize<VN_SITE_THREADS><<<1, VN_SITE_THREADS, 0, st>>>(slab, ws.blocks, out2);
     VN_LAUNCH_STATUS();
     return VN_OK;
 }

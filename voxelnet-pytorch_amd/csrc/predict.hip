@@ -9,7 +9,7 @@
 // arithmetic with a float32 exp; float32 corners, float64 stand-up rectangles; areas without "+1"; `IoU <= overlap`
 // keeps (a NaN IoU suppresses).  Equal scores: the larger flat index first (the reference's unstable sort leaves
 // that order open).
-#include "common.h"
+#include "rpn_common.h"
 
 namespace {
 
@@ -78,29 +78,13 @@ __global__ void __launch_bounds__(PR_THREADS) k_pr_select_nms(const float *__res
     // ---- decode the selected boxes (utils.py:476-489) and their stand-up rectangles (utils.py:230-252, 283-330)
     if ((int)threadIdx.x < n_sel) {
         const int j = sel_i[threadIdx.x];
-        const float *d = deltas + ((size_t)b * N + j) * 7;
-        const double *a = anchors + (size_t)j * 7;
-        const double diag = sqrt(a[4] * a[4] + a[5] * a[5]);
-        float *o = box[threadIdx.x];
-        o[0] = (float)((double)d[0] * diag + a[0]);
-        o[1] = (float)((double)d[1] * diag + a[1]);
-        o[2] = (float)((double)d[2] * anchor_h + a[2]);
-        o[3] = (float)((double)expf(d[3]) * a[3]);
-        o[4] = (float)((double)expf(d[4]) * a[4]);
-        o[5] = (float)((double)expf(d[5]) * a[5]);
-        o[6] = (float)((double)d[6] + a[6]);
-        const double x = o[0], y = o[1], w = o[4], l = o[5], yaw = o[6];
-        const double c = cos(yaw), s = sin(yaw);
-        const double fx[4] = {-l / 2, -l / 2, l / 2, l / 2}, fy[4] = {w / 2, -w / 2, -w / 2, w / 2};
-        float x1 = INFINITY, y1 = INFINITY, x2 = -INFINITY, y2 = -INFINITY;
+        float d[7], r[4];
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const float cx = (float)((c * fx[q] + (-s) * fy[q]) + x);      // np.dot row, then + translation; float32 store
-            const float cy = (float)((s * fx[q] + c * fy[q]) + y);
-            x1 = fminf(x1, cx); x2 = fmaxf(x2, cx);
-            y1 = fminf(y1, cy); y2 = fmaxf(y2, cy);
-        }
-        rect[threadIdx.x][0] = x1; rect[threadIdx.x][1] = y1; rect[threadIdx.x][2] = x2; rect[threadIdx.x][3] = y2;
+        for (int k = 0; k < 7; ++k) d[k] = deltas[((size_t)b * N + j) * 7 + k];
+        vn_box_decode_f32(d, anchors + (size_t)j * 7, anchor_h, box[threadIdx.x]);
+        vn_box_standup_f32(box[threadIdx.x], r);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) rect[threadIdx.x][k] = r[k];
     }
     __syncthreads();
     // ---- greedy NMS over the <= top_k boxes in descending key order (utils.py:519-551)

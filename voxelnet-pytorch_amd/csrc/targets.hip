@@ -15,7 +15,7 @@
 // Three launches: per-workgroup argmax partials (value, first index) -> per-box argmax (fixed order) -> per-anchor
 // classification and encoding (the IoUs are recomputed: G*12 flops per anchor, cheaper than storing them).
 // HBM-bound and tiny: 56 B read + 36 B written per anchor.
-#include "common.h"
+#include "rpn_common.h"
 
 namespace {
 
@@ -140,17 +140,8 @@ __global__ void __launch_bounds__(TG_THREADS) k_tg_encode(const double *__restri
     pos[o] = box >= 0 ? 1.f : 0.f;
     neg[o] = all_neg ? 1.f : 0.f;
     float t[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (box >= 0) {
-        const double *g = gt + ((size_t)b * max_gt + box) * 7;
-        const double diag = sqrt(a[4] * a[4] + a[5] * a[5]);      // utils.py:390-392
-        t[0] = (float)((g[0] - a[0]) / diag);
-        t[1] = (float)((g[1] - a[1]) / diag);
-        t[2] = (float)((g[2] - a[2]) / anchor_h);
-        t[3] = (float)log(g[3] / a[3]);
-        t[4] = (float)log(g[4] / a[4]);
-        t[5] = (float)log(g[5] / a[5]);
-        t[6] = (float)(g[6] - a[6]);
-    }
+    if (box >= 0)
+        vn_box_encode(gt + ((size_t)b * max_gt + box) * 7, a, anchor_h, t);
 #pragma unroll
     for (int j = 0; j < 7; ++j) targets[o * 7 + j] = t[j];
 }

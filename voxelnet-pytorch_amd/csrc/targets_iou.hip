@@ -20,8 +20,8 @@
 //   Rotated kind: a pair whose centres are further apart than the two half-diagonals together has disjoint footprints, the
 //   pair function returns exactly 0 for it, and it is skipped without clipping (k_dt_nms's reject): ~1,000 of the 70,400
 //   anchors reach the float64 clipping per box.
-//   k_ti_encode         matched, pos, neg and the seven regression targets (k_tg_encode's expressions) of every anchor.
-#include "common.h"
+//   k_ti_encode         matched, pos, neg and the seven regression targets (rpn_common.h's vn_box_encode, as k_tg_encode) of every anchor.
+#include "rpn_common.h"
 
 namespace {
 
@@ -154,18 +154,8 @@ __global__ void __launch_bounds__(TI_THREADS) k_ti_encode(const double *__restri
     neg[o] = (box < 0 && (G == 0 || m < neg_iou)) ? 1.f : 0.f;
     if (matched) matched[o] = box;
     float t[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (box >= 0) {
-        const double *a = anchors + (size_t)n * 7;
-        const double *g = gt + ((size_t)b * max_gt + box) * 7;
-        const double diag = sqrt(a[4] * a[4] + a[5] * a[5]);      // utils.py:390-392, as k_tg_encode
-        t[0] = (float)((g[0] - a[0]) / diag);
-        t[1] = (float)((g[1] - a[1]) / diag);
-        t[2] = (float)((g[2] - a[2]) / anchor_h);
-        t[3] = (float)log(g[3] / a[3]);
-        t[4] = (float)log(g[4] / a[4]);
-        t[5] = (float)log(g[5] / a[5]);
-        t[6] = (float)(g[6] - a[6]);
-    }
+    if (box >= 0)
+        vn_box_encode(gt + ((size_t)b * max_gt + box) * 7, anchors + (size_t)n * 7, anchor_h, t);
 #pragma unroll
     for (int j = 0; j < 7; ++j) targets[o * 7 + j] = t[j];
 }

@@ -7,6 +7,7 @@ import math
 import torch
 
 from . import _lib
+from ._site_term import SiteTermFn, check_site_maps
 
 C_CAT = 768
 DIR_OFFSET = math.pi / 4
@@ -102,55 +103,28 @@ def dir_head_backward(d_logits, cat_rows, weight, d_cat):
     return d_w, d_b
 
 
-class _DirLossFn(torch.autograd.Function):
-    """vn_rpn_dir_loss -> (loss, acc).  The forward launch writes d_logits for an upstream gradient of 1 and keeps it;
-    backward multiplies it by the upstream scalar (0 stays +0: what vn_dir_head_bwd skips).  acc has no gradient."""
-
-    @staticmethod
-    def forward(ctx, logits, pos, tgt, anchors, H, W, dir_offset):
-        B = logits.shape[0]
-        z = logits.detach().contiguous().float()
-        need = ctx.needs_input_grad[0]
-        with _lib.on_device(z.device):
-            ws_bytes = _lib.load().vn_rpn_dir_loss_workspace_bytes(B, H, W)
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=z.device)
-            out = torch.empty(2, dtype=torch.float32, device=z.device)
-            d_logits = torch.empty_like(z) if need else None
-            _lib.call("vn_rpn_dir_loss", z.data_ptr(), pos.data_ptr(), tgt.data_ptr(), anchors.data_ptr(), B, H, W, float(dir_offset),
-                      ws.data_ptr(), ws_bytes, out.data_ptr(), d_logits.data_ptr() if need else None, _lib.raw_stream())
-        ctx.d_logits, ctx.dtype, ctx.shape = d_logits, logits.dtype, logits.shape
-        ctx.set_materialize_grads(False)
-        loss, acc = out[0], out[1]
-        ctx.mark_non_differentiable(acc)
-        return loss, acc
-
-    @staticmethod
-    def backward(ctx, g_loss, _g_acc):
-        if g_loss is None or ctx.d_logits is None:
-            return None, None, None, None, None, None, None
-        return (ctx.d_logits * g_loss.float()).to(ctx.dtype).view(ctx.shape), None, None, None, None, None, None
-
-
 def rpn_dir_loss(dir_logits, pos, targets, anchors, dir_offset=DIR_OFFSET):
     """dir_logits (B,2,H*W) or (B,2,H,W) — the head's output —, pos (B,H,W,2), targets (B,H,W,14) fp32 and anchors (H*W*2, 7)
     or (H,W,2,7) float64, all HIP tensors -> (loss, acc) device scalars: include/voxelnet_hip.h, vn_rpn_dir_loss.  loss
-    carries the gradient to dir_logits; acc — the share of positives whose logit names the right bin — is a diagnostic."""
+    carries the gradient to dir_logits (_site_term.SiteTermFn; a gradient of 0 stays +0: what vn_dir_head_bwd skips); acc — the
+    share of positives whose logit names the right bin — is a diagnostic."""
     check_spec(0.0, dir_offset)
     _need_hip("rpn_dir_loss", dir_logits=dir_logits, pos=pos, targets=targets, anchors=anchors)
     if pos.dim() != 4 or pos.shape[3] != 2:
         raise ValueError(f"rpn_dir_loss: pos {tuple(pos.shape)} is not (B,H,W,2)")
     B, H, W, _ = pos.shape
-    if (dir_logits.dim() not in (3, 4) or dir_logits.shape[:2] != (B, 2) or dir_logits[0, 0].numel() != H * W
-            or tuple(targets.shape) != (B, H, W, 14) or anchors.numel() != H * W * 14):
-        raise ValueError(f"rpn_dir_loss: shapes {tuple(dir_logits.shape)} {tuple(pos.shape)} {tuple(targets.shape)} "
-                         f"{tuple(anchors.shape)} do not belong together")
-    if anchors.dtype != torch.float64 or pos.dtype != torch.float32 or targets.dtype != torch.float32:
-        raise ValueError("rpn_dir_loss: pos and targets must be float32, anchors float64")
+    x_ok = dir_logits.dim() in (3, 4) and dir_logits.shape[:2] == (B, 2) and dir_logits[0, 0].numel() == H * W
+    check_site_maps("rpn_dir_loss", dir_logits, x_ok, pos, targets, anchors, B, H, W)
     if not dir_logits.is_floating_point():
         raise ValueError(f"rpn_dir_loss: dir_logits must be a floating-point tensor, not {dir_logits.dtype}")
-    if not (pos.device == targets.device == anchors.device == dir_logits.device):
-        raise ValueError("rpn_dir_loss: the four tensors must live on one device")
-    return _DirLossFn.apply(dir_logits, pos.contiguous(), targets.contiguous(), anchors.contiguous(), H, W, float(dir_offset))
+    pos, targets, anchors = pos.contiguous(), targets.contiguous(), anchors.contiguous()
+
+    def launch(z, out2, d_logits):
+        ws_bytes = _lib.load().vn_rpn_dir_loss_workspace_bytes(B, H, W)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=z.device)
+        _lib.call("vn_rpn_dir_loss", z.data_ptr(), pos.data_ptr(), targets.data_ptr(), anchors.data_ptr(), B, H, W, float(dir_offset),
+                  ws.data_ptr(), ws_bytes, out2.data_ptr(), None if d_logits is None else d_logits.data_ptr(), _lib.raw_stream())
+    return SiteTermFn.apply(dir_logits, launch)
 
 
 def rectify_yaw(boxes, idx, counts, dir_logits, n_anchors, dir_offset=DIR_OFFSET):

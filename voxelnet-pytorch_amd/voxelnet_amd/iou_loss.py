@@ -6,6 +6,7 @@ import math
 import torch
 
 from . import _lib
+from ._site_term import SiteTermFn, check_site_maps
 
 KINDS = {"iou": _lib.VN_IOU_LOSS_IOU, "diou": _lib.VN_IOU_LOSS_DIOU}
 METRICS = {"bev": _lib.VN_IOU_BEV, "3d": _lib.VN_IOU_3D}
@@ -28,39 +29,11 @@ def check_spec(kind, metric="3d", weight=1.0):
         raise ValueError(f"iou_weight must be a finite number, not {weight!r}")
 
 
-class _IouLossFn(torch.autograd.Function):
-    """vn_rpn_iou_loss -> (loss, mean_iou).  The forward launch writes d_delta for an upstream gradient of 1 and keeps it;
-    backward multiplies it by the upstream scalar.  mean_iou is a diagnostic without a gradient."""
-
-    @staticmethod
-    def forward(ctx, delta, pos, tgt, anchors, kind, metric):
-        B, C, H, W = delta.shape
-        d32 = delta.detach().contiguous().float()
-        need = ctx.needs_input_grad[0]
-        with _lib.on_device(d32.device):
-            ws_bytes = _lib.load().vn_rpn_iou_loss_workspace_bytes(B, H, W)
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=d32.device)
-            out = torch.empty(2, dtype=torch.float32, device=d32.device)
-            d_delta = torch.empty_like(d32) if need else None
-            _lib.call("vn_rpn_iou_loss", d32.data_ptr(), pos.data_ptr(), tgt.data_ptr(), anchors.data_ptr(), B, H, W, kind, metric,
-                      None, ws.data_ptr(), ws_bytes, out.data_ptr(), d_delta.data_ptr() if need else None, _lib.raw_stream())
-        ctx.d_delta, ctx.dtype = d_delta, delta.dtype
-        ctx.set_materialize_grads(False)
-        loss, mean_iou = out[0], out[1]          # (views of one buffer, as _LossFn's five)
-        ctx.mark_non_differentiable(mean_iou)
-        return loss, mean_iou
-
-    @staticmethod
-    def backward(ctx, g_loss, _g_iou):
-        if g_loss is None or ctx.d_delta is None:
-            return None, None, None, None, None, None
-        return (ctx.d_delta * g_loss.float()).to(ctx.dtype), None, None, None, None, None
-
-
 def rpn_iou_loss(delta, pos, targets, anchors, kind="iou", metric="3d"):
     """delta (B,14,H,W) — the module's regression output —, pos (B,H,W,2), targets (B,H,W,14) fp32 and anchors (H*W*2, 7)
     or (H,W,2,7) float64, all HIP tensors -> (loss, mean_iou) device scalars: include/voxelnet_hip.h, vn_rpn_iou_loss.
-    loss carries the gradient to delta; mean_iou — the positives' mean IoU — is a diagnostic."""
+    loss carries the gradient to delta (the launch writes it for an upstream gradient of 1, _site_term.SiteTermFn scales it);
+    mean_iou — the positives' mean IoU — is a diagnostic without one."""
     check_spec(kind, metric)
     for name, t in (("delta", delta), ("pos", pos), ("targets", targets), ("anchors", anchors)):
         if not (torch.is_tensor(t) and t.is_cuda):
@@ -68,11 +41,13 @@ def rpn_iou_loss(delta, pos, targets, anchors, kind="iou", metric="3d"):
     if delta.dim() != 4 or delta.shape[1] != 14:
         raise ValueError(f"rpn_iou_loss: delta {tuple(delta.shape)} is not (B,14,H,W)")
     B, _, H, W = delta.shape
-    if tuple(pos.shape) != (B, H, W, 2) or tuple(targets.shape) != (B, H, W, 14) or anchors.numel() != H * W * 14:
-        raise ValueError(f"rpn_iou_loss: shapes {tuple(delta.shape)} {tuple(pos.shape)} {tuple(targets.shape)} "
-                         f"{tuple(anchors.shape)} do not belong together")
-    if anchors.dtype != torch.float64 or pos.dtype != torch.float32 or targets.dtype != torch.float32:
-        raise ValueError("rpn_iou_loss: pos and targets must be float32, anchors float64")
-    if not (pos.device == targets.device == anchors.device == delta.device):
-        raise ValueError("rpn_iou_loss: the four tensors must live on one device")
-    return _IouLossFn.apply(delta, pos.contiguous(), targets.contiguous(), anchors.contiguous(), KINDS[kind], METRICS[metric])
+    check_site_maps("rpn_iou_loss", delta, True, pos, targets, anchors, B, H, W)
+    pos, targets, anchors = pos.contiguous(), targets.contiguous(), anchors.contiguous()
+
+    def launch(d32, out2, d_delta):
+        ws_bytes = _lib.load().vn_rpn_iou_loss_workspace_bytes(B, H, W)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=d32.device)
+        _lib.call("vn_rpn_iou_loss", d32.data_ptr(), pos.data_ptr(), targets.data_ptr(), anchors.data_ptr(), B, H, W, KINDS[kind],
+                  METRICS[metric], None, ws.data_ptr(), ws_bytes, out2.data_ptr(), None if d_delta is None else d_delta.data_ptr(),
+                  _lib.raw_stream())
+    return SiteTermFn.apply(delta, launch)
