@@ -373,33 +373,46 @@ def relu_like(shape, seed, channel_axis):
     return torch.from_numpy((v * sc.reshape(bshape)).astype(np.float32))
 
 
-def run_rulebook_first_layer(mode):
+def run_rulebook_first_layer(mode, B=2, D=10, H=134, W=140, coord=None, seed=8101, perm=None, dense_oracle=True):
     """middle_layer.0 as the executor runs it (csrc/runtime.hip net_prepare + vn_net_forward, layer 0) in `mode`
     ("bf16": bf16 voxel rows and weights, bf16 y; "fp32" / "fp32x3" with engine.X3 set by the caller: fp32 operands that
     are not bf16-representable, the P GEMM with VN_F32 / VN_F32X3 operands, y in fp32) -> the kernel's y and statistics
-    slab and the float64 oracle (conv3d of the scattered grid) on the same operands"""
+    slab and the float64 oracle (conv3d of the scattered grid) on the same operands.
+    coord: (K,4) int64 [b,z,y,x] voxel cells of the B x D x H x W grid (default: 3000 seeded random cells, sorted); the
+    operands are seeded from seed + 1 .. seed + 3.  perm: the same voxels and rows handed to the kernels in that order
+    (tests/test_gpu_sparse_first_layer.py: the result may not depend on it).  dense_oracle=False: no float64 conv3d (a
+    grid too large for it on the CPU; "y64" / "dense" are None)."""
     from voxelnet_amd import _lib, engine as E
     from voxelnet_amd.net import layer_table
     dev = torch.device(DEV)
     lib = _lib.load()
     spec = dict(layer_table(2))["middle_layer.0"]
-    B, D, H, W, K = 2, 10, 134, 140, 3000
-    rng = np.random.default_rng(8101)
-    cells = rng.choice(B * D * H * W, size=K, replace=False)
-    cells.sort()
-    coord = torch.from_numpy(np.stack([cells // (D * H * W), (cells // (H * W)) % D, (cells // W) % H, cells % W], 1).astype(np.int64))
-    if mode == "bf16":
-        vw = bf16r(seeded((K, 128), 8102))
-        w = bf16r(tr._fill((64, 128, 3, 3, 3), 8103, 1.0 / np.sqrt(128 * 27)))
+    if coord is None:
+        K = 3000
+        rng = np.random.default_rng(seed)
+        cells = rng.choice(B * D * H * W, size=K, replace=False)
+        cells.sort()
+        coord = torch.from_numpy(np.stack([cells // (D * H * W), (cells // (H * W)) % D, (cells // W) % H, cells % W], 1).astype(np.int64))
     else:
-        vw = relu_like((K, 128), 8102, 1)
-        w = tr._fill((64, 128, 3, 3, 3), 8103, 1.0 / np.sqrt(128 * 27))
-    bias = tr._fill((64,), 8104, 0.1)
+        coord = torch.as_tensor(np.array(coord), dtype=torch.int64).reshape(-1, 4)
+        K = coord.shape[0]
+    if mode == "bf16":
+        vw = bf16r(seeded((K, 128), seed + 1))
+        w = bf16r(tr._fill((64, 128, 3, 3, 3), seed + 2, 1.0 / np.sqrt(128 * 27)))
+    else:
+        vw = relu_like((K, 128), seed + 1, 1)
+        w = tr._fill((64, 128, 3, 3, 3), seed + 2, 1.0 / np.sqrt(128 * 27))
+    bias = tr._fill((64,), seed + 3, 0.1)
     od = spec.out_dims((D, H, W))
-    dense = torch.zeros((B, D, H, W, 128), dtype=torch.float64)
-    dense[coord[:, 0], coord[:, 1], coord[:, 2], coord[:, 3]] = vw.double()
-    dense = dense.permute(0, 4, 1, 2, 3)
-    y64 = F.conv3d(dense, w.double(), bias.double(), spec.stride, spec.pad)
+    dense = y64 = None
+    if dense_oracle:
+        dense = torch.zeros((B, D, H, W, 128), dtype=torch.float64)
+        dense[coord[:, 0], coord[:, 1], coord[:, 2], coord[:, 3]] = vw.double()
+        dense = dense.permute(0, 4, 1, 2, 3)
+        y64 = F.conv3d(dense, w.double(), bias.double(), spec.stride, spec.pad)
+    if perm is not None:
+        perm = torch.as_tensor(np.asarray(perm), dtype=torch.int64)
+        coord, vw = coord[perm].contiguous(), vw[perm].contiguous()
     # --- the executor's call sequence (csrc/runtime.hip net_prepare + vn_net_forward, layer 0)
     vdt = _lib.VN_BF16 if mode == "bf16" else _lib.VN_F32
     odt = E.VN_F32X3 if (mode != "bf16" and E.X3["on"]) else vdt        # operand dtype of the P GEMM
@@ -422,7 +435,7 @@ def run_rulebook_first_layer(mode):
     g.divD = g.divH = g.divW = 1
     g.src_sW = 128; g.src_sH = W * 128; g.src_sD = H * W * 128; g.src_sB = D * H * W * 128
     g.out_sB, g.out_sD, g.out_sH, g.out_sW = y.strides
-    cap = min(M, K * 2 * 3 * 3)
+    cap = max(1, min(M, K * 2 * 3 * 3))                                   # (K = 0: a list of one unused row, as the engine sizes it)
     aws_bytes = lib.vn_active_sites_workspace_bytes(ctypes.byref(g))
     aws = torch.empty(aws_bytes, dtype=torch.uint8, device=dev)
     alist = torch.empty((cap, 4), dtype=torch.int64, device=dev)
@@ -431,7 +444,7 @@ def run_rulebook_first_layer(mode):
               acount.data_ptr(), E.stream())
     igrid = torch.empty(B * D * H * W, dtype=torch.int32, device=dev)
     _lib.call("vn_voxel_index_grid", coord_d.data_ptr(), K, B, D, H, W, igrid.data_ptr(), E.stream())
-    rbP = torch.empty((K, 27 * 64), dtype=torch.float32, device=dev)
+    rbP = torch.empty((max(K, 1), 27 * 64), dtype=torch.float32, device=dev)
     q = _lib.VnConv()
     q.dtype = odt
     q.B = 1
@@ -444,24 +457,29 @@ def run_rulebook_first_layer(mode):
     q.divD = q.divH = q.divW = 1
     q.src_sB = q.src_sD = q.src_sH = K * 128; q.src_sW = 128
     q.out_sB = q.out_sD = q.out_sH = K * 27 * 64; q.out_sW = 27 * 64
-    gemm_plan = lib.vn_conv_plan_id(ctypes.byref(q))
-    _lib.call("vn_conv_gather_gemm", vw_d.data_ptr(), wp.data_ptr(), None, rbP.data_ptr(), _lib.VN_F32, ctypes.byref(q), 0,
-              None, E.stream())
+    gemm_plan = lib.vn_conv_plan_id(ctypes.byref(q)) if K > 0 else None
+    if K > 0:                                                            # (the executor launches no P GEMM without voxels)
+        _lib.call("vn_conv_gather_gemm", vw_d.data_ptr(), wp.data_ptr(), None, rbP.data_ptr(), _lib.VN_F32, ctypes.byref(q), 0,
+                  None, E.stream())
     srows = lib.vn_rulebook_slab_rows(cap)
     slab = torch.empty((srows, 2, 64), dtype=torch.float32, device=dev)
     _lib.call("vn_rulebook_combine", rbP.data_ptr(), igrid.data_ptr(), alist.data_ptr(), cap, acount.data_ptr(),
               ctypes.byref(g), bias_d.data_ptr(), y.ptr(), vdt, slab.data_ptr(), E.stream())
     torch.cuda.synchronize()
     return {"y": y, "y64": y64, "bias": bias, "slab": slab, "dense": dense, "vw": vw, "w": w, "active": int(acount[0]), "M": M,
-            "gemm_plan": gemm_plan}
+            "gemm_plan": gemm_plan, "list": alist, "cap": cap}
 
 
-def assert_rulebook_slab(r):
-    """the rulebook's fused statistics: sum / sum of squares of (y - bias) over the active rows == over all rows"""
+def assert_rulebook_slab(r, yc_rows=None):
+    """the rulebook's fused statistics: sum / sum of squares of (y - bias) over the active rows == over all rows.
+    yc_rows: float64 (rows, 64) oracle of y - bias at the active sites only (every other row contributes exactly 0), for a
+    grid without a dense oracle; default: all rows of r["y64"].  -> the relative L2 distances of the two sums"""
     s = r["slab"].double().sum(0).cpu()
-    yc = (r["y64"] - r["bias"].double().view(1, 64, 1, 1, 1))
-    assert_fp32_sum(s[0].float(), yc.sum(dim=(0, 2, 3, 4)).numpy(), yc.abs().sum(dim=(0, 2, 3, 4)).numpy(), "rulebook sum")
-    assert_fp32_sum(s[1].float(), (yc * yc).sum(dim=(0, 2, 3, 4)).numpy(), (yc * yc).sum(dim=(0, 2, 3, 4)).numpy(), "rulebook sumsq")
+    if yc_rows is None:
+        yc_rows = (r["y64"] - r["bias"].double().view(1, 64, 1, 1, 1)).permute(0, 2, 3, 4, 1).reshape(-1, 64)
+    yc = torch.as_tensor(yc_rows, dtype=torch.float64).reshape(-1, 64)
+    return (assert_fp32_sum(s[0].float(), yc.sum(dim=0).numpy(), yc.abs().sum(dim=0).numpy(), "rulebook sum"),
+            assert_fp32_sum(s[1].float(), (yc * yc).sum(dim=0).numpy(), (yc * yc).sum(dim=0).numpy(), "rulebook sumsq"))
 
 
 def test_bf16_rulebook_first_layer():
