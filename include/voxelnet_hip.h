@@ -1352,6 +1352,44 @@ int vn_rpn_detect_layout(const float *probs, const float *deltas, const double *
                          double anchor_h, float *boxes, float *scores, int32_t *counts, void *workspace, size_t workspace_bytes,
                          vnStream stream, int32_t layout);
 
+/* ---- anchor mask (SECOND's anchor_area_threshold; csrc/anchor_mask.hip; rules: DESIGN.md section 1k) -----------
+ * An anchor over whose bird's-eye footprint the frame has (almost) no occupied voxel takes no part in the loss and can
+ * never become a detection.  Every quantity is an integer: the outputs are exact, and bit-identical from run to run.
+ *   coord  [K,4] int64 rows [b, d, h, w]: the batch's concatenated voxel coordinates.  occ[b,h,w] = the number of rows
+ *          with that (b, h, w) — rows are counted, not de-duplicated; a row with b outside [0,B), h outside [0,H) or w
+ *          outside [0,W) is ignored: neither counted nor written anywhere.  K == 0 is legal (coord may then be NULL):
+ *          every count is 0.
+ *   rects  [n_anchors,4] int32 = [w0, h0, w1, h1]: the INCLUSIVE cell rectangle of anchor n's footprint on the (H, W)
+ *          grid, anchor order n = 2 * site + a — the order of pos.reshape(B, n_anchors).  Host work
+ *          (voxelnet_amd/anchor_mask.py anchor_cell_rects: half-open footprint, edges within 1e-9 of a cell boundary
+ *          snapped onto it, clipped to the grid).  w1 < w0 or h1 < h0: an empty rectangle, count 0.  A component outside
+ *          the grid is clipped on the device.  16-byte aligned, else VN_EUNSUPPORTED.
+ *   count  [B,n_anchors] int32, or NULL: sum of occ[b, h0..h1, w0..w1] — the whole rectangle.
+ *   mask   [B,n_anchors] uint8: count > threshold (threshold >= 0; SECOND's value is 1).
+ *   pos, neg [B,n_anchors] float32 IN PLACE, or both NULL: 0.0f is stored into both where mask == 0 (the anchor is
+ *          ignored by the loss); a kept anchor's two floats are not written at all.
+ *   workspace: vn_anchor_mask_workspace_bytes(B, H, W, n_anchors) bytes (0 for unsupported sizes: B, H, W or n_anchors
+ *          <= 0, B * (H+1) * (W+1) or B * n_anchors >= 2^28).  The call clears whatever part of it it reads: its contents
+ *          before the call do not matter.
+ * A summed-area table (B, H+1, W+1) int32 is built in the workspace (an int32 atomicAdd per row of coord, a row pass, a
+ * segmented column pass); the query is four reads per anchor for any anchor or voxel size.
+ * VN_EINVAL, before anything is launched: a size outside the limits, K < 0 or K >= 2^31, threshold < 0, a NULL coord with
+ * K > 0, a NULL rects / mask / workspace, exactly one of pos / neg NULL; VN_EWORKSPACE: workspace_bytes below the query's
+ * answer.  Asynchronous on `stream`, no host synchronisation, no global state; integer atomics of an order-free sum only.
+ *
+ * vn_anchor_mask_probs: out = a COPY of probs (B, n_anchors floats per sample) in which a masked-out anchor's score is
+ * +0.0f and every other element is bit-identical, in the layout the decode reads (VN_DETECT_FLAT: anchor n <-> flat element
+ * n of probs[b];  VN_DETECT_SITE: anchor n = 2*s + a <-> probs[b,a,s], n_anchors even).  The detection tails above then
+ * run unchanged on `out`; with score_thres <= 0 a score of 0 would be a candidate — the caller refuses that.  VN_EINVAL: a
+ * NULL pointer, B or n_anchors <= 0, B * n_anchors >= 2^28, an unknown layout, or `out` overlapping `probs`. */
+size_t vn_anchor_mask_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t n_anchors);
+int vn_anchor_mask(const int64_t *coord, int64_t K, int32_t B, int32_t H, int32_t W, const int32_t *rects /*[n_anchors,4]*/,
+                   int32_t n_anchors, int32_t threshold, uint8_t *mask, int32_t *count /*may be NULL*/,
+                   float *pos /*in place; may be NULL*/, float *neg /*in place; NULL iff pos is*/, void *workspace,
+                   size_t workspace_bytes, vnStream stream);
+int vn_anchor_mask_probs(const float *probs, const uint8_t *mask, int32_t B, int32_t n_anchors, int32_t layout, float *out,
+                         vnStream stream);
+
 #ifdef __cplusplus
 }
 #endif

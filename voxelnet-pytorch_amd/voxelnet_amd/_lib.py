@@ -338,6 +338,9 @@ SIGNATURES = {
                                             c_sz, c_vp, c_i32]),
     "vn_rpn_detect_layout": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, c_i32, c_i32, ctypes.c_double, c_i32, ctypes.c_double, c_vp,
                                      c_vp, c_vp, c_vp, c_sz, c_vp, c_i32]),
+    "vn_anchor_mask_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32, c_i32]),
+    "vn_anchor_mask": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "vn_anchor_mask_probs": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "vn_clip_sgd_workspace_bytes": (c_sz, [c_i32]),
     "vn_clip_sgd": (c_i32, [c_vp, c_i32, c_f32, c_f32, c_i32, c_vp, c_sz, c_vp, c_vp]),
     "vn_clip_adamw_workspace_bytes": (c_sz, [c_i32]),

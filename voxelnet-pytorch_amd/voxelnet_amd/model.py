@@ -1003,7 +1003,10 @@ class RPN3D(nn.Module):
     """model.py:284-362.  forward(x: 7-tuple batch, device) -> 7-tuple like the reference.
     Targets (model.py:309): generated on the device from the batch's label lines x[1] (voxelnet_amd/targets.py,
     csrc/targets.hip), unless `targets=(pos_equal_one, neg_equal_one, targets)` (channels-last arrays as
-    utils.generate_targets returns them) is passed or `target_fn` is set."""
+    utils.generate_targets returns them) is passed or `target_fn` is set.
+    anchor_area_threshold: with an int >= 0 the targets generated here are edited by SECOND's anchor mask on the
+    target stream, and evaluate / predict hand the batch's mask to the decoder; targets passed in or made by `target_fn` are
+    NOT edited (anchor_mask.AnchorMasker is public for those callers)."""
 
     # the loss's objective (DESIGN.md 1e).  Class-level defaults: a model pickled before these attributes existed loads
     # without them in its __dict__ and still reads the reference's objective here.
@@ -1018,15 +1021,22 @@ class RPN3D(nn.Module):
     dir_head, dir_weight, dir_offset = False, 0.2, math.pi / 4
     last_dir = None          # the latest (L_dir, acc) pair: detached device scalars, no synchronisation
     last_dir_logits = None   # the head's logits (B,2,h,w) of the latest detect(), with the autograd graph in training
+    # SECOND's anchor mask (voxelnet_amd/anchor_mask.py): None = off, nothing new is allocated or launched; an
+    # int >= 0: an anchor with at most that many voxels over its footprint is ignored by the loss and is never a detection
+    anchor_area_threshold = None
+    last_anchor_mask = None  # the latest (B,h,w,2) uint8 mask: detached, no synchronisation
 
     def __init__(self, cls_name="Car", alpha=ALPHA, beta=BETA, sigma=SIGMA, *, cls_loss="bce", focal_alpha=0.25, focal_gamma=2.0,
                  yaw_loss="diff", iou_loss=None, iou_weight=1.0, iou_metric="3d", target_assign="reference", dir_head=False,
-                 dir_weight=0.2, dir_offset=math.pi / 4):
+                 dir_weight=0.2, dir_offset=math.pi / 4, anchor_area_threshold=None):
         super().__init__()
         from .targets import ASSIGN_KINDS
         if target_assign not in ASSIGN_KINDS:
             raise ValueError(f"target_assign must be one of {sorted(ASSIGN_KINDS)}, not {target_assign!r}")
         self.target_assign = target_assign
+        if anchor_area_threshold is not None:
+            from .anchor_mask import check_threshold
+            self.anchor_area_threshold = check_threshold(anchor_area_threshold)
         self.cls_name, self.alpha, self.beta, self.sigma = cls_name, alpha, beta, sigma
         loss_spec(cls_loss, focal_alpha, focal_gamma, yaw_loss)      # (ValueError here, not at the first step)
         self.cls_loss, self.focal_alpha, self.focal_gamma, self.yaw_loss = cls_loss, focal_alpha, focal_gamma, yaw_loss
@@ -1055,7 +1065,7 @@ class RPN3D(nn.Module):
     # `torch.save(model)` (the reference's checkpoint format, train.py:24/27) or `copy.deepcopy(model)`.
     _RUNTIME_KEYS = ("_side", "_tgt_stream", "_ws_pool", "_flat_grads", "_targets", "_decoder", "_nbt", "_flat_param_list", "_net_ctx",
                      "_named_param_list", "_anchor_t", "_bucket_views", "_mg_cache", "_step_sc", "_nbt_table", "last_iou", "last_dir",
-                     "last_dir_logits")
+                     "last_dir_logits", "_maskers", "last_anchor_mask")
 
     def __getstate__(self):
         d = self.__dict__.copy()
@@ -1130,6 +1140,47 @@ class RPN3D(nn.Module):
             self.anchors = gen.anchors
         return gen
 
+    def _anchor_masker(self, device, anchors):
+        """the anchor_mask.AnchorMasker of `anchors` (the target generator's or a decoder's (h,w,2,7) array) on this module's
+        voxel grid at anchor_area_threshold as it is now (like cls_loss it may be set after construction); a few are kept,
+        by the array they were built from: the cell rectangles are host work per anchor set"""
+        from .anchor_mask import AnchorMasker, check_threshold
+        thr, grid, device = check_threshold(self.anchor_area_threshold), self.feature_net._grid, torch.device(device)
+        cache = self.__dict__.setdefault("_maskers", {})
+        hit = cache.get(id(anchors))
+        if hit is None or hit[0] is not anchors or hit[1].device != device or hit[1].threshold != thr or hit[1].grid != grid:
+            if len(cache) >= 4:
+                cache.clear()
+            hit = cache[id(anchors)] = (anchors, AnchorMasker(self.cls_name, device, anchors=anchors, threshold=thr, grid=grid))
+        return hit[1]
+
+    def _mask_targets(self, targets, voxel_coordinates, main):
+        """anchor_area_threshold set, targets the module generated itself: the anchors without voxels under them become
+        ignored — pos = neg = 0 in place (vn_anchor_mask) — on the CURRENT stream, the target stream, which is first ordered
+        after `main`, the stream the batch's coordinates are ready on (None: they are ready on this one).  Caller-supplied
+        targets and a target_fn's are never edited."""
+        pos, neg = targets[0], targets[1]
+        dev = pos.device
+        cur = _lib.current_stream(dev)
+        if main is not None and main != cur:
+            with torch.cuda.stream(main):
+                coord = _batch_cat(voxel_coordinates, torch.int64)
+            cur.wait_stream(main)
+            coord.record_stream(cur)
+        else:
+            coord = _batch_cat(voxel_coordinates, torch.int64)
+        masker = self._anchor_masker(dev, self._target_generator(dev).anchors)
+        self.last_anchor_mask = masker.mask(coord, len(voxel_coordinates), pos=pos, neg=neg)
+        return targets
+
+    def _decode_mask(self, dec, voxel_coordinates, device):
+        """the (B,h,w,2) uint8 mask of a batch for the decoder `dec` (its anchors), on the current stream"""
+        coord = _batch_cat(_parts_to(voxel_coordinates, device), torch.int64)
+        if not coord.is_cuda:
+            raise _lib.VoxelnetHipError("anchor_area_threshold: the voxel coordinates must live on a HIP device (no CPU path)")
+        self.last_anchor_mask = self._anchor_masker(coord.device, dec.anchors).mask(coord, len(voxel_coordinates))
+        return self.last_anchor_mask
+
     def predict(self, data, probs, deltas, summary=False, visual=False, decode=None):
         """model.py:364-441 without the drawing branches: -> (tag, ret_box_3d_score), one array per sample of
         [cls_name, x, y, z, h, w, l, r, score] rows (strings, as np.concatenate makes them at model.py:389-394).
@@ -1139,7 +1190,13 @@ class RPN3D(nn.Module):
             raise NotImplementedError("the summary / visual branches of RPN3D.predict draw with OpenCV (model.py:396-439): "
                                       "outside the accelerated path")
         dec = self._box_decoder(probs.device)
-        ret_box_3d, ret_score = dec(probs, deltas, **self._dir_decode(dict(decode or {}), dec))
+        kw = self._dir_decode(dict(decode or {}), dec)
+        if self.anchor_area_threshold is not None:
+            # (the mask comes from the voxel coordinates of the batch the maps were made from, data[4])
+            if len(data) < 5 or data[4] is None:
+                raise _lib.VoxelnetHipError("predict: anchor_area_threshold needs the batch's voxel coordinates (data[4])")
+            kw["anchor_mask"] = self._decode_mask(dec, data[4], probs.device)
+        ret_box_3d, ret_score = dec(probs, deltas, **kw)
         out = []
         for boxes_3d, scores in zip(ret_box_3d, ret_score):
             out.append(np.concatenate([np.tile(self.cls_name, len(boxes_3d))[:, np.newaxis], boxes_3d,
@@ -1208,7 +1265,11 @@ class RPN3D(nn.Module):
             with torch.no_grad(), (ema.applied() if ema is not None else contextlib.nullcontext()):
                 for x in batches:
                     prob, delta = self.detect(_parts_to(x[2], device), _parts_to(x[4], device))
-                    det = dec.decode_device(prob, delta, top_k=evaluator.top_k, **self._dir_decode(kw, dec))
+                    if self.anchor_area_threshold is None:
+                        det = dec.decode_device(prob, delta, top_k=evaluator.top_k, **self._dir_decode(kw, dec))
+                    else:                         # (an anchor without voxels under it is never a detection)
+                        det = dec.decode_device(prob, delta, top_k=evaluator.top_k, **self._dir_decode(kw, dec),
+                                                anchor_mask=self._decode_mask(dec, x[4], device))
                     if calib_of is None:
                         evaluator.update(*det, x[1])
                     else:
@@ -1442,8 +1503,11 @@ class RPN3D(nn.Module):
                 if ts is None or ts.device != dev:
                     from .voxelize import pipeline_stream
                     ts = self.__dict__["_tgt_stream"] = pipeline_stream(dev)
+                main = _lib.current_stream(dev) if self.anchor_area_threshold is not None else None
                 with torch.cuda.stream(ts):
                     targets = self._target_generator(dev)(label)
+                    if main is not None:          # (the edited maps are the pos / neg that go into vnStep)
+                        targets = self._mask_targets(targets, voxel_coordinates, main)
             else:
                 def f32(a):
                     if torch.is_tensor(a) and a.dtype == torch.float32 and a.device == dev and a.is_contiguous():
@@ -1519,6 +1583,8 @@ class RPN3D(nn.Module):
                 cur = _lib.current_stream(dev)
                 for t_ in targets:
                     t_.record_stream(cur)         # (allocated on the target stream, read by the loss kernels on this one)
+                if self.anchor_area_threshold is not None:
+                    self.last_anchor_mask.record_stream(cur)
             if red is not None:
                 def waiter(bi):
                     return lambda st: _lib.call("vn_net_wait_bucket", self._net_handle(dev), bi, ctypes.c_void_p(st.cuda_stream))
@@ -1573,14 +1639,19 @@ class RPN3D(nn.Module):
             if ts is None or ts.device != dev_:
                 from .voxelize import pipeline_stream
                 ts = self.__dict__["_tgt_stream"] = pipeline_stream(dev_)     # (the input pipeline's stream: one queue for both)
+            main = _lib.current_stream(dev_) if self.anchor_area_threshold is not None else None
             with torch.cuda.stream(ts):
                 early = self._target_generator(dev_)(label)
+                if main is not None:              # (right after the target generator, on its stream)
+                    early = self._mask_targets(early, voxel_coordinates, main)
         prob_out, delta_out = self.detect(voxel_features, voxel_coordinates)
         if early is not None:
             cur = _lib.current_stream(prob_out.device)
             cur.wait_stream(self.__dict__["_tgt_stream"])
             for t_ in early:
                 t_.record_stream(cur)         # (allocated on the target stream, read by the loss kernels on this one)
+            if self.anchor_area_threshold is not None:
+                self.last_anchor_mask.record_stream(cur)
             targets = early
         if targets is None:
             if self.target_fn is not None:
@@ -1590,5 +1661,7 @@ class RPN3D(nn.Module):
                                             "target_fn")
             else:
                 targets = self._target_generator(prob_out.device)(label)
+                if self.anchor_area_threshold is not None:
+                    targets = self._mask_targets(targets, voxel_coordinates, None)
         loss, cls_loss, reg_loss, cpos, cneg = self.loss(prob_out, delta_out, *targets)
         return prob_out, delta_out, loss, cls_loss, reg_loss, cpos, cneg

@@ -15,7 +15,10 @@ package's loss has to be decoded with layout="site": `TRAINED_DECODE`.
 
 `dir_logits=`: the direction head's map (B,2,h,w) turns every detection's yaw into the half-plane its
 anchor's logit names (`dir_head.rectify_yaw`); the tail is then composed from the public pieces — candidates, the yaw
-rectification, `nms_device`, a gather of the kept rows — and needs layout="site"."""
+rectification, `nms_device`, a gather of the kept rows — and needs layout="site".
+
+`anchor_mask=`: a (B,h,w,2) uint8 mask of `anchor_mask.AnchorMasker` — an anchor without voxels under
+its footprint scores 0 in a copy of the probability map (`vn_anchor_mask_probs`), and every tail above runs unchanged on it."""
 import ctypes
 import math
 
@@ -101,6 +104,21 @@ class BoxDecoder:
             raise ValueError(f"maps of {probs[0].numel()} / {deltas[0].numel()} elements do not match {N} anchors")
         return probs, deltas
 
+    def _masked(self, probs, anchor_mask, score_thres, layout, what):
+        """the copy of probs in which every anchor the mask (anchor_mask.AnchorMasker) leaves out scores 0, in the
+        layout the decode reads: every tail below runs unchanged on it"""
+        from .anchor_mask import mask_probs
+        if not score_thres > 0:
+            raise ValueError(f"{what}: anchor_mask needs score_thres > 0 (a masked-out anchor scores 0 and would be a candidate), "
+                             f"not {score_thres!r}")
+        lay = _layout(self.layout if layout is None else layout)
+        if not (torch.is_tensor(probs) and probs.is_cuda):
+            raise _lib.VoxelnetHipError(f"{what}: probs / deltas must be HIP tensors (no CPU path)")
+        if torch.is_tensor(anchor_mask) and anchor_mask.is_cuda and (anchor_mask.dim() < 1 or anchor_mask.shape[0] != probs.shape[0]
+                                                                     or anchor_mask.numel() != probs.shape[0] * self.n_anchors):
+            raise ValueError(f"{what}: anchor_mask {tuple(anchor_mask.shape)} is not a mask of {probs.shape[0]} x {self.n_anchors} anchors")
+        return mask_probs(probs.detach().float(), anchor_mask, self.n_anchors, lay)
+
     def _decode_dir(self, probs, deltas, score_thres, nms_thres, top_k, nms, pre_nms_top_k, layout, dir_logits, dir_offset):
         """decode_device with the direction head's logits: vn_rpn_select_decode_layout -> vn_boxes_rectify_yaw -> vn_box_nms ->
         a gather of the kept rows.  The yaw changes by multiples of pi only, so the candidates, the kept set and the scores
@@ -132,7 +150,7 @@ class BoxDecoder:
         return boxes, scores, kc
 
     def decode_device(self, probs, deltas, score_thres=SCORE_THRES, nms_thres=NMS_THRES, top_k=NMS_POST_TOPK, nms="standup",
-                      pre_nms_top_k=None, layout=None, dir_logits=None, dir_offset=math.pi / 4):
+                      pre_nms_top_k=None, layout=None, dir_logits=None, dir_offset=math.pi / 4, anchor_mask=None):
         """probs (B,2,h,w), deltas (B,14,h,w) fp32 device tensors -> (boxes (B,top_k,7) f32, scores (B,top_k) f32, counts (B,)
         int32) ON THE DEVICE, enqueued on the current stream without any host synchronisation: per sample the first
         counts[b] rows are the kept detections in descending score, the rest is zero.  What evaluate.DetectionEvaluator
@@ -144,7 +162,11 @@ class BoxDecoder:
         pre_nms_top_k=None too (the reference's tail read in the layout the loss trains).
         dir_logits (None: every path above exactly as it is): the direction head's (B,2,h,w) map, layout "site" only — column 6
         becomes wrap_pi(r - dir_offset) + dir_offset + pi * [logit > 0] through the composed tail; apart from that
-        column the kept set and the scores are the ones of the call without it."""
+        column the kept set and the scores are the ones of the call without it.
+        anchor_mask (None: nothing new is allocated or launched): a (B,h,w,2) uint8 mask (anchor_mask.AnchorMasker) —
+        every path above runs unchanged on a copy of probs in which a masked-out anchor scores 0; needs score_thres > 0."""
+        if anchor_mask is not None:
+            probs = self._masked(probs, anchor_mask, score_thres, layout, "predict")
         if dir_logits is not None:
             return self._decode_dir(probs, deltas, score_thres, nms_thres, top_k, nms, pre_nms_top_k, layout, dir_logits, dir_offset)
         mode = _nms_mode(nms)
@@ -181,12 +203,16 @@ class BoxDecoder:
                           counts.data_ptr(), ws.data_ptr(), nbytes, _lib.raw_stream(), lay)
         return boxes, scores, counts
 
-    def candidates_device(self, probs, deltas, score_thres, pre_nms_top_k, layout=None, dir_logits=None, dir_offset=math.pi / 4):
+    def candidates_device(self, probs, deltas, score_thres, pre_nms_top_k, layout=None, dir_logits=None, dir_offset=math.pi / 4,
+                          anchor_mask=None):
         """The first half of the tail on its own (vn_rpn_select_decode): per sample the min(M, pre_nms_top_k) best of the M
         candidates with p >= score_thres, decoded, in descending (score, flat index) order -> (boxes (B,pre,7) f32, scores
         (B,pre) f32, flat anchor indices (B,pre) int32, counts (B,) int32) on the device; rows past the count are zero.
         layout "site" (vn_rpn_select_decode_layout): the index is the anchor index n = 2 * site + rotation of the target maps.
-        dir_logits (layout "site" only): the candidates' yaw is rectified by the direction head's map (dir_head.rectify_yaw)."""
+        dir_logits (layout "site" only): the candidates' yaw is rectified by the direction head's map (dir_head.rectify_yaw).
+        anchor_mask: as decode_device's — a masked-out anchor is never a candidate."""
+        if anchor_mask is not None:
+            probs = self._masked(probs, anchor_mask, score_thres, layout, "candidates")
         lay = _layout(self.layout if layout is None else layout)
         if dir_logits is not None and lay != _lib.VN_DETECT_SITE:
             raise ValueError("dir_logits: the direction head's logits are laid out by site; layout must be 'site'")
@@ -219,10 +245,10 @@ class BoxDecoder:
         return boxes, scores, idx, counts
 
     def __call__(self, probs, deltas, score_thres=SCORE_THRES, nms_thres=NMS_THRES, top_k=NMS_POST_TOPK, nms="standup",
-                 pre_nms_top_k=None, layout=None, dir_logits=None, dir_offset=math.pi / 4):
+                 pre_nms_top_k=None, layout=None, dir_logits=None, dir_offset=math.pi / 4, anchor_mask=None):
         """probs (B,2,h,w), deltas (B,14,h,w) fp32 device tensors -> ([boxes (n_i,7) f32 numpy], [scores (n_i,) f32 numpy])"""
         boxes, scores, counts = self.decode_device(probs, deltas, score_thres, nms_thres, top_k, nms, pre_nms_top_k, layout,
-                                                   dir_logits, dir_offset)
+                                                   dir_logits, dir_offset, anchor_mask)
         B = boxes.shape[0]
         cnt = counts.cpu().numpy()
         bh, sh = boxes.cpu().numpy(), scores.cpu().numpy()

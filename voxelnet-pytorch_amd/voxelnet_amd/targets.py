@@ -150,6 +150,19 @@ class TargetGenerator:
         self._parsed = {}          # (label lines, coordinate) -> (G, 7) float64 boxes
         self._standup = {}         # id-free cache of gt_standup_boxes, keyed by the boxes' bytes
 
+    def _apply_mask(self, out, anchor_mask):
+        """pos / neg of a fresh result with the anchors a (B,h,w,2) uint8 mask leaves out IGNORED — both zero:
+        copies in which a kept entry is bit-identical (vn_anchor_mask_probs, flat: the maps are in anchor order); targets and
+        matched stay as they are"""
+        if anchor_mask is None:
+            return out
+        from .anchor_mask import mask_probs
+        pos, neg = out[0], out[1]
+        if torch.is_tensor(anchor_mask) and anchor_mask.is_cuda and tuple(anchor_mask.shape) != tuple(pos.shape):
+            raise ValueError(f"anchor_mask {tuple(anchor_mask.shape)} is not the targets' {tuple(pos.shape)}")
+        N = self.n_anchors
+        return (mask_probs(pos, anchor_mask, N, _lib.VN_DETECT_FLAT), mask_probs(neg, anchor_mask, N, _lib.VN_DETECT_FLAT)) + tuple(out[2:])
+
     def _from_boxes_iou(self, gt_boxes, return_matched):
         """assign = "standup" / "rotated": everything per box happens on the device too (no stand-up rectangles here)"""
         B = len(gt_boxes)
@@ -177,11 +190,13 @@ class TargetGenerator:
                       tgt.data_ptr(), matched.data_ptr() if return_matched else None, ws.data_ptr(), nbytes, _lib.raw_stream())
         return (pos, neg, tgt, matched) if return_matched else (pos, neg, tgt)
 
-    def from_boxes(self, gt_boxes, return_matched=False):
+    def from_boxes(self, gt_boxes, return_matched=False, anchor_mask=None):
         """gt_boxes: list of (G_i, 7) float64 lidar boxes per sample.  return_matched (assign "standup" / "rotated" only): a
-        fourth tensor (B,h,w,2) int32, every anchor's ground-truth index or -1"""
+        fourth tensor (B,h,w,2) int32, every anchor's ground-truth index or -1.  anchor_mask (None: nothing new is launched): a
+        (B,h,w,2) uint8 device mask (anchor_mask.AnchorMasker) — after the assignment, forced positives included,
+        an anchor it leaves out is ignored: pos = neg = 0; targets and matched are not touched."""
         if self.assign != "reference":
-            return self._from_boxes_iou(gt_boxes, return_matched)
+            return self._apply_mask(self._from_boxes_iou(gt_boxes, return_matched), anchor_mask)
         if return_matched:
             raise ValueError('return_matched needs assign="standup" or "rotated": the reference assignment reports no index')
         B = len(gt_boxes)
@@ -221,9 +236,9 @@ class TargetGenerator:
                       B, G, self.pos_iou, self.neg_iou, float(self.cfg["h"]), pos.data_ptr(),
                       neg.data_ptr(), tgt.data_ptr(), ws.data_ptr(), nbytes,
                       _lib.raw_stream())
-        return pos, neg, tgt
+        return self._apply_mask((pos, neg, tgt), anchor_mask)
 
-    def __call__(self, labels, feature_map_shape=None, coordinate="lidar"):
+    def __call__(self, labels, feature_map_shape=None, coordinate="lidar", anchor_mask=None):
         if feature_map_shape is not None and tuple(feature_map_shape) != tuple(self.shape):
             raise ValueError(f"feature map {tuple(feature_map_shape)} does not match the anchors {tuple(self.shape)}")
         # label lines -> lidar boxes is a pure function of the TEXT of a sample's label: remembered per sample (an epoch
@@ -240,7 +255,7 @@ class TargetGenerator:
                 hit.setflags(write=False)
                 self._parsed[key] = hit
             boxes.append(hit)
-        return self.from_boxes(boxes)
+        return self.from_boxes(boxes, anchor_mask=anchor_mask)
 
 
 def generate_targets(labels, feature_map_shape, anchors, cls_name="Car", coordinate="lidar", device="cuda:0"):
