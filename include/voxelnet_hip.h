@@ -1035,6 +1035,41 @@ int vn_boxes_rectify_yaw(float *boxes /*[B][K][7]*/, const int32_t *idx /*[B][K]
                          const float *dir_logits /*[B][2][n_anchors/2]*/, int32_t B, int32_t K, int32_t n_anchors,
                          double dir_offset, vnStream stream);
 
+/* ---- IoU-aware confidence head (csrc/iou_head.hip) -----------------------------------------------
+ * A second Conv2d(768, 2, 1) on the concatenation: z[b][a][s], the site layout of prob and of the direction logits,
+ * q = sigmoid(z) predicts the IoU of anchor n = 2*s + a's decoded box with its ground truth.  The head's forward and
+ * backward are vn_dir_head_fwd / vn_dir_head_bwd.  All three entry points are asynchronous on `stream`, without host
+ * synchronisation; none is part of vn_net_step.
+ *
+ * vn_rpn_iou_head_loss: logits (B,2,H*W), delta (B,14,H,W), pos (B,H,W,2), targets (B,H,W,14) fp32, anchors (H*W*2, 7)
+ * float64.  With P = decode(delta[b, 7a..7a+6, s], A_n), G = decode(targets[b, s, 7a..7a+6], A_n) (vn_rpn_iou_loss'
+ * decode and validity rules: an invalid pair scores 0) and t = clamp(IoU_metric(P, G), 0, 1), a CONSTANT:
+ *   out2[0] = L   = sum_b (1/P_b) sum m * (max(z,0) - z t + log1p(exp(-|z|))),  m = pos[b,s,a],  P_b = max(1, sum pos[b])
+ *   out2[1] = mae = (sum m * |q - t|) / max(1, sum m)                            (a diagnostic)
+ *   d_logits (B,2,H*W) or NULL: m * (q - t) / P_b, and exactly +0.0f where m == 0 (what vn_dir_head_bwd skips)
+ *   iou_target (B,2,H*W) or NULL: (float)t where m != 0, +0.0f elsewhere
+ * Every element of the two maps is written; there is NO gradient for delta.  float64 arithmetic, nothing is read where
+ * m == 0; slab sums added in one fixed order: bit-identical from run to run and with or without the optional outputs.
+ * VN_EINVAL: B, H or W <= 0 or B*H*W >= 2^31, an unknown metric (VN_IOU_BEV / VN_IOU_3D), a NULL logits / delta / pos /
+ * targets / anchors / workspace / out2; VN_EWORKSPACE: workspace_bytes below vn_rpn_iou_head_loss_workspace_bytes.
+ *
+ * vn_iou_rectify_probs: out[i] = (float)(pow((double)probs[i], 1 - alpha) * pow(sigmoid((double)iou_logits[i]), alpha)),
+ * i < n = B*2*S, elementwise in the site layout; alpha == 0 copies probs bit for bit.  out must not be probs.
+ * VN_EINVAL: n <= 0 or >= 2^31, alpha outside [0, 1] or not finite, a NULL pointer, out == probs.
+ *
+ * vn_site_heads_fwd: vn_dir_head_fwd for n_out = 2 or 4 outputs in ONE read of the rows: w [n_out][768] (16-byte aligned),
+ * bias [n_out] or NULL, logits [B][n_out][S].  Output c has the bits vn_dir_head_fwd gives for weight row c (the same
+ * FMAs in the same order, the same butterfly).  Rows as for vn_dir_head_fwd; VN_EINVAL also for any other n_out. */
+size_t vn_rpn_iou_head_loss_workspace_bytes(int32_t B, int32_t H, int32_t W);
+int vn_rpn_iou_head_loss(const float *logits /*[B][2][H*W]*/, const float *delta, const float *pos, const float *targets,
+                         const double *anchors /*[H*W*2,7]*/, int32_t B, int32_t H, int32_t W, int32_t metric, void *workspace,
+                         size_t workspace_bytes, float *out2, float *d_logits /*NULL: forward only*/,
+                         float *iou_target /*[B][2][H*W] or NULL*/, vnStream stream);
+int vn_iou_rectify_probs(const float *probs, const float *iou_logits, int64_t n, double alpha, float *out, vnStream stream);
+int vn_site_heads_fwd(const void *cat_rows, int32_t dtype, int64_t cat_stride, const float *w /*[n_out][768]*/,
+                      const float *bias /*[n_out] or NULL*/, int32_t n_out, int32_t B, int64_t S,
+                      float *logits /*[B][n_out][S]*/, vnStream stream);
+
 /* ---- optimizer tail (voxelnet/train.py:153-154 with the optimizer of train.py:130-132) ---------------------
  * torch.nn.utils.clip_grad_norm_(parameters, max_norm) followed by an update rule, in two launches.  The clip is the
  * same code under both rules (vn_clip_sgd here, vn_clip_adamw below):

@@ -18,29 +18,10 @@
 
 namespace {
 
-constexpr int DH_C = 768;                  // channels of the concatenation
-constexpr int DH_THREADS = 256;
-constexpr int DH_TILE = 64;                // rows per workgroup of the forward: 8 half-waves x 8 rows
-constexpr int DH_ROWS_PER_HALF = DH_TILE / (DH_THREADS / 32);
 constexpr int DH_BWD_THREADS = 192;        // backward: 4 channels per thread
 constexpr int DH_BWD_MAX_WG = 256;         // workgroups (= partial rows) of the backward's pass over the list
 constexpr int DH_PART = 2 * DH_C + 2;      // one partial row: d_w[2][768], d_bias[2]
 constexpr double DH_PI = 3.14159265358979323846;
-
-// The 24 channels of lane l (of 32) of a row, as NLOAD 16-byte loads of PER channels each: channel (j * 32 + l) * PER + e.
-template <int DT> struct DhRow;
-template <> struct DhRow<VN_BF16> {
-    static constexpr int NLOAD = 3, PER = 8;
-    typedef bf16x8_t vec_t;
-    typedef bf16_t elem_t;
-    static __device__ __forceinline__ float get(const vec_t &v, int e) { return vn_bf2f(v[e]); }
-};
-template <> struct DhRow<VN_F32> {
-    static constexpr int NLOAD = 6, PER = 4;
-    typedef f32x4_t vec_t;
-    typedef float elem_t;
-    static __device__ __forceinline__ float get(const vec_t &v, int e) { return v[e]; }
-};
 
 // logits[b][c][s] = bias[c] + sum_k cat[b * S + s][k] * w[c][k]; products and sums fp32, the lane's 24 in channel order,
 // then the butterfly over the 32 lanes.
@@ -279,12 +260,6 @@ __global__ void __launch_bounds__(DH_THREADS) k_rectify_yaw(float *__restrict__ 
     boxes[i * 7 + 6] = (float)((x - floor(x / DH_PI) * DH_PI) + off + (z > 0.f ? DH_PI : 0.0));
 }
 
-bool dh_sizes_ok(int32_t B, int64_t S) { return B > 0 && S > 0 && (int64_t)B * S < (1ll << 31); }
-bool dh_rows_ok(const void *p, int32_t dtype, int64_t stride) {
-    if (dtype != VN_BF16 && dtype != VN_F32) return false;          // (the split [hi|lo] formats are not handled here)
-    const int64_t per16 = dtype == VN_BF16 ? 8 : 4;
-    return p && stride >= DH_C && stride % per16 == 0 && reinterpret_cast<uintptr_t>(p) % 16 == 0;
-}
 int dh_bwd_wgs(int64_t M) { return (int)(M < DH_BWD_MAX_WG ? M : DH_BWD_MAX_WG); }
 
 }  // namespace

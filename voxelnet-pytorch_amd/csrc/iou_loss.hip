@@ -49,16 +49,9 @@ __device__ __forceinline__ void iou_pair_loss(const double (&dp)[7], const doubl
     loss = 1.0;
 #pragma unroll
     for (int k = 0; k < 7; ++k) grad[k] = 0.0;
-    const double diag = sqrt(A[4] * A[4] + A[5] * A[5]);
-    double P[7], G[7];
-    vn_box_decode_f64(dp, A, diag, P);
-    vn_box_decode_f64(dg, A, diag, G);
-    if (!(box_ok(P) && box_ok(G))) return;
-    const double area_p = P[4] * P[5], area_g = G[4] * G[5];
-    const double S = area_p + area_g, V = P[3] * area_p + G[3] * area_g;
-    if (!isfinite(metric == VN_IOU_3D ? V : S)) return;
-    double ib, i3;
-    box_iou_pair(P, G, ib, i3);
+    double P[7], G[7], diag, S, V, ib, i3;
+    if (!vn_iou_pair_value(dp, dg, A, metric, diag, P, G, S, V, ib, i3)) return;          // (rpn_common.h: the value half)
+    const double area_p = P[4] * P[5];
     iou = metric == VN_IOU_3D ? i3 : ib;
     loss = 1.0 - iou;
     const double ptop = P[2] + P[3], gtop = G[2] + G[3];

@@ -1,4 +1,4 @@
-// Shared by the RPN tail — iou_loss.hip, dir_head.hip, predict.hip, detect.hip, targets.hip, targets_iou.hip — and by nothing
+// Shared by the RPN tail — iou_loss.hip, dir_head.hip, iou_head.hip, predict.hip, detect.hip, targets.hip, targets_iou.hip — and by nothing
 // else: the ONE copy of the anchor box codec and of the scaffold of a loss term summed over the (B, h, w) anchor sites
 // (DESIGN.md 1j).  common.h goes into every translation unit; the two kernels here do not belong in the convolution files.
 #pragma once
@@ -32,6 +32,29 @@ __device__ __forceinline__ void vn_box_decode_f64(const double (&d)[7], const do
     P[6] = d[6] + A[6];
 }
 
+// The IoU VALUE of the pair an anchor's regression channels dp and its targets dg decode to: what
+// iou_loss.hip differentiates and iou_head.hip takes as the confidence head's target.  -> false for an invalid pair — a
+// decoded field not finite, a size not > 0, the area (bev) / volume (3d) sum not finite —, which scores 0 (ib = i3 = 0).
+// P, G, diag, S = the areas' sum and V = the volumes' sum are what the derivative needs again.
+__device__ __forceinline__ bool vn_iou_pair_value(const double (&dp)[7], const double (&dg)[7], const double (&A)[7], int metric,
+                                                  double &diag, double (&P)[7], double (&G)[7], double &S, double &V, double &ib,
+                                                  double &i3) {
+    ib = 0.0;
+    i3 = 0.0;
+    S = 0.0;
+    V = 0.0;
+    diag = sqrt(A[4] * A[4] + A[5] * A[5]);
+    vn_box_decode_f64(dp, A, diag, P);
+    vn_box_decode_f64(dg, A, diag, G);
+    if (!(box_ok(P) && box_ok(G))) return false;
+    const double area_p = P[4] * P[5], area_g = G[4] * G[5];
+    S = area_p + area_g;
+    V = P[3] * area_p + G[3] * area_g;
+    if (!isfinite(metric == VN_IOU_3D ? V : S)) return false;
+    box_iou_pair(P, G, ib, i3);
+    return true;
+}
+
 // the regression targets of ground-truth box g on anchor a (utils.py:390-392): float64 arithmetic, float32 storage
 __device__ __forceinline__ void vn_box_encode(const double *g, const double *a, double anchor_h, float (&t)[7]) {
     const double diag = sqrt(a[4] * a[4] + a[5] * a[5]);
@@ -60,9 +83,37 @@ __device__ __forceinline__ void vn_box_standup_f32(const float (&o)[7], float (&
     r[0] = x1; r[1] = y1; r[2] = x2; r[3] = y2;
 }
 
+// ---- rows of the concatenation, as the 1x1 heads on it read them (dir_head.hip, iou_head.hip) ----
+constexpr int DH_C = 768;                  // channels of the concatenation
+constexpr int DH_THREADS = 256;
+constexpr int DH_TILE = 64;                // rows per workgroup of a head's forward: 8 half-waves x 8 rows
+constexpr int DH_ROWS_PER_HALF = DH_TILE / (DH_THREADS / 32);
+
+// The 24 channels of lane l (of 32) of a row, as NLOAD 16-byte loads of PER channels each: channel (j * 32 + l) * PER + e.
+template <int DT> struct DhRow;
+template <> struct DhRow<VN_BF16> {
+    static constexpr int NLOAD = 3, PER = 8;
+    typedef bf16x8_t vec_t;
+    typedef bf16_t elem_t;
+    static __device__ __forceinline__ float get(const vec_t &v, int e) { return vn_bf2f(v[e]); }
+};
+template <> struct DhRow<VN_F32> {
+    static constexpr int NLOAD = 6, PER = 4;
+    typedef f32x4_t vec_t;
+    typedef float elem_t;
+    static __device__ __forceinline__ float get(const vec_t &v, int e) { return v[e]; }
+};
+
+bool dh_sizes_ok(int32_t B, int64_t S) { return B > 0 && S > 0 && (int64_t)B * S < (1ll << 31); }
+bool dh_rows_ok(const void *p, int32_t dtype, int64_t stride) {
+    if (dtype != VN_BF16 && dtype != VN_F32) return false;          // (the split [hi|lo] formats are not handled here)
+    const int64_t per16 = dtype == VN_BF16 ? 8 : 4;
+    return p && stride >= DH_C && stride % per16 == 0 && reinterpret_cast<uintptr_t>(p) % 16 == 0;
+}
+
 // ---- site-term scaffold: loss = sum_b (1 / P_b) sum over positives of a per-anchor term, P_b = max(1, sum pos[b]) ----
 // Three launches, all sums float64 in a fixed order (no atomics, bit-identical runs): k_pos_norm, 16 workgroups per sample,
-// leaves partial sums of pos; the term's own kernel (k_iou_loss, k_dir_loss), one thread per site, adds a sample's
+// leaves partial sums of pos; the term's own kernel (k_iou_loss, k_dir_loss, k_iou_head_loss), one thread per site, adds a sample's
 // partials with vn_pos_total and writes one slab row of three sums per workgroup; k_site_term_finalize adds the rows.
 constexpr int VN_SITE_THREADS = 256;
 constexpr int VN_POS_CHUNKS = 16;          // workgroups per sample in k_pos_norm
@@ -86,7 +137,7 @@ __device__ __forceinline__ double vn_block_sum3(double s0, double s1, double s2)
 }
 
 // The two kernels are templates on the workgroup size (always VN_SITE_THREADS) so that only the files that launch them
-// instantiate them: a plain __global__ function would be compiled into the code object of all six includers.
+// instantiate them: a plain __global__ function would be compiled into the code object of every includer.
 // part[b * VN_POS_CHUNKS + chunk] = partial sum of pos[b] (per_b elements per sample)
 template <int THREADS>
 __global__ void __launch_bounds__(THREADS) k_pos_norm(const float *__restrict__ pos, int64_t per_b, double *__restrict__ part) {

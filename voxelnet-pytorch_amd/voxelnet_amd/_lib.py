@@ -311,6 +311,10 @@ SIGNATURES = {
     "vn_rpn_dir_loss_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32]),
     "vn_rpn_dir_loss": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, ctypes.c_double, c_vp, c_sz, c_vp, c_vp, c_vp]),
     "vn_boxes_rectify_yaw": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, ctypes.c_double, c_vp]),
+    "vn_rpn_iou_head_loss_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32]),
+    "vn_rpn_iou_head_loss": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_sz, c_vp, c_vp, c_vp, c_vp]),
+    "vn_iou_rectify_probs": (c_i32, [c_vp, c_vp, c_i64, ctypes.c_double, c_vp, c_vp]),
+    "vn_site_heads_fwd": (c_i32, [c_vp, c_i32, c_i64, c_vp, c_vp, c_i32, c_i32, c_i64, c_vp, c_vp]),
     "vn_rpn_targets_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32]),
     "vn_rpn_targets": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, c_f32, ctypes.c_double, c_vp, c_vp, c_vp,
                                c_vp, c_sz, c_vp]),

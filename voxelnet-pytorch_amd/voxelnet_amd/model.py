@@ -426,6 +426,36 @@ def _dir_params(mid):
     return [mid.dir_conv.conv.weight, mid.dir_conv.conv.bias]
 
 
+def _iou_params(mid):
+    return [mid.iou_conv.conv.weight, mid.iou_conv.conv.bias]
+
+
+def _iou_grads(ctx, G):
+    """_dir_grads for the IoU-aware head, whose two parameters travel behind the direction head's"""
+    if not ctx.iou_head:
+        return ()
+    g = G.get("iou_head")
+    return (None, None) if g is None else (g["weight"], g["bias"])
+
+
+def _peel_site_heads(has_dir, has_iou, flat):
+    """flat = (..., [dir weight, bias], [iou weight, bias]) -> (dirp, ioup, the rest): each head's detached pair or None"""
+    dirp = ioup = None
+    if has_iou:
+        ioup, flat = tuple(f.detach() for f in flat[-2:]), flat[:-2]
+    if has_dir:
+        dirp, flat = tuple(f.detach() for f in flat[-2:]), flat[:-2]
+    return dirp, ioup, flat
+
+
+def _head_out_grads(ctx, d_heads):
+    """the gradients of the site heads' logits, which follow (prob, reg) in a Function's outputs -> (d_dir, d_iou)"""
+    d = list(d_heads)
+    d_dir = d.pop(0) if ctx.dir_head and d else None
+    d_iou = d.pop(0) if ctx.iou_head and d else None
+    return d_dir, d_iou
+
+
 class _MiddleFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, mod, training, *flat):
@@ -433,9 +463,8 @@ class _MiddleFn(torch.autograd.Function):
         mode = _mode()
         names, P, Bf, _ = _collect_middle(mod)
         P = _detached(P)
-        dirp = None
-        if getattr(mod, "dir_conv", None) is not None:       # (the direction head's two parameters travel last)
-            dirp, flat = tuple(f.detach() for f in flat[-2:]), flat[:-2]
+        # (the direction head's two parameters travel last, the IoU-aware head's two behind them)
+        dirp, ioup, flat = _peel_site_heads(getattr(mod, "dir_conv", None) is not None, getattr(mod, "iou_conv", None) is not None, flat)
         P["heads"] = _heads_params([f.detach() for f in flat])
         with _lib.on_device(x.device):
             B, D, H, W, C = x.shape
@@ -446,23 +475,24 @@ class _MiddleFn(torch.autograd.Function):
                 dense = E.new_rows(B, (D, H, W), 128, torch.bfloat16, E.is_split(mode), x.device)
                 _lib.call("vn_cast_rows", xc.data_ptr(), _lib.VN_F32, 128, B * D * H * W, 128, dense.ptr(),
                           _lib.VN_BF16, dense.t.shape[-1], dense.lo_off, E.stream())
-            out = N.middle_forward(dense, P, Bf, mod._block1_stride, training, mode, dir_head=dirp)
+            out = N.middle_forward(dense, P, Bf, mod._block1_stride, training, mode, dir_head=dirp, iou_head=ioup)
         st = out[-1]
         ctx.st, ctx.P, ctx.names = st, P, names
         ctx.need_dx = x.requires_grad
         ctx.training = bool(training)
-        ctx.dir_head = dirp is not None
+        ctx.dir_head, ctx.iou_head = dirp is not None, ioup is not None
         return out[:-1]
 
     @staticmethod
-    def backward(ctx, d_prob, d_reg, d_dir=None):
+    def backward(ctx, d_prob, d_reg, *d_heads):
         _need_training(ctx.training)
+        d_dir, d_iou = _head_out_grads(ctx, d_heads)
         with _lib.on_device(d_prob.device):
-            G, d_dense = N.middle_backward(ctx.st, d_prob.float(), d_reg.float(), ctx.P, need_dx=ctx.need_dx, d_dir=d_dir)
+            G, d_dense = N.middle_backward(ctx.st, d_prob.float(), d_reg.float(), ctx.P, need_dx=ctx.need_dx, d_dir=d_dir, d_iou=d_iou)
             dx = None
             if d_dense is not None:
                 dx = d_dense.t if d_dense.t.dtype == torch.float32 else d_dense.t.float()
-        return (dx, None, None) + tuple(_middle_grads_flat(ctx.names, G)) + _dir_grads(ctx, G)
+        return (dx, None, None) + tuple(_middle_grads_flat(ctx.names, G)) + _dir_grads(ctx, G) + _iou_grads(ctx, G)
 
 
 class MiddleConvNet(nn.Module):
@@ -470,7 +500,9 @@ class MiddleConvNet(nn.Module):
 
     last_dir_logits = None   # the direction head's latest logits (dir_conv is registered by dir_head=True only)
 
-    def __init__(self, cls_name="Car", dir_head=False):
+    last_iou_logits = None   # the IoU-aware head's latest logits (iou_conv is registered by iou_head=True only)
+
+    def __init__(self, cls_name="Car", dir_head=False, iou_head=False):
         super().__init__()
         g = grid_config(cls_name)
         self._block1_stride = g.block1_stride
@@ -492,6 +524,9 @@ class MiddleConvNet(nn.Module):
         self.reg_conv = ConvMD(2, 768, 14, 1, (1, 1), (0, 0), bn=False, activation=False)
         if dir_head:
             self.dir_conv = ConvMD(2, 768, 2, 1, (1, 1), (0, 0), bn=False, activation=False)
+        if iou_head:
+            self.iou_conv = ConvMD(2, 768, 2, 1, (1, 1), (0, 0), bn=False, activation=False)
+            nn.init.zeros_(self.iou_conv.conv.bias)          # (q starts around 1/2 whatever the features' offset)
         # config.py FEATURE_HEIGHT/WIDTH: car 200x176; ped/cyc 100x120 (although the network emits 200x240,
         # SURVEY.md §8a a8 — kept as the reference has it)
         self.output_shape = [g.H // 2, g.W // 2]
@@ -501,6 +536,7 @@ class MiddleConvNet(nn.Module):
         d.pop("_native_arrays", None)
         d.pop("_nbt", None)
         d.pop("last_dir_logits", None)
+        d.pop("last_iou_logits", None)
         return d
 
     def _tick(self):
@@ -513,10 +549,18 @@ class MiddleConvNet(nn.Module):
 
     def forward(self, x):
         _, _, _, flat = _collect_middle(self)
-        if getattr(self, "dir_conv", None) is not None:       # (same two outputs; the head's logits are kept as last_dir_logits)
+        has_dir, has_iou = getattr(self, "dir_conv", None) is not None, getattr(self, "iou_conv", None) is not None
+        if has_dir or has_iou:       # (same two outputs; the heads' logits are kept as last_dir_logits / last_iou_logits)
             if E.X3["on"]:
-                raise ValueError("dir_head: the fp32x3 mode is not supported with the direction head (DESIGN.md 1i)")
-            prob, reg, self.last_dir_logits = _MiddleFn.apply(x, self, self.training, *flat, *_dir_params(self))
+                raise ValueError(f"{'dir_head' if has_dir else 'iou_head'}: the fp32x3 mode is not supported with the "
+                                 f"{'direction' if has_dir else 'IoU-aware'} head (DESIGN.md {'1i' if has_dir else '1l'})")
+            extra = (_dir_params(self) if has_dir else []) + (_iou_params(self) if has_iou else [])
+            out = list(_MiddleFn.apply(x, self, self.training, *flat, *extra))
+            prob, reg = out[0], out[1]
+            if has_dir:
+                self.last_dir_logits = out[2]
+            if has_iou:
+                self.last_iou_logits = out[-1]
         else:
             prob, reg = _MiddleFn.apply(x, self, self.training, *flat)
         self._tick()
@@ -624,10 +668,10 @@ class _DetectorFn(torch.autograd.Function):
         # requires grad stands for them, and the backward assigns / adds the gradients to .grad itself (what the direct_grads
         # mode did anyway): wrapping and unwrapping 104 inputs and their AccumulateGrad edges cost ~0.4 ms of host time a step
         ctx.anchor = len(flat) == 1
-        dirp = None
-        if rpn.dir_head and not ctx.anchor:       # (the direction head's two parameters travel last)
-            dirp, flat = tuple(f.detach() for f in flat[-2:]), flat[:-2]
-        ctx.dir_head = dirp is not None
+        dirp = ioup = None
+        if not ctx.anchor:       # (the direction head's two parameters travel last, the IoU-aware head's behind them)
+            dirp, ioup, flat = _peel_site_heads(bool(rpn.dir_head), bool(rpn.iou_head), flat)
+        ctx.dir_head, ctx.iou_head = dirp is not None, ioup is not None
         if ctx.anchor:
             flat = rpn._flat_params()
             vparams = flat[:nv]
@@ -721,7 +765,7 @@ class _DetectorFn(torch.autograd.Function):
                     _lib.call("vn_cast_rows", vw.data_ptr(), _lib.VN_F32, 128, vw.shape[0], 128, vw_rows.data_ptr(),
                               _lib.VN_BF16, 128, 0, E.stream())
                 sparse = (coord, vw_rows)
-            out = N.middle_forward(dense, P, Bf, mid._block1_stride, training, mode, sparse=sparse, dir_head=dirp)
+            out = N.middle_forward(dense, P, Bf, mid._block1_stride, training, mode, sparse=sparse, dir_head=dirp, iou_head=ioup)
         st = out[-1]
         ctx.saved = (feature, coord, stats, wst, vparams, st, P, names)
         ctx.reducer = rpn.grad_reducer
@@ -729,8 +773,9 @@ class _DetectorFn(torch.autograd.Function):
         return out[:-1]
 
     @staticmethod
-    def backward(ctx, d_prob, d_reg, d_dir=None):
+    def backward(ctx, d_prob, d_reg, *d_heads):
         _need_training(ctx.training)
+        d_dir, d_iou = _head_out_grads(ctx, d_heads)
         feature, coord, stats, wst, vparams, st, P, names = ctx.saved
         red = ctx.reducer
         if ctx.native:
@@ -751,13 +796,13 @@ class _DetectorFn(torch.autograd.Function):
                 red.grad_ready(f"middle_rpn.{name}.batch_norm.weight", g["gamma"])
                 red.grad_ready(f"middle_rpn.{name}.batch_norm.bias", g["beta"])
         with _lib.on_device(d_prob.device):
-            G, d_dense = N.middle_backward(st, d_prob.float(), d_reg.float(), P, need_dx=True, on_grads=on_grads, d_dir=d_dir)
+            G, d_dense = N.middle_backward(st, d_prob.float(), d_reg.float(), P, need_dx=True, on_grads=on_grads, d_dir=d_dir, d_iou=d_iou)
             d_vw = d_dense if torch.is_tensor(d_dense) else gather_rows(d_dense, coord, feature.shape[0], 128)
             vg = featnet_backward(feature, wst, stats, d_vw, vparams, training=ctx.training)
             if red is not None:
                 for key, g in zip(VFE_KEYS, vg):
                     red.grad_ready(key, g)
-        return (None, None, None, None, None) + tuple(vg) + tuple(_middle_grads_flat(names, G)) + _dir_grads(ctx, G)
+        return (None, None, None, None, None) + tuple(vg) + tuple(_middle_grads_flat(names, G)) + _dir_grads(ctx, G) + _iou_grads(ctx, G)
 
 
 def _detector_backward_segments(cfg, arr, heads, dp, dr, prob, dense, coord, vw_rows, K, ws, ws_bytes, garr, dhw, dhb, d_in,
@@ -1025,10 +1070,15 @@ class RPN3D(nn.Module):
     # int >= 0: an anchor with at most that many voxels over its footprint is ignored by the loss and is never a detection
     anchor_area_threshold = None
     last_anchor_mask = None  # the latest (B,h,w,2) uint8 mask: detached, no synchronisation
+    # the IoU-aware confidence head (voxelnet_amd/iou_head.py): False = nothing is registered or launched
+    iou_head, iou_head_weight, iou_head_metric, iou_rectify = False, 1.0, "3d", 0.5
+    last_iou_head = None     # the latest (L, mae) pair of the head's loss: detached device scalars (last_iou is the regression term's)
+    last_iou_logits = None   # the head's logits (B,2,h,w) of the latest detect(), with the autograd graph in training
 
     def __init__(self, cls_name="Car", alpha=ALPHA, beta=BETA, sigma=SIGMA, *, cls_loss="bce", focal_alpha=0.25, focal_gamma=2.0,
                  yaw_loss="diff", iou_loss=None, iou_weight=1.0, iou_metric="3d", target_assign="reference", dir_head=False,
-                 dir_weight=0.2, dir_offset=math.pi / 4, anchor_area_threshold=None):
+                 dir_weight=0.2, dir_offset=math.pi / 4, anchor_area_threshold=None, iou_head=False, iou_head_weight=1.0,
+                 iou_head_metric="3d", iou_rectify=0.5):
         super().__init__()
         from .targets import ASSIGN_KINDS
         if target_assign not in ASSIGN_KINDS:
@@ -1047,8 +1097,13 @@ class RPN3D(nn.Module):
             from .dir_head import check_spec
             check_spec(dir_weight, dir_offset)
             self.dir_weight, self.dir_offset = dir_weight, dir_offset
+        self.iou_head = bool(iou_head)
+        if self.iou_head:
+            from .iou_head import check_spec as iou_head_check
+            iou_head_check(iou_head_weight, iou_rectify, iou_head_metric)
+            self.iou_head_weight, self.iou_head_metric, self.iou_rectify = iou_head_weight, iou_head_metric, iou_rectify
         self.feature_net = FeatureLearningNet(cls_name)
-        self.middle_rpn = MiddleConvNet(cls_name, dir_head=self.dir_head)
+        self.middle_rpn = MiddleConvNet(cls_name, dir_head=self.dir_head, iou_head=self.iou_head)
         self.rpn_output_shape = self.middle_rpn.output_shape
         self.anchors = None      # model.py:295 utils.generate_anchors(): built with the first target generation
         self.target_fn = None    # callable(label, rpn_output_shape) -> (pos, neg, targets)
@@ -1065,7 +1120,7 @@ class RPN3D(nn.Module):
     # `torch.save(model)` (the reference's checkpoint format, train.py:24/27) or `copy.deepcopy(model)`.
     _RUNTIME_KEYS = ("_side", "_tgt_stream", "_ws_pool", "_flat_grads", "_targets", "_decoder", "_nbt", "_flat_param_list", "_net_ctx",
                      "_named_param_list", "_anchor_t", "_bucket_views", "_mg_cache", "_step_sc", "_nbt_table", "last_iou", "last_dir",
-                     "last_dir_logits", "_maskers", "last_anchor_mask")
+                     "last_dir_logits", "_maskers", "last_anchor_mask", "last_iou_head", "last_iou_logits")
 
     def __getstate__(self):
         d = self.__dict__.copy()
@@ -1205,7 +1260,16 @@ class RPN3D(nn.Module):
 
     def _dir_decode(self, kw, dec=None):
         """`kw` (BoxDecoder keyword arguments) with the direction head's logits of the latest detect() and its offset added
-        when the head is on; the decode then has to read the maps by site (predict.TRAINED_DECODE)"""
+        when the head is on; the decode then has to read the maps by site (predict.TRAINED_DECODE).  The IoU-aware head's
+        logits and iou_rectify travel the same way, under the same rule."""
+        if self.iou_head:
+            layout = kw.get("layout", dec.layout if dec is not None else "flat")
+            if layout != "site":
+                raise ValueError(f"iou_head: the IoU-aware head's logits are laid out by site; decode with layout='site' "
+                                 f"(predict.TRAINED_DECODE), not {layout!r}")
+            if self.last_iou_logits is None:
+                raise _lib.VoxelnetHipError("iou_head: no logits yet — decode after detect() / forward()")
+            kw = dict(kw, iou_logits=self.last_iou_logits.detach(), iou_rectify=float(self.iou_rectify))
         if not self.dir_head:
             return kw
         layout = kw.get("layout", dec.layout if dec is not None else "flat")
@@ -1259,6 +1323,8 @@ class RPN3D(nn.Module):
             raise ValueError("evaluate: `ema` averages another module")
         if self.dir_head and kw.get("layout", dec.layout) != "site":
             raise ValueError("evaluate: with dir_head the decode must read the maps by site: decode=predict.TRAINED_DECODE")
+        if self.iou_head and kw.get("layout", dec.layout) != "site":
+            raise ValueError("evaluate: with iou_head the decode must read the maps by site: decode=predict.TRAINED_DECODE")
         was_training = self.training
         self.eval()
         try:
@@ -1332,6 +1398,9 @@ class RPN3D(nn.Module):
         if self.dir_head:
             self._dir_check(_mode())
             flat = flat + _dir_params(self.middle_rpn)
+        if self.iou_head:
+            self._iou_head_check(_mode())
+            flat = flat + _iou_params(self.middle_rpn)
         if (self._native_ok(_mode()) and self.training and self.direct_grads and torch.is_grad_enabled() and feature.is_cuda
                 and self._all_need_grad(flat)):
             prob, reg = _DetectorFn.apply(feature, coord, bs, self, self.training, self._anchor(feature.device))
@@ -1344,8 +1413,18 @@ class RPN3D(nn.Module):
             prob, reg = out[0], out[1]
             if self.dir_head:
                 self.last_dir_logits = out[2]
+            if self.iou_head:
+                self.last_iou_logits = out[-1]
         self._tick()
         return prob, reg
+
+    def _iou_head_check(self, mode):
+        """_dir_check for the IoU-aware head (out of scope): the fp32x3 mode and a gradient reducer"""
+        if mode == "fp32x3" or E.X3["on"]:
+            raise ValueError("iou_head: the fp32x3 mode is not supported with the IoU-aware head; use 'bf16' or 'fp32'")
+        if self.grad_reducer is not None:
+            raise ValueError("iou_head: a grad_reducer is not supported with the IoU-aware head: the DDP bucket plan does not "
+                             "know its two parameters")
 
     def _dir_check(self, mode):
         """ValueError for what the direction head does not run with (out of scope): the fp32x3 mode, and a
@@ -1362,7 +1441,8 @@ class RPN3D(nn.Module):
         path: every other configuration (bf16x3, other depths, native_executor = False, dir_head = True: the direction head
         rides on the per-layer orchestration) trains through the per-layer orchestration with the 104
         parameters (and the head's two) as autograd inputs."""
-        return bool(self.native_executor) and not self.dir_head and not E.is_split(mode) and 9 <= self.feature_net._grid.D <= 12
+        return (bool(self.native_executor) and not self.dir_head and not self.iou_head          # (iou_head: DESIGN.md 1l, likewise)
+                and not E.is_split(mode) and 9 <= self.feature_net._grid.D <= 12)
 
     def _all_need_grad(self, flat):
         return all(p.requires_grad for p in flat)
@@ -1385,7 +1465,9 @@ class RPN3D(nn.Module):
         iou_weight * L_iou (the anchors are the target generator's) is added to loss and to reg_loss and
         the pair (L_iou, mean_iou) is kept, detached, as self.last_iou.  With dir_head on, dir_weight * L_dir (DESIGN.md 1i;
         the logits are last_dir_logits of the detect() before) is added to loss and to cls_loss, and (L_dir, acc) is kept,
-        detached, as self.last_dir."""
+        detached, as self.last_dir.  With iou_head on, iou_head_weight * L (the logits are last_iou_logits, the
+        target is the IoU of the box delta_out decodes to, a constant) is added to loss and to cls_loss, and (L, mae) is kept,
+        detached, as self.last_iou_head."""
         dev = prob_out.device
         spec, iou = self._loss_spec(), self._iou_spec()
 
@@ -1396,7 +1478,7 @@ class RPN3D(nn.Module):
         pos, tgt = f32(pos_equal_one), f32(targets)
         out = _LossFn.apply(prob_out, delta_out, pos, f32(neg_equal_one), tgt,
                             float(self.alpha), float(self.beta), float(self.sigma), spec)
-        if iou is None and not self.dir_head:
+        if iou is None and not self.dir_head and not self.iou_head:
             return out
         gen = self._target_generator(dev)
         if gen.n_anchors != delta_out.shape[2] * delta_out.shape[3] * 2:
@@ -1417,6 +1499,17 @@ class RPN3D(nn.Module):
             l_dir, acc = rpn_dir_loss(logits, pos, tgt, gen._anchors_dev, float(self.dir_offset))
             self.last_dir = (l_dir.detach(), acc)
             term = float(self.dir_weight) * l_dir
+            out = (out[0] + term, out[1] + term) + tuple(out[2:])
+        if self.iou_head:
+            # iou_head_weight * L joins loss and cls_loss; the target is a constant, delta_out gets no gradient
+            from .iou_head import check_spec as iou_head_check, rpn_iou_head_loss
+            iou_head_check(self.iou_head_weight, self.iou_rectify, self.iou_head_metric)
+            logits = self.last_iou_logits
+            if logits is None or logits.shape[0] != delta_out.shape[0] or tuple(logits.shape[2:]) != tuple(delta_out.shape[2:]):
+                raise _lib.VoxelnetHipError("iou_head: loss() needs the logits of the detect() that produced these maps")
+            l_head, mae = rpn_iou_head_loss(logits, delta_out, pos, tgt, gen._anchors_dev, self.iou_head_metric)
+            self.last_iou_head = (l_head.detach(), mae)
+            term = float(self.iou_head_weight) * l_head
             out = (out[0] + term, out[1] + term) + tuple(out[2:])
         return out
 
@@ -1470,7 +1563,8 @@ class RPN3D(nn.Module):
         Whatever the fused call does not cover — per-layer orchestration, eval mode, target_fn, gradient accumulation, a
         reducer without a communication stream, bench.py's per-section timer, the rotated-IoU term (iou_loss set: it is
         not part of vnStep), the direction head (dir_head=True: it runs on the per-layer orchestration, outside
-        the native executor) — takes the separate calls, same results."""
+        the native executor), the IoU-aware head (iou_head=True, likewise) — takes the separate
+        calls, same results."""
         from .optim import ClipSGD
         mode = _mode()
         spec = self._loss_spec()            # (checked before anything is launched)

@@ -51,7 +51,7 @@ def _dir_rows(rows, mode, what):
     return rows.t.view(-1, rows.t.shape[-1])
 
 
-def middle_forward(dense, P, Bf, block1_stride, training, mode, sparse=None, dir_head=None):
+def middle_forward(dense, P, Bf, block1_stride, training, mode, sparse=None, dir_head=None, iou_head=None):
     """dense: Rows (B,D,H,W,128[hi|lo]).  P[name] = {weight,bias,gamma,beta}; Bf[name] =
     {running_mean,running_var}; P['heads'] = {weight (16,768,1,1), bias (16)}.
     sparse = (coord (K,4) int64, vw_rows (K,128) operand dtype): the occupied sites of `dense`; the first
@@ -59,6 +59,8 @@ def middle_forward(dense, P, Bf, block1_stride, training, mode, sparse=None, dir
     (K,128) voxel gradient instead of a dense grid gradient.
     dir_head = (weight (2,768[,1,1]), bias (2)) fp32: the direction head runs on the concatenation after the
     heads, its logits (B,2,h,w) fp32 are a third output in front of the state, and the state keeps the concatenation.
+    iou_head = (weight, bias) likewise: the IoU-aware confidence head, its logits the output behind the
+    direction head's; with both heads on the two forwards are ONE read of the concatenation (iou_head.site_heads_forward).
     Returns prob (B,2,h,w) after sigmoid, reg (B,14,h,w) fp32 NCHW, and the saved state."""
     specs = dict(layer_table(block1_stride))
     st = MiddleState()
@@ -109,24 +111,33 @@ def middle_forward(dense, P, Bf, block1_stride, training, mode, sparse=None, dir
     st.prob = prob.detach()     # an alias, NOT the returned tensor: saving an autograd.Function's own output on its ctx is a
                                 # reference cycle that only the cyclic GC frees (720 MB of dense grid per step piled up)
     st.fmap = (hf, wf)
-    if dir_head is not None:
+    on = [h for h in (dir_head, iou_head) if h is not None]
+    if not on:
+        return prob, reg, st
+    st.cat = cat
+    st.dir_w = dir_head[0] if dir_head is not None else None
+    st.iou_w = iou_head[0] if iou_head is not None else None
+    rows = _dir_rows(cat, mode, "the concatenation")
+    if len(on) == 2:
+        from .iou_head import site_heads_forward
+        logits = site_heads_forward(rows, [h[0] for h in on], [h[1] for h in on], B)
+    else:
         from .dir_head import dir_head_forward
-        st.cat, st.dir_w = cat, dir_head[0]
-        logits = dir_head_forward(_dir_rows(cat, mode, "the concatenation"), dir_head[0], dir_head[1], B).view(B, 2, hf, wf)
-        return prob, reg, logits, st
-    return prob, reg, st
+        logits = (dir_head_forward(rows, on[0][0], on[0][1], B),)
+    return (prob, reg) + tuple(z.view(B, 2, hf, wf) for z in logits) + (st,)
 
 
-def middle_backward(st, d_prob, d_reg, P, need_dx=True, on_grads=None, d_dir=None):
+def middle_backward(st, d_prob, d_reg, P, need_dx=True, on_grads=None, d_dir=None, d_iou=None):
     """-> ({name: {weight,bias,gamma,beta}}, d_dense Rows (plain f32/bf16) or None).
     on_grads(layer_name, grads): called as soon as a layer's parameter gradients exist (DDP bucketing).
     d_dir (B,2,h,w) fp32, for a forward that ran the direction head: its backward adds to the concatenation's gradient at
-    the rows where d_dir is not zero, right after the heads' data gradient wrote it; G["dir_head"] = {weight, bias}."""
+    the rows where d_dir is not zero, right after the heads' data gradient wrote it; G["dir_head"] = {weight, bias}.
+    d_iou: the same for the IoU-aware head, after the direction head's; G["iou_head"]."""
     with E._x3_as_saved(st):
-        return _middle_backward(st, d_prob, d_reg, P, need_dx, on_grads, d_dir)
+        return _middle_backward(st, d_prob, d_reg, P, need_dx, on_grads, d_dir, d_iou)
 
 
-def _middle_backward(st, d_prob, d_reg, P, need_dx=True, on_grads=None, d_dir=None):
+def _middle_backward(st, d_prob, d_reg, P, need_dx=True, on_grads=None, d_dir=None, d_iou=None):
     mode = st.mode
     split = E.is_split(mode)
     L = st.layers
@@ -141,11 +152,13 @@ def _middle_backward(st, d_prob, d_reg, P, need_dx=True, on_grads=None, d_dir=No
     G["heads"], d_cat = E.layer_backward(L["heads"], d_rows, P["heads"], mode)
     if on_grads is not None:
         on_grads("heads", G["heads"])
-    if d_dir is not None:
-        from .dir_head import dir_head_backward
-        dw, db = dir_head_backward(d_dir.contiguous().float().view(B, 2, hf * wf), _dir_rows(st.cat, mode, "the concatenation"),
-                                   st.dir_w, _dir_rows(d_cat, mode, "the concatenation's gradient"))
-        G["dir_head"] = {"weight": dw.view_as(st.dir_w), "bias": db}
+    for key, d_z, w in (("dir_head", d_dir, getattr(st, "dir_w", None)), ("iou_head", d_iou, getattr(st, "iou_w", None))):
+        if d_z is None:
+            continue
+        from .dir_head import dir_head_backward          # (each call accumulates onto d_cat in place)
+        dw, db = dir_head_backward(d_z.contiguous().float().view(B, 2, hf * wf), _dir_rows(st.cat, mode, "the concatenation"),
+                                   w, _dir_rows(d_cat, mode, "the concatenation's gradient"))
+        G[key] = {"weight": dw.view_as(w), "bias": db}
 
     def dslice(off):
         return Rows(d_cat.t[..., off:off + 256], 256)

@@ -18,7 +18,11 @@ anchor's logit names (`dir_head.rectify_yaw`); the tail is then composed from th
 rectification, `nms_device`, a gather of the kept rows — and needs layout="site".
 
 `anchor_mask=`: a (B,h,w,2) uint8 mask of `anchor_mask.AnchorMasker` — an anchor without voxels under
-its footprint scores 0 in a copy of the probability map (`vn_anchor_mask_probs`), and every tail above runs unchanged on it."""
+its footprint scores 0 in a copy of the probability map (`vn_anchor_mask_probs`), and every tail above runs unchanged on it.
+
+`iou_logits=`: the IoU-aware head's map (B,2,h,w) — every anchor is scored by p^(1 - iou_rectify) *
+sigmoid(z)^iou_rectify in a copy of the probability map (`iou_head.rectify_probs`), made BEFORE the anchor mask edits that
+copy; every tail above runs unchanged on it, score_thres applies to the rectified score, and it needs layout="site"."""
 import ctypes
 import math
 
@@ -119,6 +123,23 @@ class BoxDecoder:
             raise ValueError(f"{what}: anchor_mask {tuple(anchor_mask.shape)} is not a mask of {probs.shape[0]} x {self.n_anchors} anchors")
         return mask_probs(probs.detach().float(), anchor_mask, self.n_anchors, lay)
 
+    def _rectified(self, probs, iou_logits, iou_rectify, layout, what):
+        """the copy of probs in which every anchor scores p^(1 - iou_rectify) * sigmoid(iou_logits)^iou_rectify:
+        every tail below — and the anchor mask, which comes after it — runs unchanged on it"""
+        from .iou_head import rectify_probs
+        lay = self.layout if layout is None else layout
+        if _layout(lay) != _lib.VN_DETECT_SITE:
+            raise ValueError(f"iou_logits: the IoU-aware head's logits are laid out by site; layout must be 'site', not {lay!r}")
+        if not (torch.is_tensor(probs) and probs.is_cuda):
+            raise _lib.VoxelnetHipError(f"{what}: probs / deltas must be HIP tensors (no CPU path)")
+        if not (torch.is_tensor(iou_logits) and iou_logits.is_cuda):
+            raise _lib.VoxelnetHipError(f"{what}: iou_logits must be a HIP tensor (no CPU path)")
+        B = probs.shape[0]
+        if probs.numel() != B * self.n_anchors or iou_logits.shape[0] != B or iou_logits.numel() != B * self.n_anchors:
+            raise ValueError(f"iou_logits {tuple(iou_logits.shape)} / probs {tuple(probs.shape)} do not match {B} samples of "
+                             f"{self.n_anchors} anchors")
+        return rectify_probs(probs, iou_logits, iou_rectify).view(probs.shape)
+
     def _decode_dir(self, probs, deltas, score_thres, nms_thres, top_k, nms, pre_nms_top_k, layout, dir_logits, dir_offset):
         """decode_device with the direction head's logits: vn_rpn_select_decode_layout -> vn_boxes_rectify_yaw -> vn_box_nms ->
         a gather of the kept rows.  The yaw changes by multiples of pi only, so the candidates, the kept set and the scores
@@ -150,7 +171,8 @@ class BoxDecoder:
         return boxes, scores, kc
 
     def decode_device(self, probs, deltas, score_thres=SCORE_THRES, nms_thres=NMS_THRES, top_k=NMS_POST_TOPK, nms="standup",
-                      pre_nms_top_k=None, layout=None, dir_logits=None, dir_offset=math.pi / 4, anchor_mask=None):
+                      pre_nms_top_k=None, layout=None, dir_logits=None, dir_offset=math.pi / 4, anchor_mask=None, iou_logits=None,
+                      iou_rectify=0.5):
         """probs (B,2,h,w), deltas (B,14,h,w) fp32 device tensors -> (boxes (B,top_k,7) f32, scores (B,top_k) f32, counts (B,)
         int32) ON THE DEVICE, enqueued on the current stream without any host synchronisation: per sample the first
         counts[b] rows are the kept detections in descending score, the rest is zero.  What evaluate.DetectionEvaluator
@@ -164,7 +186,12 @@ class BoxDecoder:
         becomes wrap_pi(r - dir_offset) + dir_offset + pi * [logit > 0] through the composed tail; apart from that
         column the kept set and the scores are the ones of the call without it.
         anchor_mask (None: nothing new is allocated or launched): a (B,h,w,2) uint8 mask (anchor_mask.AnchorMasker) —
-        every path above runs unchanged on a copy of probs in which a masked-out anchor scores 0; needs score_thres > 0."""
+        every path above runs unchanged on a copy of probs in which a masked-out anchor scores 0; needs score_thres > 0.
+        iou_logits (None: nothing new is allocated or launched): the IoU-aware head's (B,2,h,w) map, layout "site"
+        only — every path above, the anchor mask included, runs on a copy of probs in which an anchor scores
+        p^(1 - iou_rectify) * sigmoid(z)^iou_rectify, iou_rectify in [0, 1]; score_thres applies to that score."""
+        if iou_logits is not None:          # (before the mask: 0^0 = 1 would bring a masked-out anchor back at iou_rectify = 1)
+            probs = self._rectified(probs, iou_logits, iou_rectify, layout, "predict")
         if anchor_mask is not None:
             probs = self._masked(probs, anchor_mask, score_thres, layout, "predict")
         if dir_logits is not None:
@@ -204,13 +231,16 @@ class BoxDecoder:
         return boxes, scores, counts
 
     def candidates_device(self, probs, deltas, score_thres, pre_nms_top_k, layout=None, dir_logits=None, dir_offset=math.pi / 4,
-                          anchor_mask=None):
+                          anchor_mask=None, iou_logits=None, iou_rectify=0.5):
         """The first half of the tail on its own (vn_rpn_select_decode): per sample the min(M, pre_nms_top_k) best of the M
         candidates with p >= score_thres, decoded, in descending (score, flat index) order -> (boxes (B,pre,7) f32, scores
         (B,pre) f32, flat anchor indices (B,pre) int32, counts (B,) int32) on the device; rows past the count are zero.
         layout "site" (vn_rpn_select_decode_layout): the index is the anchor index n = 2 * site + rotation of the target maps.
         dir_logits (layout "site" only): the candidates' yaw is rectified by the direction head's map (dir_head.rectify_yaw).
-        anchor_mask: as decode_device's — a masked-out anchor is never a candidate."""
+        anchor_mask: as decode_device's — a masked-out anchor is never a candidate.
+        iou_logits / iou_rectify: as decode_device's — the candidates are picked, ordered and scored by the rectified score."""
+        if iou_logits is not None:
+            probs = self._rectified(probs, iou_logits, iou_rectify, layout, "candidates")
         if anchor_mask is not None:
             probs = self._masked(probs, anchor_mask, score_thres, layout, "candidates")
         lay = _layout(self.layout if layout is None else layout)
@@ -245,10 +275,11 @@ class BoxDecoder:
         return boxes, scores, idx, counts
 
     def __call__(self, probs, deltas, score_thres=SCORE_THRES, nms_thres=NMS_THRES, top_k=NMS_POST_TOPK, nms="standup",
-                 pre_nms_top_k=None, layout=None, dir_logits=None, dir_offset=math.pi / 4, anchor_mask=None):
+                 pre_nms_top_k=None, layout=None, dir_logits=None, dir_offset=math.pi / 4, anchor_mask=None, iou_logits=None,
+                 iou_rectify=0.5):
         """probs (B,2,h,w), deltas (B,14,h,w) fp32 device tensors -> ([boxes (n_i,7) f32 numpy], [scores (n_i,) f32 numpy])"""
         boxes, scores, counts = self.decode_device(probs, deltas, score_thres, nms_thres, top_k, nms, pre_nms_top_k, layout,
-                                                   dir_logits, dir_offset, anchor_mask)
+                                                   dir_logits, dir_offset, anchor_mask, iou_logits, iou_rectify)
         B = boxes.shape[0]
         cnt = counts.cpu().numpy()
         bh, sh = boxes.cpu().numpy(), scores.cpu().numpy()
