@@ -1425,6 +1425,64 @@ int vn_anchor_mask(const int64_t *coord, int64_t K, int32_t B, int32_t H, int32_
 int vn_anchor_mask_probs(const float *probs, const uint8_t *mask, int32_t B, int32_t n_anchors, int32_t layout, float *out,
                          vnStream stream);
 
+/* ---- test-time augmentation and box voting (csrc/tta.hip; rules: DESIGN.md section 1m) ---------------------------
+ * What an evaluation does after the greedy NMS above has picked one box per cluster.  Both calls are asynchronous on
+ * `stream`, never synchronise with the host, use no floating-point atomics and give the same bits from run to run.
+ *
+ * vn_pool_merge extends vn_rpn_select_decode: the candidate pools of V VIEWS of one batch (the frame flipped, rotated
+ * and scaled by vn_augment_compose, each view decoded on its own) become one pool in one priority order, in the frame's
+ * own coordinates — what vn_box_nms takes.
+ *   boxes [V,B,K,7], scores [V,B,K] float32, counts [V,B] int32 (device): view v's rows k < min(max(counts[v,b], 0), K).
+ *   views [V,3] float64 ON THE HOST, read during the call: fy (+1.0 or -1.0), angle, factor — the view's cloud was
+ *         (x, y) -> (x, fy*y) -> turned by -angle -> times factor (augment.compose_affine's stages 2-4, no translation).
+ *   Per sample the rows with a score that is not NaN come out in descending score (-0.0 == +0.0), equal scores with the
+ *   SMALLER src = v*K + k first: out_boxes [B,V*K,7], out_scores [B,V*K], out_src [B,V*K] int32, out_counts [B] int32.
+ *   Rows beyond out_counts[b] are left untouched.  Each box is mapped back by the exact inverse, float64 on the widened
+ *   float32 fields with one float32 store:
+ *       q[0..5] = (x', y', z', h', w', l') / factor;   c = cos(angle), s = sin(angle)   (host libm)
+ *       X = q0*c - q1*s;   Y = q0*s + q1*c;   r = r' + angle;   out = (X, fy*Y, q2, q3, q4, q5, fy*r)   (r is not wrapped)
+ *   A view with fy = +1, angle = 0 and factor = 1 copies its rows bit for bit.
+ *   Limits: 1 <= V <= VN_TTA_MAX_VIEWS, B >= 1, K >= 1, V*K <= VN_DETECT_MAX_PRE; fy is +1 or -1, angle finite, factor
+ *   finite and > 0.  One workgroup per sample: 64-bit keys (score bits | ~src) sorted in LDS, then a gather.
+ *
+ * vn_box_vote extends vn_box_nms: every kept row is replaced by the weighted mean of its cluster.
+ *   boxes [B,K,7], scores [B,K], counts [B]: the pool vn_box_nms walked; keep_idx [B,P], keep_counts [B]: what it wrote.
+ *   src [B,K] int32 or NULL, rows_per_view: row j belongs to view src[j] / rows_per_view (vn_pool_merge's out_src and K); a
+ *   negative src or a view outside [0,V) takes no part in the view mean.  NULL: every row is view 0, and V must be 1.
+ *   With n = clamp(counts[b], 0, K), m = clamp(keep_counts[b], 0, P), for each t < m, i = keep_idx[b,t]:
+ *     an i outside [0,n) or a row i with a non-finite field or h, w, l <= 0 is skipped (vn_box_nms never writes one);
+ *     members: row i (u_i = 1) and every other valid row j < n with u_j = IoU_bev(i,j) >= vote_thres (the pair function of
+ *     vn_box_iou_rotated, float64 on the widened rows); weight w_j = s_j (VN_VOTE_W_SCORE) or s_j * u_j (VN_VOTE_W_SCORE_IOU);
+ *     fields 0-5 = sum w_j q_jk / sum w_j;  yaw = r_i + sum w_j d_j / sum w_j with d_j = (r_j - r_i) - pi*floor((r_j - r_i)/pi + 0.5)
+ *     (a member that points the other way counts as the same axis; the kept row's heading stays); float64 sums, one
+ *     float32 store per field; when sum w_j is not > 0 the kept row is copied unchanged;
+ *     score: the kept row's (VN_VOTE_S_KEEP), or the mean over the V views of the best member score of each view, 0 for
+ *     a view without a member, summed in float64 in view order, divided by V, stored as float32 (VN_VOTE_S_VIEW_MEAN).
+ *   out_boxes [B,P,7], out_scores [B,P], out_members [B,P] (the member count), out_counts [B]: the rows in descending
+ *   output score, equal scores by t ascending (a NaN score behind every number); rows beyond out_counts[b] untouched.
+ *   Limits: 1 <= B <= 65535, 1 <= K <= VN_DETECT_MAX_PRE, 1 <= P <= VN_PREDICT_MAX_TOPK, 1 <= V <= VN_TTA_MAX_VIEWS,
+ *   vote_thres finite and > 0, src == NULL only with V == 1, else rows_per_view >= 1.
+ *
+ * Both: VN_EINVAL, before anything is launched, for a size or value outside the limits, an unknown mode or a null pointer
+ * (src excepted); the workspace queries return 0 for sizes the call refuses; VN_EWORKSPACE for a smaller workspace. */
+#define VN_TTA_MAX_VIEWS 8
+#define VN_VOTE_W_SCORE 0        /* w_j = s_j */
+#define VN_VOTE_W_SCORE_IOU 1    /* w_j = s_j * IoU(i,j) */
+#define VN_VOTE_S_KEEP 0         /* the kept row's score */
+#define VN_VOTE_S_VIEW_MEAN 1    /* mean over the V views of the best member score of that view (0 for a view without one) */
+size_t vn_pool_merge_workspace_bytes(int32_t V, int32_t B, int32_t K);
+int vn_pool_merge(const float *boxes /*[V,B,K,7]*/, const float *scores /*[V,B,K]*/, const int32_t *counts /*[V,B]*/,
+                  const double *views /*[V,3], host*/, int32_t V, int32_t B, int32_t K, float *out_boxes /*[B,V*K,7]*/,
+                  float *out_scores /*[B,V*K]*/, int32_t *out_src /*[B,V*K]*/, int32_t *out_counts /*[B]*/, void *workspace,
+                  size_t workspace_bytes, vnStream stream);
+size_t vn_box_vote_workspace_bytes(int32_t B, int32_t K, int32_t P, int32_t V);
+int vn_box_vote(const float *boxes /*[B,K,7]*/, const float *scores /*[B,K]*/, const int32_t *counts /*[B]*/,
+                const int32_t *src /*[B,K] or NULL*/, int32_t rows_per_view, const int32_t *keep_idx /*[B,P]*/,
+                const int32_t *keep_counts /*[B]*/, int32_t B, int32_t K, int32_t P, int32_t V, double vote_thres,
+                int32_t weight_mode, int32_t score_mode, float *out_boxes /*[B,P,7]*/, float *out_scores /*[B,P]*/,
+                int32_t *out_members /*[B,P]*/, int32_t *out_counts /*[B]*/, void *workspace, size_t workspace_bytes,
+                vnStream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -164,6 +164,9 @@ VN_NMS_STANDUP, VN_NMS_ROTATED = 0, 1       # vn_box_nms' / vn_rpn_detect's `mod
 VN_DETECT_MAX_PRE, VN_PREDICT_MAX_TOPK = 4096, 64
 VN_DETECT_FLAT, VN_DETECT_SITE = 0, 1       # vn_rpn_select_decode_layout's / vn_rpn_detect_layout's `layout`
 VN_ASSIGN_STANDUP, VN_ASSIGN_ROTATED = 1, 2       # vn_rpn_targets_iou's `iou_kind`
+VN_TTA_MAX_VIEWS = 8                              # vn_pool_merge's / vn_box_vote's V
+VN_VOTE_W_SCORE, VN_VOTE_W_SCORE_IOU = 0, 1       # vn_box_vote's `weight_mode`
+VN_VOTE_S_KEEP, VN_VOTE_S_VIEW_MEAN = 0, 1        # vn_box_vote's `score_mode`
 
 
 # name -> (restype, argtypes); mirrors include/voxelnet_hip.h one to one
@@ -345,6 +348,11 @@ SIGNATURES = {
     "vn_anchor_mask_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32, c_i32]),
     "vn_anchor_mask": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "vn_anchor_mask_probs": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    "vn_pool_merge_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32]),
+    "vn_pool_merge": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "vn_box_vote_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32, c_i32]),
+    "vn_box_vote": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, ctypes.c_double, c_i32, c_i32,
+                            c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "vn_clip_sgd_workspace_bytes": (c_sz, [c_i32]),
     "vn_clip_sgd": (c_i32, [c_vp, c_i32, c_f32, c_f32, c_i32, c_vp, c_sz, c_vp, c_vp]),
     "vn_clip_adamw_workspace_bytes": (c_sz, [c_i32]),

@@ -1236,15 +1236,87 @@ class RPN3D(nn.Module):
         self.last_anchor_mask = self._anchor_masker(coord.device, dec.anchors).mask(coord, len(voxel_coordinates))
         return self.last_anchor_mask
 
-    def predict(self, data, probs, deltas, summary=False, visual=False, decode=None):
+    def _tta_decode(self, x, device, dec, kw, top_k, tta, own=None):
+        """One batch through test-time augmentation (tta.TestTimeAugment) -> decode_device's (boxes, scores,
+        counts) on the device.  Per view: the identity view takes the batch's own voxel buffers x[2] / x[4] (or `own`, its
+        (prob, delta, head keywords) when the caller has run it already); every other view uploads the raw cloud x[6][b][:, :4],
+        crops it when tta.fov_calib_dir is set, moves it by vn_augment_compose, voxelizes it on the model's grid and runs
+        detect; candidates_device with THAT view's direction / IoU logits and anchor mask.  Then tta.merge_pools, nms_device
+        on the merged pool and tta.vote_device (tta.vote None: a gather of the kept rows).  kw: decode_device's keyword
+        arguments score_thres, nms, nms_thres, pre_nms_top_k, layout.  Must run in eval mode under no_grad."""
+        from . import predict as PR
+        from .tta import TestTimeAugment, merge_pools, vote_device
+        from .voxelize import voxelize_device_async
+        if not isinstance(tta, TestTimeAugment):
+            raise ValueError(f"tta must be a tta.TestTimeAugment, not {tta!r}")
+        kw = dict(kw)
+        score_thres, nms = kw.pop("score_thres", PR.SCORE_THRES), kw.pop("nms", "standup")
+        nms_thres, pre, layout = kw.pop("nms_thres", PR.NMS_THRES), kw.pop("pre_nms_top_k", None), kw.pop("layout", None)
+        if kw:
+            raise ValueError(f"tta: the decode may set score_thres, nms, nms_thres, pre_nms_top_k and layout, not {sorted(kw)}")
+        pre = top_k if pre is None else pre
+        V = len(tta.views)
+        if not (isinstance(pre, (int, np.integer)) and 1 <= pre and pre * V <= _lib.VN_DETECT_MAX_PRE):
+            raise ValueError(f"tta: pre_nms_top_k * len(views) = {pre!r} * {V} must be in [1, {_lib.VN_DETECT_MAX_PRE}]")
+        raw = x[6] if len(x) > 6 else None
+        if any(not v.identity for v in tta.views) and (raw is None or len(raw) == 0 or any(c is None for c in raw)):
+            raise _lib.VoxelnetHipError("tta: every view but the identity needs the frames' raw clouds (x[6])")
+        lkw = {} if layout is None else {"layout": layout}
+        grid, pools, held = self.feature_net._grid, [], []
+        for view in tta.views:
+            if view.identity and own is not None:
+                prob, delta, hkw = own
+                coords = _parts_to(x[4], device) if self.anchor_area_threshold is not None else None
+            else:
+                if view.identity:
+                    feats, coords = _parts_to(x[2], device), _parts_to(x[4], device)
+                else:
+                    handles = []
+                    for b, cloud in enumerate(raw):
+                        pts, keep = tta.view_points(view, cloud, x[0][b], x[5][b] if len(x) > 5 and x[5] is not None else None, device)
+                        handles.append(voxelize_device_async(pts, grid, b, coord_cols=4))
+                        held.append((pts, keep))
+                    feats, coords = [], []
+                    for h in handles:
+                        f, c, _ = h.result()
+                        feats.append(f)
+                        coords.append(c)
+                prob, delta = self.detect(feats, coords)
+                hkw = self._dir_decode(lkw, dec)          # this view's direction / IoU logits
+            if self.anchor_area_threshold is not None:
+                hkw = dict(hkw, anchor_mask=self._decode_mask(dec, coords, device))          # and this view's occupancy
+            pools.append(dec.candidates_device(prob, delta, score_thres, int(pre), **hkw))
+        mb, ms, src, mc = merge_pools([p[0] for p in pools], [p[1] for p in pools], [p[3] for p in pools], tta.views)
+        keep, kc = PR.nms_device(mb, mc, nms, nms_thres, top_k)
+        if tta.vote is None:
+            return PR.gather_kept(mb, ms, keep, kc)
+        return vote_device(mb, ms, mc, keep, kc, tta.vote, src=src, rows_per_view=int(pre), n_views=V)[:3]
+
+    def predict(self, data, probs, deltas, summary=False, visual=False, decode=None, tta=None):
         """model.py:364-441 without the drawing branches: -> (tag, ret_box_3d_score), one array per sample of
         [cls_name, x, y, z, h, w, l, r, score] rows (strings, as np.concatenate makes them at model.py:389-394).
         Decoding, score filter and NMS run on the device (voxelnet_amd/predict.py, csrc/predict.hip).  decode: a dict of
-        BoxDecoder keyword arguments (None: the reference's tail; predict.TRAINED_DECODE for a model trained here)."""
+        BoxDecoder keyword arguments (None: the reference's tail; predict.TRAINED_DECODE for a model trained here).
+        tta: a tta.TestTimeAugment — probs / deltas (and the heads' logits of the detect() that made them)
+        serve the identity view, every other view is run from the raw clouds data[6]; the module must be in eval mode."""
         if summary or visual:
             raise NotImplementedError("the summary / visual branches of RPN3D.predict draw with OpenCV (model.py:396-439): "
                                       "outside the accelerated path")
         dec = self._box_decoder(probs.device)
+        if tta is not None:
+            if self.training:
+                raise _lib.VoxelnetHipError("predict: tta runs further forwards; put the module in eval mode first")
+            kw = dict(decode or {})
+            from .predict import NMS_POST_TOPK
+            top_k = kw.pop("top_k", NMS_POST_TOPK)
+            lkw = {"layout": kw["layout"]} if "layout" in kw else {}
+            with torch.no_grad():
+                boxes, scores, counts = self._tta_decode(data, probs.device, dec, kw, top_k, tta,
+                                                         own=(probs, deltas, self._dir_decode(lkw, dec)))
+            cnt, bh, sh = counts.cpu().numpy(), boxes.cpu().numpy(), scores.cpu().numpy()
+            out = [np.concatenate([np.tile(self.cls_name, int(cnt[b]))[:, np.newaxis], bh[b, :cnt[b]], sh[b, :cnt[b], np.newaxis]],
+                                  axis=-1) for b in range(len(cnt))]
+            return data[0], out
         kw = self._dir_decode(dict(decode or {}), dec)
         if self.anchor_area_threshold is not None:
             # (DESIGN.md 1k: the mask comes from the voxel coordinates of the batch the maps were made from, data[4])
@@ -1289,7 +1361,7 @@ class RPN3D(nn.Module):
             self.anchors = dec.anchors
         return dec
 
-    def evaluate(self, batches, device, evaluator=None, decoder=None, decode=None, ema=None, calib=None):
+    def evaluate(self, batches, device, evaluator=None, decoder=None, decode=None, ema=None, calib=None, tta=None):
         """The validation loop a user would otherwise write around `predict`: every batch tuple of `batches` (the
         7-tuples forward takes; x[1] = label lines) goes through an eval-mode, no_grad forward, BoxDecoder.decode_device
         and evaluator.update — the maps, the decoded boxes and the matching stay on the device, nothing is waited for
@@ -1303,7 +1375,10 @@ class RPN3D(nn.Module):
         calib: None — the protocol of DESIGN.md §1b, as above; or "mean", a directory of <tag>.txt KITTI calibration files,
         or a callable tag -> (P2, Tr_velo_to_cam, R0_rect): KITTI's image-plane protocol (§1b-bis).  The evaluator is then an
         evaluate.KittiDetectionEvaluator (default: a new one); x[0]'s tags pick each frame's calibration and are
-        remembered for its write_results."""
+        remembered for its write_results.
+        tta: None — every path above exactly as it is; or a tta.TestTimeAugment: every batch is run once per
+        view from its raw clouds x[6], the views' candidates are merged, suppressed and voted on the device (`_tta_decode`);
+        `decode` may then set score_thres, nms, nms_thres, pre_nms_top_k (times the number of views <= 4096) and layout."""
         from .evaluate import DetectionEvaluator, KittiDetectionEvaluator, calib_source
         device = torch.device(device)
         calib_of = None
@@ -1330,6 +1405,13 @@ class RPN3D(nn.Module):
         try:
             with torch.no_grad(), (ema.applied() if ema is not None else contextlib.nullcontext()):
                 for x in batches:
+                    if tta is not None:
+                        det = self._tta_decode(x, device, dec, kw, evaluator.top_k, tta)
+                        if calib_of is None:
+                            evaluator.update(*det, x[1])
+                        else:
+                            evaluator.update(*det, x[1], calibs=[calib_of(tag) for tag in x[0]], tags=list(x[0]))
+                        continue
                     prob, delta = self.detect(_parts_to(x[2], device), _parts_to(x[4], device))
                     if self.anchor_area_threshold is None:
                         det = dec.decode_device(prob, delta, top_k=evaluator.top_k, **self._dir_decode(kw, dec))

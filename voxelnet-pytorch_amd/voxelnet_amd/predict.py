@@ -22,7 +22,10 @@ its footprint scores 0 in a copy of the probability map (`vn_anchor_mask_probs`)
 
 `iou_logits=`: the IoU-aware head's map (B,2,h,w) — every anchor is scored by p^(1 - iou_rectify) *
 sigmoid(z)^iou_rectify in a copy of the probability map (`iou_head.rectify_probs`), made BEFORE the anchor mask edits that
-copy; every tail above runs unchanged on it, score_thres applies to the rectified score, and it needs layout="site"."""
+copy; every tail above runs unchanged on it, score_thres applies to the rectified score, and it needs layout="site".
+
+`vote=`: a `tta.BoxVote` — the composed tail ends in `tta.vote_device` (`vn_box_vote`) instead of the
+gather: every kept row becomes the weighted mean of the candidates that overlap it."""
 import ctypes
 import math
 
@@ -86,6 +89,19 @@ def nms_device(boxes, counts, mode="rotated", nms_thres=NMS_THRES, top_k=NMS_POS
     return keep, kc
 
 
+def gather_kept(boxes, scores, keep_idx, keep_counts):
+    """the kept rows of a pool in vn_rpn_predict's output format -> (boxes (B,P,7), scores (B,P), keep_counts), rows past the
+    count zero: the last step of every composed tail that ends in nms_device"""
+    B, P = keep_idx.shape
+    live = (keep_idx >= 0) & (torch.arange(P, device=keep_idx.device)[None, :] < keep_counts[:, None])
+    rows = keep_idx.clamp(min=0).long()
+    out = torch.gather(boxes, 1, rows[:, :, None].expand(B, P, 7))
+    sc = torch.gather(scores, 1, rows)
+    out = torch.where(live[:, :, None], out, torch.zeros_like(out))          # rows past the count are zero
+    sc = torch.where(live, sc, torch.zeros_like(sc))
+    return out, sc, keep_counts
+
+
 class BoxDecoder:
     def __init__(self, cls_name="Car", device="cuda:0", anchors=None, layout="flat"):
         _layout(layout)
@@ -140,39 +156,45 @@ class BoxDecoder:
                              f"{self.n_anchors} anchors")
         return rectify_probs(probs, iou_logits, iou_rectify).view(probs.shape)
 
-    def _decode_dir(self, probs, deltas, score_thres, nms_thres, top_k, nms, pre_nms_top_k, layout, dir_logits, dir_offset):
-        """decode_device with the direction head's logits: vn_rpn_select_decode_layout -> vn_boxes_rectify_yaw -> vn_box_nms ->
-        a gather of the kept rows.  The yaw changes by multiples of pi only, so the candidates, the kept set and the scores
-        are those of the fused tail (vn_rpn_detect_layout) on the same maps."""
-        from .dir_head import rectify_yaw
+    def _decode_composed(self, probs, deltas, score_thres, nms_thres, top_k, nms, pre_nms_top_k, layout, dir_logits, dir_offset,
+                         vote=None):
+        """decode_device composed from the public pieces: vn_rpn_select_decode_layout -> (dir_logits) vn_boxes_rectify_yaw ->
+        vn_box_nms -> (vote) vn_box_vote, or a gather of the kept rows.  With the direction head's logits the yaw changes by
+        multiples of pi only, so the candidates, the kept set and the scores are those of the fused tail
+        (vn_rpn_detect_layout) on the same maps; with a tta.BoxVote every kept row becomes the weighted mean of its cluster
+        (DESIGN.md 1m)."""
         _nms_mode(nms)
         lay = self.layout if layout is None else layout
-        if _layout(lay) != _lib.VN_DETECT_SITE:
+        _layout(lay)
+        if dir_logits is not None and _layout(lay) != _lib.VN_DETECT_SITE:
             raise ValueError(f"dir_logits: the direction head's logits are laid out by site; layout must be 'site', not {lay!r}")
         top_k = _check_range("top_k", top_k, _lib.VN_PREDICT_MAX_TOPK)
         pre = _check_range("pre_nms_top_k", top_k if pre_nms_top_k is None else pre_nms_top_k, _lib.VN_DETECT_MAX_PRE)
         if not np.isfinite(nms_thres):
             raise ValueError("nms_thres must be finite")
-        if not (torch.is_tensor(dir_logits) and dir_logits.is_cuda):
-            raise _lib.VoxelnetHipError("predict: dir_logits must be a HIP tensor (no CPU path)")
+        if vote is not None:
+            from .tta import BoxVote, vote_device
+            if not isinstance(vote, BoxVote):
+                raise ValueError(f"vote must be a tta.BoxVote, not {vote!r}")
         B = probs.shape[0]
-        if dir_logits.shape[0] != B or dir_logits.numel() != B * self.n_anchors:
-            raise ValueError(f"dir_logits {tuple(dir_logits.shape)} does not match {B} samples of {self.n_anchors} anchors")
-        dl = dir_logits.detach().float().contiguous().view(B, 2, self.n_anchors // 2)
-        cb, cs, idx, cc = self.candidates_device(probs, deltas, score_thres, pre, layout="site")
-        rectify_yaw(cb, idx, cc, dl, self.n_anchors, dir_offset)
+        if dir_logits is not None:
+            from .dir_head import rectify_yaw
+            if not (torch.is_tensor(dir_logits) and dir_logits.is_cuda):
+                raise _lib.VoxelnetHipError("predict: dir_logits must be a HIP tensor (no CPU path)")
+            if dir_logits.shape[0] != B or dir_logits.numel() != B * self.n_anchors:
+                raise ValueError(f"dir_logits {tuple(dir_logits.shape)} does not match {B} samples of {self.n_anchors} anchors")
+            dl = dir_logits.detach().float().contiguous().view(B, 2, self.n_anchors // 2)
+        cb, cs, idx, cc = self.candidates_device(probs, deltas, score_thres, pre, layout=lay)
+        if dir_logits is not None:
+            rectify_yaw(cb, idx, cc, dl, self.n_anchors, dir_offset)
         keep, kc = nms_device(cb, cc, nms, nms_thres, top_k)
-        live = (keep >= 0) & (torch.arange(top_k, device=keep.device)[None, :] < kc[:, None])
-        rows = keep.clamp(min=0).long()
-        boxes = torch.gather(cb, 1, rows[:, :, None].expand(B, top_k, 7))
-        scores = torch.gather(cs, 1, rows)
-        boxes = torch.where(live[:, :, None], boxes, torch.zeros_like(boxes))          # rows past the count are zero
-        scores = torch.where(live, scores, torch.zeros_like(scores))
-        return boxes, scores, kc
+        if vote is not None:
+            return vote_device(cb, cs, cc, keep, kc, vote)[:3]
+        return gather_kept(cb, cs, keep, kc)
 
     def decode_device(self, probs, deltas, score_thres=SCORE_THRES, nms_thres=NMS_THRES, top_k=NMS_POST_TOPK, nms="standup",
                       pre_nms_top_k=None, layout=None, dir_logits=None, dir_offset=math.pi / 4, anchor_mask=None, iou_logits=None,
-                      iou_rectify=0.5):
+                      iou_rectify=0.5, vote=None):
         """probs (B,2,h,w), deltas (B,14,h,w) fp32 device tensors -> (boxes (B,top_k,7) f32, scores (B,top_k) f32, counts (B,)
         int32) ON THE DEVICE, enqueued on the current stream without any host synchronisation: per sample the first
         counts[b] rows are the kept detections in descending score, the rest is zero.  What evaluate.DetectionEvaluator
@@ -189,13 +211,18 @@ class BoxDecoder:
         every path above runs unchanged on a copy of probs in which a masked-out anchor scores 0; needs score_thres > 0.
         iou_logits (None: nothing new is allocated or launched): the IoU-aware head's (B,2,h,w) map, layout "site"
         only — every path above, the anchor mask included, runs on a copy of probs in which an anchor scores
-        p^(1 - iou_rectify) * sigmoid(z)^iou_rectify, iou_rectify in [0, 1]; score_thres applies to that score."""
+        p^(1 - iou_rectify) * sigmoid(z)^iou_rectify, iou_rectify in [0, 1]; score_thres applies to that score.
+        vote (None: every path above exactly as it is, nothing new is allocated or launched): a tta.BoxVote — the
+        tail is composed, candidates_device -> nms_device -> tta.vote_device, and every kept row comes back as the weighted mean
+        of the candidates that overlap it by vote.thres; every option above keeps its meaning, the rows come in descending
+        output score."""
         if iou_logits is not None:          # (before the mask: 0^0 = 1 would bring a masked-out anchor back at iou_rectify = 1)
             probs = self._rectified(probs, iou_logits, iou_rectify, layout, "predict")
         if anchor_mask is not None:
             probs = self._masked(probs, anchor_mask, score_thres, layout, "predict")
-        if dir_logits is not None:
-            return self._decode_dir(probs, deltas, score_thres, nms_thres, top_k, nms, pre_nms_top_k, layout, dir_logits, dir_offset)
+        if dir_logits is not None or vote is not None:
+            return self._decode_composed(probs, deltas, score_thres, nms_thres, top_k, nms, pre_nms_top_k, layout, dir_logits,
+                                         dir_offset, vote)
         mode = _nms_mode(nms)
         lay = _layout(self.layout if layout is None else layout)
         probs, deltas = self._maps(probs, deltas, "predict")
@@ -276,10 +303,10 @@ class BoxDecoder:
 
     def __call__(self, probs, deltas, score_thres=SCORE_THRES, nms_thres=NMS_THRES, top_k=NMS_POST_TOPK, nms="standup",
                  pre_nms_top_k=None, layout=None, dir_logits=None, dir_offset=math.pi / 4, anchor_mask=None, iou_logits=None,
-                 iou_rectify=0.5):
+                 iou_rectify=0.5, vote=None):
         """probs (B,2,h,w), deltas (B,14,h,w) fp32 device tensors -> ([boxes (n_i,7) f32 numpy], [scores (n_i,) f32 numpy])"""
         boxes, scores, counts = self.decode_device(probs, deltas, score_thres, nms_thres, top_k, nms, pre_nms_top_k, layout,
-                                                   dir_logits, dir_offset, anchor_mask, iou_logits, iou_rectify)
+                                                   dir_logits, dir_offset, anchor_mask, iou_logits, iou_rectify, vote)
         B = boxes.shape[0]
         cnt = counts.cpu().numpy()
         bh, sh = boxes.cpu().numpy(), scores.cpu().numpy()
