@@ -1483,6 +1483,41 @@ int vn_box_vote(const float *boxes /*[B,K,7]*/, const float *scores /*[B,K]*/, c
                 int32_t *out_members /*[B,P]*/, int32_t *out_counts /*[B]*/, void *workspace, size_t workspace_bytes,
                 vnStream stream);
 
+/* ---- Soft-NMS (csrc/soft_nms.hip; rules: DESIGN.md section 1n; Bodla et al., 2017) ---------------------------------
+ * What vn_box_nms does with a DECAY in place of the deletion: a picked row multiplies the working score of every row it
+ * overlaps by a decreasing function of the overlap, and the walk goes on by the decayed scores.  Asynchronous on `stream`,
+ * never synchronises with the host, no floating-point atomics, the same bits from run to run.
+ *   boxes [B,K,7], scores [B,K] float32, counts [B] int32 (device): the rows j < n = min(max(counts[b], 0), K) of sample b.
+ *   A row is ELIGIBLE iff no field is non-finite, h, w, l > 0 (vn_box_iou_rotated's validity) and its score is finite; an
+ *   ineligible row is never kept and decays nothing.  Working score w_j = (double)scores[j].  Repeat:
+ *     i = the eligible, not yet picked, not removed row of the largest w (compared as numbers: -0.0 == +0.0), equal w: the
+ *         SMALLER row; stop if there is none or if not (w_i >= min_score);
+ *     keep_idx[b,t] = i, keep_scores[b,t] = (float)w_i; stop if t + 1 == post_top_k (before any decay);
+ *     every remaining row j, u = IoU(i,j) by the pair function of vn_box_iou_rotated on the widened rows — VN_SOFT_BEV its BEV
+ *     value, VN_SOFT_3D its 3D value —, takes ONE update:
+ *       VN_SOFT_HARD:     removed if not (u <= iou_thres)
+ *       VN_SOFT_LINEAR:   w_j = w_j * (1.0 - u)                   if u > iou_thres
+ *       VN_SOFT_GAUSSIAN: w_j = w_j * exp(-(u*u) / sigma)         if u > 0          (float64 exp)
+ *     (a pair whose centres are further apart than the two half-diagonals together has u = 0 exactly and is skipped unclipped).
+ *   keep_idx [B,P] int32: -1 past the count; keep_scores [B,P] float32: 0 past the count; keep_counts [B] int32.  For
+ *   non-negative input scores keep_scores does not increase along t.  A row's product is formed in pick order.
+ *   VN_SOFT_HARD with VN_SOFT_BEV on a pool whose scores do not increase along the rows (and min_score at or below them) IS
+ *   vn_box_nms(VN_NMS_ROTATED, nms_thres = iou_thres): the same keep_idx and keep_counts.
+ *   Limits: B >= 1, 1 <= K <= VN_DETECT_MAX_PRE, 1 <= post_top_k <= VN_PREDICT_MAX_TOPK, a known method and metric, iou_thres
+ *   finite in [0, 1], sigma finite and > 0 (read by VN_SOFT_GAUSSIAN only, checked always), min_score finite.  VN_EINVAL, before
+ *   anything is launched, for anything else or a null pointer; the workspace query returns 0 for sizes the call refuses;
+ *   VN_EWORKSPACE for a smaller workspace. */
+#define VN_SOFT_HARD 0        /* the greedy rule: a row with IoU above iou_thres is removed */
+#define VN_SOFT_LINEAR 1      /* w *= 1 - IoU above iou_thres */
+#define VN_SOFT_GAUSSIAN 2    /* w *= exp(-IoU^2 / sigma) */
+#define VN_SOFT_BEV 0
+#define VN_SOFT_3D 1
+size_t vn_box_soft_nms_workspace_bytes(int32_t B, int32_t K);
+int vn_box_soft_nms(const float *boxes /*[B,K,7]*/, const float *scores /*[B,K]*/, const int32_t *counts /*[B]*/, int32_t B, int32_t K,
+                    int32_t method, int32_t metric, double iou_thres, double sigma, double min_score, int32_t post_top_k,
+                    int32_t *keep_idx /*[B,P]*/, float *keep_scores /*[B,P]*/, int32_t *keep_counts /*[B]*/, void *workspace,
+                    size_t workspace_bytes, vnStream stream);
+
 #ifdef __cplusplus
 }
 #endif

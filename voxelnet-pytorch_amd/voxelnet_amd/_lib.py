@@ -167,6 +167,8 @@ VN_ASSIGN_STANDUP, VN_ASSIGN_ROTATED = 1, 2       # vn_rpn_targets_iou's `iou_ki
 VN_TTA_MAX_VIEWS = 8                              # vn_pool_merge's / vn_box_vote's V
 VN_VOTE_W_SCORE, VN_VOTE_W_SCORE_IOU = 0, 1       # vn_box_vote's `weight_mode`
 VN_VOTE_S_KEEP, VN_VOTE_S_VIEW_MEAN = 0, 1        # vn_box_vote's `score_mode`
+VN_SOFT_HARD, VN_SOFT_LINEAR, VN_SOFT_GAUSSIAN = 0, 1, 2       # vn_box_soft_nms' `method`
+VN_SOFT_BEV, VN_SOFT_3D = 0, 1                                 # vn_box_soft_nms' `metric`
 
 
 # name -> (restype, argtypes); mirrors include/voxelnet_hip.h one to one
@@ -353,6 +355,9 @@ SIGNATURES = {
     "vn_box_vote_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32, c_i32]),
     "vn_box_vote": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, ctypes.c_double, c_i32, c_i32,
                             c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "vn_box_soft_nms_workspace_bytes": (c_sz, [c_i32, c_i32]),
+    "vn_box_soft_nms": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, ctypes.c_double, ctypes.c_double, ctypes.c_double, c_i32,
+                                c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "vn_clip_sgd_workspace_bytes": (c_sz, [c_i32]),
     "vn_clip_sgd": (c_i32, [c_vp, c_i32, c_f32, c_f32, c_i32, c_vp, c_sz, c_vp, c_vp]),
     "vn_clip_adamw_workspace_bytes": (c_sz, [c_i32]),

@@ -1243,7 +1243,8 @@ class RPN3D(nn.Module):
         crops it when tta.fov_calib_dir is set, moves it by vn_augment_compose, voxelizes it on the model's grid and runs
         detect; candidates_device with THAT view's direction / IoU logits and anchor mask.  Then tta.merge_pools, nms_device
         on the merged pool and tta.vote_device (tta.vote None: a gather of the kept rows).  kw: decode_device's keyword
-        arguments score_thres, nms, nms_thres, pre_nms_top_k, layout.  Must run in eval mode under no_grad."""
+        arguments score_thres, nms, nms_thres, pre_nms_top_k, layout and soft_nms (predict.soft_nms_device on the
+        merged pool in place of nms_device; needs tta.vote None).  Must run in eval mode under no_grad."""
         from . import predict as PR
         from .tta import TestTimeAugment, merge_pools, vote_device
         from .voxelize import voxelize_device_async
@@ -1252,8 +1253,17 @@ class RPN3D(nn.Module):
         kw = dict(kw)
         score_thres, nms = kw.pop("score_thres", PR.SCORE_THRES), kw.pop("nms", "standup")
         nms_thres, pre, layout = kw.pop("nms_thres", PR.NMS_THRES), kw.pop("pre_nms_top_k", None), kw.pop("layout", None)
+        soft = kw.pop("soft_nms", None)
         if kw:
-            raise ValueError(f"tta: the decode may set score_thres, nms, nms_thres, pre_nms_top_k and layout, not {sorted(kw)}")
+            raise ValueError(f"tta: the decode may set score_thres, nms, nms_thres, pre_nms_top_k, layout and soft_nms, not {sorted(kw)}")
+        if soft is not None:
+            if not isinstance(soft, PR.SoftNMS):
+                raise ValueError(f"soft_nms must be a predict.SoftNMS, not {soft!r}")
+            if nms != "rotated":
+                raise ValueError(f"soft_nms decays by the rotated IoU; nms must be 'rotated', not {nms!r}")
+            if tta.vote is not None:
+                raise ValueError("tta: soft_nms with a vote is not defined (the vote's cluster around a soft-kept row); pass "
+                                 "TestTimeAugment(vote=None)")
         pre = top_k if pre is None else pre
         V = len(tta.views)
         if not (isinstance(pre, (int, np.integer)) and 1 <= pre and pre * V <= _lib.VN_DETECT_MAX_PRE):
@@ -1287,6 +1297,9 @@ class RPN3D(nn.Module):
                 hkw = dict(hkw, anchor_mask=self._decode_mask(dec, coords, device))          # and this view's occupancy
             pools.append(dec.candidates_device(prob, delta, score_thres, int(pre), **hkw))
         mb, ms, src, mc = merge_pools([p[0] for p in pools], [p[1] for p in pools], [p[3] for p in pools], tta.views)
+        if soft is not None:
+            keep, ks, kc = PR.soft_nms_device(mb, ms, mc, soft, top_k, min_score=float(score_thres))
+            return PR.gather_kept(mb, ms, keep, kc, keep_scores=ks)
         keep, kc = PR.nms_device(mb, mc, nms, nms_thres, top_k)
         if tta.vote is None:
             return PR.gather_kept(mb, ms, keep, kc)
@@ -1378,7 +1391,8 @@ class RPN3D(nn.Module):
         remembered for its write_results.
         tta: None — every path above exactly as it is; or a tta.TestTimeAugment: every batch is run once per
         view from its raw clouds x[6], the views' candidates are merged, suppressed and voted on the device (`_tta_decode`);
-        `decode` may then set score_thres, nms, nms_thres, pre_nms_top_k (times the number of views <= 4096) and layout."""
+        `decode` may then set score_thres, nms, nms_thres, pre_nms_top_k (times the number of views <= 4096), layout and
+        soft_nms (a predict.SoftNMS; with it tta.vote must be None)."""
         from .evaluate import DetectionEvaluator, KittiDetectionEvaluator, calib_source
         device = torch.device(device)
         calib_of = None

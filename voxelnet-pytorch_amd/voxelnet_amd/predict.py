@@ -25,9 +25,15 @@ sigmoid(z)^iou_rectify in a copy of the probability map (`iou_head.rectify_probs
 copy; every tail above runs unchanged on it, score_thres applies to the rectified score, and it needs layout="site".
 
 `vote=`: a `tta.BoxVote` — the composed tail ends in `tta.vote_device` (`vn_box_vote`) instead of the
-gather: every kept row becomes the weighted mean of the candidates that overlap it."""
+gather: every kept row becomes the weighted mean of the candidates that overlap it.
+
+`soft_nms=`: a `SoftNMS` — the composed tail runs `soft_nms_device` (`vn_box_soft_nms`) in place of
+`nms_device`: a kept row decays the scores of the rows it overlaps instead of deleting them, and the kept rows come back with
+their decayed scores."""
 import ctypes
 import math
+from dataclasses import dataclass
+from typing import Optional
 
 import numpy as np
 import torch
@@ -40,6 +46,8 @@ NMS_MODES = {"standup": _lib.VN_NMS_STANDUP, "rotated": _lib.VN_NMS_ROTATED}
 # A starting point for RPN3D.evaluate(decode=...), NOT tuned: there is no trained checkpoint here to tune it on.
 EVAL_DECODE = dict(score_thres=0.1, nms="rotated", nms_thres=0.1, pre_nms_top_k=1024)
 LAYOUTS = {"flat": _lib.VN_DETECT_FLAT, "site": _lib.VN_DETECT_SITE}
+SOFT_METHODS = {"hard": _lib.VN_SOFT_HARD, "linear": _lib.VN_SOFT_LINEAR, "gaussian": _lib.VN_SOFT_GAUSSIAN}
+SOFT_METRICS = {"bev": _lib.VN_SOFT_BEV, "3d": _lib.VN_SOFT_3D}
 # EVAL_DECODE in the layout the loss trains: RPN3D.evaluate(decode=TRAINED_DECODE) for a model trained here
 TRAINED_DECODE = dict(EVAL_DECODE, layout="site")
 
@@ -89,14 +97,82 @@ def nms_device(boxes, counts, mode="rotated", nms_thres=NMS_THRES, top_k=NMS_POS
     return keep, kc
 
 
-def gather_kept(boxes, scores, keep_idx, keep_counts):
+def _is_real(v):
+    return isinstance(v, (int, float, np.floating, np.integer)) and not isinstance(v, (bool, np.bool_)) and math.isfinite(v)
+
+
+@dataclass(frozen=True)
+class SoftNMS:
+    """Soft-NMS (vn_box_soft_nms).  method: "gaussian" (w *= exp(-IoU^2 / sigma) for every IoU > 0), "linear"
+    (w *= 1 - IoU above iou_thres) or "hard" (a row above iou_thres is removed: the greedy rule); metric: the "bev" or the "3d"
+    IoU of evaluate.box_iou_rotated; sigma > 0 is read by "gaussian", iou_thres in [0, 1] by "linear" and "hard"; min_score: the
+    walk stops at the first pick whose decayed score is below it (None: the decode call's score_thres).  Not tuned: there is
+    no trained checkpoint here to tune it on."""
+    method: str = "gaussian"
+    sigma: float = 0.5
+    iou_thres: float = 0.3
+    metric: str = "bev"
+    min_score: Optional[float] = None
+
+    def __post_init__(self):
+        if self.method not in SOFT_METHODS:
+            raise ValueError(f"SoftNMS.method must be one of {sorted(SOFT_METHODS)}, not {self.method!r}")
+        if self.metric not in SOFT_METRICS:
+            raise ValueError(f"SoftNMS.metric must be one of {sorted(SOFT_METRICS)}, not {self.metric!r}")
+        if not (_is_real(self.sigma) and self.sigma > 0):
+            raise ValueError(f"SoftNMS.sigma must be finite and > 0, not {self.sigma!r}")
+        if not (_is_real(self.iou_thres) and 0 <= self.iou_thres <= 1):
+            raise ValueError(f"SoftNMS.iou_thres must be in [0, 1], not {self.iou_thres!r}")
+        if self.min_score is not None and not _is_real(self.min_score):
+            raise ValueError(f"SoftNMS.min_score must be finite or None, not {self.min_score!r}")
+
+
+def soft_nms_device(boxes, scores, counts, soft, top_k=NMS_POST_TOPK, min_score=None):
+    """Soft-NMS as an operation of its own (vn_box_soft_nms): boxes (B,K,7) f32, scores (B,K) f32, counts (B,) int32 device
+    tensors (counts read on the device; above K means K), soft: a SoftNMS -> (keep_idx (B,top_k) int32, the picked row numbers
+    in pick order, -1 past the count; keep_scores (B,top_k) f32, their decayed scores, 0 past the count; keep_counts (B,) int32),
+    on the device, no host synchronisation.  The rows need no order: every pick is an arg-max.  min_score: where the walk stops
+    when soft.min_score is None (one of the two must be set).  Rows with a non-finite field, h, w, l <= 0 or a non-finite score
+    are never kept and decay nothing."""
+    if not isinstance(soft, SoftNMS):
+        raise ValueError(f"soft must be a predict.SoftNMS, not {soft!r}")
+    floor = soft.min_score if soft.min_score is not None else min_score
+    if floor is None:
+        raise ValueError("soft_nms_device: min_score is None and so is soft.min_score; one of them must say where the walk stops")
+    if not _is_real(floor):
+        raise ValueError(f"min_score must be finite, not {floor!r}")
+    if not all(torch.is_tensor(t) and t.is_cuda for t in (boxes, scores, counts)):
+        raise _lib.VoxelnetHipError("soft_nms_device: boxes / scores / counts must be HIP tensors (no CPU path)")
+    if boxes.dim() != 3 or boxes.shape[2] != 7 or scores.shape != boxes.shape[:2] or counts.shape != (boxes.shape[0],) \
+            or boxes.shape[0] < 1:
+        raise ValueError(f"boxes {tuple(boxes.shape)} / scores {tuple(scores.shape)} / counts {tuple(counts.shape)}: want (B,K,7), "
+                         "(B,K) and (B,)")
+    B, K = boxes.shape[0], _check_range("K", boxes.shape[1], _lib.VN_DETECT_MAX_PRE)
+    top_k = _check_range("top_k", top_k, _lib.VN_PREDICT_MAX_TOPK)
+    boxes, scores = boxes.detach().float().contiguous(), scores.detach().float().contiguous()
+    counts = counts.to(torch.int32).contiguous()
+    dev = boxes.device
+    keep = torch.empty((B, top_k), dtype=torch.int32, device=dev)
+    ks = torch.empty((B, top_k), dtype=torch.float32, device=dev)
+    kc = torch.empty(B, dtype=torch.int32, device=dev)
+    nbytes = _lib.load().vn_box_soft_nms_workspace_bytes(B, K)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    with _lib.on_device(dev):
+        _lib.call("vn_box_soft_nms", boxes.data_ptr(), scores.data_ptr(), counts.data_ptr(), B, K, SOFT_METHODS[soft.method],
+                  SOFT_METRICS[soft.metric], float(soft.iou_thres), float(soft.sigma), float(floor), top_k, keep.data_ptr(),
+                  ks.data_ptr(), kc.data_ptr(), ws.data_ptr(), nbytes, _lib.raw_stream())
+    return keep, ks, kc
+
+
+def gather_kept(boxes, scores, keep_idx, keep_counts, keep_scores=None):
     """the kept rows of a pool in vn_rpn_predict's output format -> (boxes (B,P,7), scores (B,P), keep_counts), rows past the
-    count zero: the last step of every composed tail that ends in nms_device"""
+    count zero: the last step of every composed tail that ends in nms_device.  keep_scores (None: the pool's scores, gathered):
+    soft_nms_device's (B,P) decayed scores, which then come back in place of the pool's — the one copy for every soft tail."""
     B, P = keep_idx.shape
     live = (keep_idx >= 0) & (torch.arange(P, device=keep_idx.device)[None, :] < keep_counts[:, None])
     rows = keep_idx.clamp(min=0).long()
     out = torch.gather(boxes, 1, rows[:, :, None].expand(B, P, 7))
-    sc = torch.gather(scores, 1, rows)
+    sc = torch.gather(scores, 1, rows) if keep_scores is None else keep_scores
     out = torch.where(live[:, :, None], out, torch.zeros_like(out))          # rows past the count are zero
     sc = torch.where(live, sc, torch.zeros_like(sc))
     return out, sc, keep_counts
@@ -157,20 +233,28 @@ class BoxDecoder:
         return rectify_probs(probs, iou_logits, iou_rectify).view(probs.shape)
 
     def _decode_composed(self, probs, deltas, score_thres, nms_thres, top_k, nms, pre_nms_top_k, layout, dir_logits, dir_offset,
-                         vote=None):
+                         vote=None, soft_nms=None):
         """decode_device composed from the public pieces: vn_rpn_select_decode_layout -> (dir_logits) vn_boxes_rectify_yaw ->
         vn_box_nms -> (vote) vn_box_vote, or a gather of the kept rows.  With the direction head's logits the yaw changes by
         multiples of pi only, so the candidates, the kept set and the scores are those of the fused tail
         (vn_rpn_detect_layout) on the same maps; with a tta.BoxVote every kept row becomes the weighted mean of its cluster
-        (DESIGN.md 1m)."""
+        (DESIGN.md 1m).  With a SoftNMS vn_box_soft_nms stands in place of vn_box_nms and the gather takes its
+        decayed scores; nms_thres is then not read."""
         _nms_mode(nms)
+        if soft_nms is not None:
+            if not isinstance(soft_nms, SoftNMS):
+                raise ValueError(f"soft_nms must be a predict.SoftNMS, not {soft_nms!r}")
+            if nms != "rotated":
+                raise ValueError(f"soft_nms decays by the rotated IoU; nms must be 'rotated', not {nms!r}")
+            if vote is not None:
+                raise ValueError("soft_nms with vote: the vote's cluster around a soft-kept row is not defined; pass one of the two")
         lay = self.layout if layout is None else layout
         _layout(lay)
         if dir_logits is not None and _layout(lay) != _lib.VN_DETECT_SITE:
             raise ValueError(f"dir_logits: the direction head's logits are laid out by site; layout must be 'site', not {lay!r}")
         top_k = _check_range("top_k", top_k, _lib.VN_PREDICT_MAX_TOPK)
         pre = _check_range("pre_nms_top_k", top_k if pre_nms_top_k is None else pre_nms_top_k, _lib.VN_DETECT_MAX_PRE)
-        if not np.isfinite(nms_thres):
+        if soft_nms is None and not np.isfinite(nms_thres):
             raise ValueError("nms_thres must be finite")
         if vote is not None:
             from .tta import BoxVote, vote_device
@@ -187,6 +271,9 @@ class BoxDecoder:
         cb, cs, idx, cc = self.candidates_device(probs, deltas, score_thres, pre, layout=lay)
         if dir_logits is not None:
             rectify_yaw(cb, idx, cc, dl, self.n_anchors, dir_offset)
+        if soft_nms is not None:
+            keep, ks, kc = soft_nms_device(cb, cs, cc, soft_nms, top_k, min_score=float(score_thres))
+            return gather_kept(cb, cs, keep, kc, keep_scores=ks)
         keep, kc = nms_device(cb, cc, nms, nms_thres, top_k)
         if vote is not None:
             return vote_device(cb, cs, cc, keep, kc, vote)[:3]
@@ -194,7 +281,7 @@ class BoxDecoder:
 
     def decode_device(self, probs, deltas, score_thres=SCORE_THRES, nms_thres=NMS_THRES, top_k=NMS_POST_TOPK, nms="standup",
                       pre_nms_top_k=None, layout=None, dir_logits=None, dir_offset=math.pi / 4, anchor_mask=None, iou_logits=None,
-                      iou_rectify=0.5, vote=None):
+                      iou_rectify=0.5, vote=None, soft_nms=None):
         """probs (B,2,h,w), deltas (B,14,h,w) fp32 device tensors -> (boxes (B,top_k,7) f32, scores (B,top_k) f32, counts (B,)
         int32) ON THE DEVICE, enqueued on the current stream without any host synchronisation: per sample the first
         counts[b] rows are the kept detections in descending score, the rest is zero.  What evaluate.DetectionEvaluator
@@ -215,14 +302,20 @@ class BoxDecoder:
         vote (None: every path above exactly as it is, nothing new is allocated or launched): a tta.BoxVote — the
         tail is composed, candidates_device -> nms_device -> tta.vote_device, and every kept row comes back as the weighted mean
         of the candidates that overlap it by vote.thres; every option above keeps its meaning, the rows come in descending
-        output score."""
+        output score.
+        soft_nms (None: every path above exactly as it is, nothing new is allocated or launched): a SoftNMS — the
+        tail is composed, candidates_device -> soft_nms_device -> gather_kept: a picked row decays the scores of the rows it
+        overlaps instead of deleting them, and the rows come back in pick order with their DECAYED scores.  dir_logits,
+        iou_logits, anchor_mask, layout and pre_nms_top_k keep their meaning; nms must be "rotated"; nms_thres is NOT read
+        (soft_nms.iou_thres is); the walk stops below soft_nms.min_score, or below score_thres when that is None; together
+        with vote it is a ValueError."""
         if iou_logits is not None:          # (before the mask: 0^0 = 1 would bring a masked-out anchor back at iou_rectify = 1)
             probs = self._rectified(probs, iou_logits, iou_rectify, layout, "predict")
         if anchor_mask is not None:
             probs = self._masked(probs, anchor_mask, score_thres, layout, "predict")
-        if dir_logits is not None or vote is not None:
+        if dir_logits is not None or vote is not None or soft_nms is not None:
             return self._decode_composed(probs, deltas, score_thres, nms_thres, top_k, nms, pre_nms_top_k, layout, dir_logits,
-                                         dir_offset, vote)
+                                         dir_offset, vote, soft_nms)
         mode = _nms_mode(nms)
         lay = _layout(self.layout if layout is None else layout)
         probs, deltas = self._maps(probs, deltas, "predict")
@@ -303,10 +396,10 @@ class BoxDecoder:
 
     def __call__(self, probs, deltas, score_thres=SCORE_THRES, nms_thres=NMS_THRES, top_k=NMS_POST_TOPK, nms="standup",
                  pre_nms_top_k=None, layout=None, dir_logits=None, dir_offset=math.pi / 4, anchor_mask=None, iou_logits=None,
-                 iou_rectify=0.5, vote=None):
+                 iou_rectify=0.5, vote=None, soft_nms=None):
         """probs (B,2,h,w), deltas (B,14,h,w) fp32 device tensors -> ([boxes (n_i,7) f32 numpy], [scores (n_i,) f32 numpy])"""
         boxes, scores, counts = self.decode_device(probs, deltas, score_thres, nms_thres, top_k, nms, pre_nms_top_k, layout,
-                                                   dir_logits, dir_offset, anchor_mask, iou_logits, iou_rectify, vote)
+                                                   dir_logits, dir_offset, anchor_mask, iou_logits, iou_rectify, vote, soft_nms)
         B = boxes.shape[0]
         cnt = counts.cpu().numpy()
         bh, sh = boxes.cpu().numpy(), scores.cpu().numpy()
