@@ -470,6 +470,58 @@ int vn_gt_paste(const float *points, int64_t n, const vnGtBox *boxes, int32_t n_
                 vnStream stream);
 
 /* ------------------------------------------------------------------------
+ * The occlusion-consistent paste (csrc/gtsample.hip): vn_gt_paste with a coarse range image
+ * of the frame.  A pasted object whose points are mostly hidden behind scene points is rejected; the hidden points of an
+ * accepted object go; scene points, and points of other pasted objects, in the shadow of an accepted object go.
+ * Everything below is float64, evaluated as written, no contraction, IEEE divides.
+ *   Bin of a point (px, py, pz), float32 widened exactly — four side faces of a cube around the sensor:
+ *     ax = |px|, ay = |py|;  ax >= ay: a = ax, face = px > 0 ? 0 : 2, u = py / a;  else: a = ay, face = py > 0 ? 1 : 3,
+ *     u = px / a;  v = pz / a.  No bin when any of x, y, z is non-finite or a == 0.
+ *     iu = min(floor((u + 1.0) * (nu / 2)), nu - 1);  iv = floor((v - v_lo) * v_scale), iv < 0 or iv >= nv: no bin.
+ *     bin = (face * nv + iv) * nu + iu;  depth = a (exactly a float32: its bit pattern as uint32 orders like the value).
+ *   vnVisGrid (HOST struct): nu even in 2..2048, nv in 1..256, v_lo < v_hi finite, v_scale = nv / (v_hi - v_lo) computed
+ *     by the caller (finite, > 0), margin >= 0 (+inf allowed, NaN refused), min_visible >= 0.
+ *   obj_offsets: HOST pointer to n_boxes + 1 int32, non-decreasing, [0] == 0, [n_boxes] == m, read and validated during
+ *     the call; object o owns object rows [offsets[o], offsets[o+1]).
+ *   1. Dscene[bin] = min depth over the scene rows with no NaN in x, y, z that have a bin and lie inside NO box of the
+ *      table (vn_gt_paste's inside test).
+ *   2. an object point is visible <=> none of x, y, z is NaN and not (it has a bin and (double)depth >
+ *      (double)Dscene[bin] + margin);  visible[o] = the visible points of object o;  accepted[o] <=> visible[o] >= min_visible.
+ *   3. Dobj[bin] = min, over the visible points of accepted objects that have a bin, of (depth bits << 32) | o: the
+ *      nearest depth and its owner, equal depths to the lower object.
+ *   4. a scene row is kept <=> no NaN in x, y, z, inside no ACCEPTED box, and not (it has a bin, the bin has an owner and
+ *      depth > Dobj.depth + margin);  an object point is kept <=> visible, its object accepted, and not (it has a bin
+ *      whose owner is ANOTHER object and depth > Dobj.depth + margin).
+ *   5. out_points (cap rows, cap >= n + m, else VN_EINVAL): rows [0, k) = the kept scene rows in input order, [k, k + m')
+ *      = the kept object points in input order, verbatim, [k + m', cap) = NaN points;  *out_count = k + m'.
+ *   6. out_visible[n_boxes] (pass 2's counts: the caller derives acceptance from them), out_kept[n_boxes] (the final
+ *      points per object), out_stats[2] = {scene rows removed by an accepted box, scene rows removed by shadow only}:
+ *      DEVICE int32, 4-byte aligned; out_visible / out_kept may be NULL when n_boxes == 0.
+ *   Acceptance is decided by scene visibility only: an accepted object may end with fewer than min_visible points after
+ *   another pasted object culls it.  Scene points inside a REJECTED object's box stay, but were no occluders in pass 1.
+ *   margin = +inf with min_visible = 0 is vn_gt_paste bit for bit (for object points without NaN coordinates).
+ * Bad sizes, a bad grid, bad offsets, overlapping out_points / inputs: VN_EINVAL; a workspace below
+ * vn_gt_paste_visible_workspace_bytes(n, m, grid) (0 for bad arguments): VN_EWORKSPACE; pointers (workspace included) off
+ * their 16-byte / 4-byte alignment: VN_EUNSUPPORTED — all decided before the first launch.  The depth buffers live in the
+ * workspace and are reset on the stream by every call.  Seven launches (reset, scene depth, visible counts, object depth,
+ * keep flags over the n + m rows, the one-workgroup scan, compaction + NaN fill); integer minima and sums only, so the
+ * result does not depend on the order of the atomics; no workgroup waits on another one.  Asynchronous.
+ * ---------------------------------------------------------------------- */
+typedef struct vnVisGrid {
+    int32_t nu, nv;             /* bins across a face, rows */
+    double v_lo, v_hi;          /* the rows cover v = z / a in [v_lo, v_hi) */
+    double v_scale;             /* nv / (v_hi - v_lo) */
+    double margin;              /* metres of depth a point may lie behind the front of its bin */
+    int32_t min_visible;        /* an object needs this many visible points */
+    int32_t reserved;
+} vnVisGrid;                    /* 48 bytes */
+size_t vn_gt_paste_visible_workspace_bytes(int64_t n, int64_t m, const vnVisGrid *grid);
+int vn_gt_paste_visible(const float *points, int64_t n, const vnGtBox *boxes, int32_t n_boxes, const float *obj_points,
+                        int64_t m, const int32_t *obj_offsets, const vnVisGrid *grid, float *out_points, int64_t cap,
+                        int32_t *out_count, int32_t *out_visible, int32_t *out_kept, int32_t *out_stats, void *workspace,
+                        size_t workspace_bytes, vnStream stream);
+
+/* ------------------------------------------------------------------------
  * Point shuffle on the device — the reference's np.random.shuffle(point_cloud) in front of the voxelizer
  * (voxelnet/utils.py:35), which decides which <= T points of a crowded voxel survive, as a row gather right behind the
  * host->device copy (csrc/shuffle.hip; the draws are voxelnet_amd/shuffle.py).  points / out: (n,4) fp32

@@ -156,6 +156,11 @@ class VnGtBox(ctypes.Structure):   # vnGtBox (vn_points_in_boxes, vn_gt_paste): 
     _fields_ = [(n, ctypes.c_double) for n in ("x", "y", "z0", "z1", "hl", "hw", "c", "s")]
 
 
+class VnVisGrid(ctypes.Structure):   # vnVisGrid (vn_gt_paste_visible): the range image's grid and thresholds, HOST memory, 48 bytes
+    _fields_ = [("nu", c_i32), ("nv", c_i32), ("v_lo", ctypes.c_double), ("v_hi", ctypes.c_double), ("v_scale", ctypes.c_double),
+                ("margin", ctypes.c_double), ("min_visible", c_i32), ("reserved", c_i32)]
+
+
 VN_GT_MAX_BOXES = 128
 VN_EVAL_BEV, VN_EVAL_3D = 0, 1       # vn_box_iou_rotated's `metric`; axis 1 of vn_eval_match's outputs
 VN_EVAL_MAX_TOPK, VN_EVAL_MAX_DIFF = 32, 8
@@ -195,6 +200,9 @@ SIGNATURES = {
     "vn_points_in_boxes": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_vp, c_vp, c_vp]),
     "vn_gt_paste_workspace_bytes": (c_sz, [c_i64]),
     "vn_gt_paste": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_sz, c_vp]),
+    "vn_gt_paste_visible_workspace_bytes": (c_sz, [c_i64, c_i64, _P(VnVisGrid)]),
+    "vn_gt_paste_visible": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_vp, c_i64, c_vp, _P(VnVisGrid), c_vp, c_i64, c_vp, c_vp, c_vp, c_vp,
+                                    c_vp, c_sz, c_vp]),
     "vn_permute_points": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp]),
     "vn_shuffle_points": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp]),
     "vn_comm_rccl_version": (c_i32, []),

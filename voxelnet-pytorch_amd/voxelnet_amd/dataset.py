@@ -22,7 +22,9 @@ Ground-truth database sampling (gtsample.py; SECOND's "GT-paste", no counterpart
 of the augmentation: copy -> [field-of-view crop] -> paste -> augment -> voxelize.  `DeviceCollate(..., gt_sampler=s)` /
 `DeviceBatcher(..., gt_sampler=s)` draw the pasted objects per sample on the host (after the sample's shuffle, before the
 augmentation's draw, which then runs on the enlarged labels), paste their points on the device (csrc/gtsample.hip) and
-hand the model labels + the pasted objects' lines.
+hand the model labels + the pasted objects' lines.  A sampler with `visibility=gtsample.Visibility(...)` pastes with
+`vn_gt_paste_visible` instead: objects hidden behind scene points are rejected on the device,
+and `concat` drops their label lines once the sample's visible counts have arrived in pinned host memory.
 
 The sample's shuffle (utils.py:35) is by default the reference's: `np.random.shuffle` of the host cloud, in the thread that
 also enqueues the train step.  `shuffle_points="index"` / `"device"` move the per-point half to the device (shuffle.py,
@@ -77,6 +79,17 @@ class KITTIDataset(torch.utils.data.Dataset):
         return tag, img, pcl, labels, None
 
 
+def drop_rejected_lines(labels, n_pasted, visible, min_visible):
+    """labels: a sample's label lines whose last `n_pasted` are pasted objects' (possibly moved by the augmentation: one
+    line per input line, in order); visible: their visible counts (vn_gt_paste_visible's out_visible).  -> the lines
+    without those of the rejected objects (visible < min_visible)"""
+    visible = np.asarray(visible).reshape(-1)
+    if visible.shape[0] != n_pasted or n_pasted > len(labels):
+        raise ValueError(f"{visible.shape[0]} visible counts for {n_pasted} pasted lines of {len(labels)} label lines")
+    first = len(labels) - n_pasted
+    return list(labels[:first]) + [line for line, v in zip(labels[first:], visible) if v >= min_visible]
+
+
 class DeviceCollate:
     """collate_fn (dataset.py:70-97) with pcl_to_voxels (utils.py:10-100) run on the device for the whole batch:
     parts = [(tag, img, pcl, labels, _)] -> the reference's 7-tuple, with x[2] / x[3] / x[4] = lists of DEVICE tensors
@@ -111,7 +124,9 @@ class DeviceCollate:
         `gt_sampler.draw(labels, tag)` picks database objects that collide with nothing in the frame; their points are
         pasted into the (cropped) cloud on the device in front of the augmentation (the scene points inside their boxes
         go) and the batch's `label` element holds labels + their lines (moved by the augmentation when it is on).  None:
-        nothing is drawn, nothing is launched."""
+        nothing is drawn, nothing is launched.  A sampler with a `visibility` pastes with vn_gt_paste_visible: the
+        augmentation's draw still runs on labels + the lines of EVERY candidate (a rejected object still takes part in
+        its collision test), and `concat` removes the rejected objects' lines from the sample's (moved) labels."""
         # (strings are truthy: an unknown one must not fall through to the host shuffle)
         if isinstance(shuffle_points, str) and shuffle_points in ("host", "index", "device"):
             self._shuffle_mode = shuffle_points
@@ -141,8 +156,10 @@ class DeviceCollate:
         handles = []
         if self.augment or self.recipe is not None:
             from . import augment as A
+        visibility = None
         if self.gt_sampler is not None:
             from . import gtsample as G
+            visibility = getattr(self.gt_sampler, "visibility", None)
         if self.augment or self.recipe is not None or self.gt_sampler is not None:
             parts = list(parts)
         mode = self._shuffle_mode
@@ -167,9 +184,11 @@ class DeviceCollate:
                 if self.augment:
                     params = A.draw_augmentation(p[3])                         # dataset.py:122-219, host: O(boxes)
                     parts[b] = (p[0], p[1], p[2], A.augment_labels(p[3], params), *p[4:])
+                    assert len(parts[b][3]) == len(p[3])                       # one line per input line, in order
                 elif self.recipe is not None:
                     params = A.draw_compose(p[3], self.recipe)                 # the composed recipe, host: O(boxes^2)
                     parts[b] = (p[0], p[1], p[2], A.compose_labels(p[3], params), *p[4:])
+                    assert len(parts[b][3]) == len(p[3])
                 host = torch.from_numpy(np.ascontiguousarray(pcl[:, :4], dtype=np.float32)).pin_memory()
                 pts = host.to(self.device, non_blocking=True)
                 if mode == "index":
@@ -187,7 +206,14 @@ class DeviceCollate:
                     # padded form: no 4-byte read-back per sample (it would stall the host behind everything queued
                     # on this stream); the rows past the device-side count are NaN points, which the voxelizer drops
                     pts, _ = fov_crop_device(pts, P, Tr, R, rows, cols, padded=True)
-                if pasted is not None:
+                rejects = None
+                if pasted is not None and visibility is not None:
+                    # the same place; the visible counts follow in pinned memory (concat reads them): the sample's last
+                    # len(pasted.lines) label lines are pasted ones
+                    pts, keep, visible = G.enqueue_gt_paste_visible(pts, pasted, visibility)
+                    host = (host, keep)
+                    rejects = (visible, len(pasted.lines), visibility.min_visible)
+                elif pasted is not None:
                     # behind the copy / the crop on this stream; the NaN rows of the padded crop go, NaN rows come out, so
                     # the count is not read back either; `keep` = the staged table and object points
                     pts, keep = G.enqueue_gt_paste(pts, pasted)
@@ -200,20 +226,27 @@ class DeviceCollate:
                 elif self.recipe is not None:
                     pts, keep = A.enqueue_compose_points(pts, params, out=pts)          # the same place, one launch
                     host = (host, keep)
-                handles.append((voxelize_device_async(pts, self.grid, b, coord_cols=4), pts, host))
+                handles.append((voxelize_device_async(pts, self.grid, b, coord_cols=4), pts, host, rejects))
         return parts, handles
 
     def concat(self, launched):
         """second stage, still on the pipeline's stream: slice the capacity-sized outputs to K and make the concatenations
         the model starts with (RPN3D.detect) — off the train step's dependency chain.  `DeviceBatcher` calls this for
         batch i BEFORE it launches batch i+1, so the concatenation of batch i is queued behind batch i's own voxelizer
-        only (queued behind the next batch's copies, crop and voxelization it would make step i wait for all of them)."""
+        only (queued behind the next batch's copies, crop and voxelization it would make step i wait for all of them).
+        With a visibility sampler this is also where the label lines of the objects the device rejected go: the counts
+        were copied to pinned memory in front of the sample's voxelizer, whose result is waited for here anyway."""
         if len(launched) == 5:
             return launched
         parts, handles = launched
         feats, nums, coords = [], [], []
-        for h, _, _ in handles:
+        for b, (h, _, _, rejects) in enumerate(handles):
             f, c, n = h.result()                    # waits for the 4-byte K copy of this sample only
+            if rejects is not None:
+                # everything queued earlier on the pipeline's stream has run: the pinned counts are there
+                visible, n_pasted, min_visible = rejects
+                p = parts[b]
+                parts[b] = (p[0], p[1], p[2], drop_rejected_lines(p[3], n_pasted, visible.numpy(), min_visible), *p[4:])
             feats.append(f)
             coords.append(c)
             nums.append(n)

@@ -17,9 +17,14 @@ Inside, for a float32 point widened exactly to float64, evaluated as written wit
     inside  <=>  |u| <= hl  and  |v| <= hw  and  pz >= z0  and  pz <= z1                  (inclusive; a NaN anywhere fails)
 
 Objects are pasted at their source position: all frames share the lidar frame.  Stated divergences from SECOND: no
-ground-plane alignment of a pasted object, no check that it is visible from the sensor, the mean calibration as
-everywhere in targets.py, and pasted points come after all scene points (in a voxel shared with surviving scene points
-the scene points win the T slots)."""
+ground-plane alignment of a pasted object, no check that it is visible from the sensor (unless the sampler carries a
+`Visibility`: below), the mean calibration as everywhere in targets.py, and pasted points come after all scene points (in
+a voxel shared with surviving scene points the scene points win the T slots).
+
+`GTSampler(..., visibility=Visibility())` switches the paste to `vn_gt_paste_visible`: a
+coarse range image of the frame rejects objects hidden behind scene points, drops the hidden points of the others and
+whatever lies in their shadow; `DeviceCollate` then drops the label lines of the rejected objects."""
+import ctypes
 import os
 from dataclasses import dataclass
 
@@ -181,16 +186,66 @@ class GTDatabase:
 class GTSampleParams:
     """one frame's draw, in acceptance order: `table` (G,) BOX_DTYPE, `points` (M,4) float32 = the accepted objects'
     points concatenated, `boxes` (G,7) float64, `lines` = their stored label lines (the frame's labels become
-    labels + lines)"""
+    labels + lines), `offsets` (G+1,) int32 = object o owns points[offsets[o]:offsets[o+1]] (GTSampler.draw fills it;
+    only the visibility paste reads it)"""
     table: np.ndarray
     points: np.ndarray
     boxes: np.ndarray
     lines: list
+    offsets: np.ndarray = None
+
+
+@dataclass(frozen=True)
+class Visibility:
+    """the range image of the occlusion-consistent paste (vnVisGrid): four side faces of a cube
+    around the sensor, `nu` bins across a face and `nv` rows over v = z / max(|x|, |y|) in [v_lo, v_hi); a point lies
+    behind another one when its depth exceeds the other's by more than `margin` metres (inf: never); a pasted object
+    needs `min_visible` visible points.  The defaults are about one HDL-64 beam per row and are not tuned."""
+    nu: int = 512
+    nv: int = 64
+    v_lo: float = -0.47
+    v_hi: float = 0.10
+    margin: float = 0.3
+    min_visible: int = 5
+
+    def __post_init__(self):
+        for name in ("nu", "nv", "min_visible"):
+            v = getattr(self, name)
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"Visibility.{name}={v!r}: expected an integer")
+            object.__setattr__(self, name, int(v))
+        for name in ("v_lo", "v_hi", "margin"):
+            object.__setattr__(self, name, float(getattr(self, name)))
+        if not (2 <= self.nu <= 2048 and self.nu % 2 == 0):
+            raise ValueError(f"Visibility.nu={self.nu}: expected an even number in 2..2048")
+        if not 1 <= self.nv <= 256:
+            raise ValueError(f"Visibility.nv={self.nv}: expected 1..256")
+        if not (np.isfinite(self.v_lo) and np.isfinite(self.v_hi) and self.v_lo < self.v_hi):
+            raise ValueError(f"Visibility.v_lo={self.v_lo}, v_hi={self.v_hi}: expected finite v_lo < v_hi")
+        if not self.margin >= 0.0:                                   # (NaN fails; inf passes)
+            raise ValueError(f"Visibility.margin={self.margin}: expected >= 0 (inf allowed)")
+        if not 0 <= self.min_visible < 2 ** 31:
+            raise ValueError(f"Visibility.min_visible={self.min_visible}: expected 0..2^31-1")
+        if not (np.isfinite(self.v_scale) and self.v_scale > 0.0):
+            raise ValueError(f"Visibility: nv / (v_hi - v_lo) = {self.v_scale} is not a positive finite number")
+
+    @property
+    def v_scale(self):
+        return float(np.float64(self.nv) / (np.float64(self.v_hi) - np.float64(self.v_lo)))
+
+    def grid(self):
+        """-> the vnVisGrid the library reads during the call"""
+        return _lib.VnVisGrid(self.nu, self.nv, self.v_lo, self.v_hi, self.v_scale, self.margin, self.min_visible, 0)
 
 
 class GTSampler:
-    def __init__(self, db, per_class=None, min_points=5):
-        """per_class: {class: the number of objects of that class a frame is filled up to}, drawn in its order"""
+    def __init__(self, db, per_class=None, min_points=5, visibility=None):
+        """per_class: {class: the number of objects of that class a frame is filled up to}, drawn in its order.
+        visibility: a `Visibility` — DeviceCollate then pastes with vn_gt_paste_visible and drops the label lines of the
+        objects it rejects; the draw itself is the same, random numbers included.  None: the plain paste."""
+        if visibility is not None and not isinstance(visibility, Visibility):
+            raise ValueError(f"visibility={visibility!r}: expected None or a gtsample.Visibility")
+        self.visibility = visibility
         self.db = db
         self.per_class = dict(per_class if per_class is not None else {"Car": 15})
         self.min_points = int(min_points)
@@ -221,7 +276,9 @@ class GTSampler:
                 taken.append(cand)
         boxes = np.array([e.box for e in taken], dtype=np.float64).reshape(-1, 7)
         points = np.concatenate([e.points for e in taken] + [np.zeros((0, 4), np.float32)]).astype(np.float32, copy=False)
-        return GTSampleParams(box_table(boxes), points, boxes, [e.line for e in taken])
+        offsets = np.zeros(len(taken) + 1, dtype=np.int32)
+        offsets[1:] = np.cumsum([e.points.shape[0] for e in taken], dtype=np.int64)
+        return GTSampleParams(box_table(boxes), points, boxes, [e.line for e in taken], offsets)
 
 
 def _paste(points, params, cap):
@@ -266,3 +323,92 @@ def gt_paste_device(points, params, padded=False, cap=None):
     if padded:
         return out, count
     return out[:int(count.item())]
+
+
+class GTVisibleResult:
+    """what vn_gt_paste_visible reports besides the cloud, held on the device until it is read: `visible` (G,) int32 =
+    the visible points per object, `accepted` (G,) bool = visible >= min_visible, `kept` (G,) int32 = the points per
+    object in the output, `stats` (2,) int32 = scene rows removed by an accepted box / by shadow only.  Each attribute is a
+    NumPy array read back from the device (a host synchronisation) when it is asked for."""
+
+    def __init__(self, visible, kept, stats, min_visible):
+        self._visible, self._kept, self._stats, self.min_visible = visible, kept, stats, int(min_visible)
+
+    @property
+    def visible(self):
+        return self._visible.cpu().numpy()
+
+    @property
+    def kept(self):
+        return self._kept.cpu().numpy()
+
+    @property
+    def stats(self):
+        return self._stats.cpu().numpy()
+
+    @property
+    def accepted(self):
+        return self.visible >= self.min_visible
+
+
+def _paste_visible(points, params, visibility, cap):
+    _check_points(points, "gt_paste_visible_device")
+    if not isinstance(visibility, Visibility):
+        raise ValueError(f"visibility={visibility!r}: expected a gtsample.Visibility")
+    dev, n = points.device, points.shape[0]
+    obj_host = np.array(params.points, dtype=np.float32).reshape(-1, 4)          # (a copy: the staging needs a writable array)
+    m = int(obj_host.shape[0])
+    if params.offsets is None:
+        raise _lib.VoxelnetHipError("vn_gt_paste_visible needs params.offsets (GTSampler.draw fills it)")
+    offsets = np.ascontiguousarray(params.offsets, dtype=np.int32).reshape(-1)   # host memory, read during the call
+    cap = n + m if cap is None else int(cap)
+    keep = (points,)
+    with _lib.on_device(dev):
+        ptr, g, staged = _stage_table(params.table, dev, "vn_gt_paste_visible")
+        if offsets.shape[0] != g + 1:
+            raise _lib.VoxelnetHipError(f"{offsets.shape[0]} offsets for {g} table entries; vn_gt_paste_visible needs {g + 1}")
+        keep += staged
+        obj_ptr = None
+        if m:
+            host = torch.from_numpy(obj_host).pin_memory()
+            obj = host.to(dev, non_blocking=True)
+            obj_ptr = obj.data_ptr()
+            keep += (host, obj)
+        out = torch.empty((max(cap, 1), 4), dtype=torch.float32, device=dev)
+        # count | stats[2] | visible[g] | kept[g]: one allocation, every slice 4-byte aligned
+        ints = torch.empty(3 + 2 * g, dtype=torch.int32, device=dev)
+        count, stats, visible, kept = ints[0:1], ints[1:3], ints[3:3 + g], ints[3 + g:3 + 2 * g]
+        grid = visibility.grid()
+        nbytes = _lib.load().vn_gt_paste_visible_workspace_bytes(n, m, ctypes.byref(grid))
+        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+        _lib.call("vn_gt_paste_visible", points.data_ptr(), n, ptr, g, obj_ptr, m, offsets.ctypes.data, ctypes.byref(grid),
+                  out.data_ptr(), cap, count.data_ptr(), visible.data_ptr() if g else None, kept.data_ptr() if g else None,
+                  stats.data_ptr(), ws.data_ptr(), ws.numel(), _lib.raw_stream())
+    return out[:max(cap, 0)], count, GTVisibleResult(visible, kept, stats, visibility.min_visible), keep + (ints, ws)
+
+
+def enqueue_gt_paste_visible(points, params, visibility, cap=None):
+    """the occlusion-consistent paste without host synchronisation -> (out: the capacity-sized buffer of enqueue_gt_paste,
+    tensors the queued work reads or writes: keep them referenced until the stream has run it, visible: a PINNED host
+    (G,) int32 tensor — it is also among the kept references — into which a device->host copy of the visible counts is
+    queued right behind the call: valid once the stream has run that copy; object o is accepted when visible[o] >=
+    visibility.min_visible)."""
+    out, _, res, keep = _paste_visible(points, params, visibility, cap)
+    with _lib.on_device(points.device):
+        visible = torch.empty(res._visible.shape[0], dtype=torch.int32).pin_memory()
+        visible.copy_(res._visible, non_blocking=True)
+    return out, keep + (visible,), visible
+
+
+def gt_paste_visible_device(points, params, visibility, padded=False, cap=None):
+    """points: contiguous (N,4) float32 HIP tensor; params: a GTSampleParams with `offsets`; visibility: a Visibility ->
+    (the pasted cloud, the count, a GTVisibleResult): the scene rows that are not NaN points, lie in no accepted object's
+    box and in no accepted object's shadow, in input order, then the kept points of the accepted objects (a view of the
+    capacity-sized buffer sliced to the count, which is then a Python int: one device->host read of 4 bytes).
+    padded=True: no host synchronisation — the whole buffer, whose rows past the count are NaN points, and the count as a
+    device int32 tensor.  Raises VoxelnetHipError for anything but a HIP tensor."""
+    out, count, res, _ = _paste_visible(points, params, visibility, cap)
+    if padded:
+        return out, count, res
+    k = int(count.item())
+    return out[:k], k, res
