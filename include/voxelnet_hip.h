@@ -1273,6 +1273,48 @@ int vn_rpn_targets_iou(const double *anchors, int32_t n_anchors, const double *g
                        int32_t *matched /*[B,n_anchors] ground-truth index or -1; may be NULL*/, void *workspace,
                        size_t workspace_bytes, vnStream stream);
 
+/* ---- RPN training targets by ATSS (csrc/targets_atss.hip) -------------------------------------------
+ * Adaptive Training Sample Selection (Zhang et al., CVPR 2020): instead of the two fixed thresholds of the calls above,
+ * every ground-truth box takes the anchors nearest to it as candidates and sets its own IoU threshold from them.  Same
+ * anchors, gt, gt_count and output maps as vn_rpn_targets_iou; the anchors' two rotations stand for the paper's pyramid
+ * levels.  All arithmetic is float64.
+ * Inputs: anchors [n_anchors,7], anchor n = site * 2 + rotation, n_anchors even; group a = the anchors with (n & 1) == a.
+ *   gt [B,max_gt,7] = (x, y, z, h, w, l, r); gt_count[b] (device) is clamped to [0, max_gt]; 1 <= top_k <= VN_ATSS_MAX_TOPK.
+ * Validity: box k of sample b is valid when k < gt_count[b], all seven fields are finite and h, w, l > 0.  An invalid box has
+ *   no candidates, makes no positive and gets stats of zeros.
+ * For a valid box k:
+ *   1. d2(n,k) = dx*dx + dy*dy with dx = x_n - x_k, dy = y_n - y_k (a NaN d2 — an anchor without a position — counts as +inf).
+ *   2. C_k = the union over the two groups of the min(top_k, n_anchors / 2) anchors of the group with the smallest (d2, n)
+ *      in lexicographic order: equal d2 goes to the smaller n.  |C_k| = 2 min(top_k, n_anchors / 2) >= 2.
+ *   3. v(n,k) for n in C_k: the IoU of iou_kind (VN_ASSIGN_STANDUP or VN_ASSIGN_ROTATED) exactly as vn_rpn_targets_iou
+ *      computes it for the pair — the same device functions.
+ *   4. mu_k = sum(v) / |C_k|;  sd_k = sqrt(sum((v - mu_k)^2) / (|C_k| - 1)) (the unbiased estimate, the published code's
+ *      std);  t_k = mu_k + sd_k.  Both sums run over C_k in one fixed order: group 0's candidates by ascending (d2, n),
+ *      then group 1's.
+ *   5. Box k accepts n in C_k when v(n,k) >= t_k, v(n,k) > 0 and the anchor's centre lies inside the box's bird's-eye
+ *      footprint: with c = cos r_k, s = sin r_k, u = dx*c + dy*s (along the box's LENGTH l, its local x axis) and
+ *      w' = -(dx*s) + dy*c (along its WIDTH w), |u| <= l/2 and |w'| <= w/2 — the edge is inside.  (The footprint of
+ *      vn_box_iou_rotated and vn_points_in_boxes: l along the heading r, w across it.)
+ *   6. matched[n] = the box that accepted n with the largest v(n,k), the smallest k among equals; -1 when none did.
+ *      [B,n_anchors] int32, or NULL.  pos = matched >= 0;  neg = not pos: there is no ignore band and no forced positive,
+ *      and every anchor of a sample without a box is negative.
+ *      targets: vn_rpn_targets_iou's encoding of gt[matched[n]] on anchor n, float64 rounded to float32; zeros for a
+ *      non-positive.
+ *   7. stats [B,max_gt,4] float64, or NULL: (mu_k, sd_k, t_k, the number of anchors with matched == k); zeros for an invalid
+ *      box and for k >= gt_count[b].  A box that ends with no anchor — off the grid (every v is 0, stats all zero), or no
+ *      candidate centre inside it — is plain ATSS behaviour and shows here.
+ * Limits as vn_rpn_targets_iou.  VN_EINVAL, before anything is launched, for a size outside the limits, an odd n_anchors,
+ * top_k outside its range, an unknown iou_kind, a null pointer (matched and stats excepted) or anchor_h == 0; VN_EWORKSPACE
+ * for a workspace below the query's answer (0 for unsupported sizes).  Asynchronous on `stream`, no host synchronisation;
+ * no floating-point atomics, integer atomics of order-independent results only: outputs are bit-identical from run to run. */
+#define VN_ATSS_MAX_TOPK 32
+size_t vn_rpn_targets_atss_workspace_bytes(int32_t B, int32_t n_anchors, int32_t max_gt, int32_t top_k);
+int vn_rpn_targets_atss(const double *anchors, int32_t n_anchors, const double *gt /*[B,max_gt,7]*/,
+                        const int32_t *gt_count /*device [B]*/, int32_t B, int32_t max_gt, int32_t iou_kind, int32_t top_k,
+                        double anchor_h, float *pos, float *neg, float *targets, int32_t *matched /*may be NULL*/,
+                        double *stats /*[B,max_gt,4]; may be NULL*/, void *workspace, size_t workspace_bytes,
+                        vnStream stream);
+
 /* ---- inference tail (voxelnet/model.py:364-395 RPN3D.predict: utils.deltas_to_boxes_3d utils.py:476-489,
  * filter_boxes model.py:28-57, utils.nms utils.py:492-553) ----------------------------------------------
  * probs (B,2,h,w) and deltas (B,14,h,w): the module's fp32 NCHW outputs, read as the flat (B, n_anchors) and

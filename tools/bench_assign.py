@@ -1,10 +1,11 @@
-"""Time the three target assigners and the two detection layouts, alternated inside one process.
+"""Time the four target assigners and the two detection layouts (DESIGN.md sections 1h, 1o), alternated inside one process.
 
 1. Assignment on the full Car grid (70,400 anchors), B = 2, with 8 and with 128 boxes per frame: us per call (every launch
-   of the call: vn_rpn_targets' three, vn_rpn_targets_iou's memset + three) for
+   of the call: vn_rpn_targets' three, vn_rpn_targets_iou's memset + three, vn_rpn_targets_atss' memset + three) for
      reference   vn_rpn_targets (the reference's assignment; its stand-up rectangles are made on the host beforehand)
      standup     vn_rpn_targets_iou, VN_ASSIGN_STANDUP
      rotated     vn_rpn_targets_iou, VN_ASSIGN_ROTATED
+     atss        vn_rpn_targets_atss, VN_ASSIGN_ROTATED, top_k = --atss-top-k (9), no stats; its ratio to `rotated` is printed
    and, from the same run, the encoder's forward (RPN3D.feature_net on the benchmark's two Car frames, bf16 mode) — the
    assigner runs on the targets stream beside it, off the step's dependency chain.
 2. The evaluation tail at predict.EVAL_DECODE (pre-NMS 1024, rotated NMS at 0.1, cap 20) on random full-grid maps, B = 2:
@@ -14,7 +15,8 @@
                            layout replaces
 Method of tools/bench_loss.py: per arm and round --round-launches calls back to back between two device events, the arms
 alternated round by round; reported: median [min, max] over the rounds.  No threshold is set on these numbers.
-usage: python tools/bench_assign.py [--rounds 20] [--round-launches 50] [--out FILE]"""
+--assign-only leaves out the encoder and the evaluation tail.
+usage: python tools/bench_assign.py [--rounds 20] [--round-launches 50] [--atss-top-k 9] [--assign-only] [--out FILE]"""
 import argparse
 import os
 import statistics
@@ -43,6 +45,8 @@ def say(s):
 ap = argparse.ArgumentParser()
 ap.add_argument("--rounds", type=int, default=20)
 ap.add_argument("--round-launches", type=int, default=50)
+ap.add_argument("--atss-top-k", type=int, default=9)
+ap.add_argument("--assign-only", action="store_true")
 ap.add_argument("--out")
 args = ap.parse_args()
 if not torch.cuda.is_available():
@@ -79,6 +83,12 @@ def assigner(kind, G):
         a = (anchors.data_ptr(), N, gt.data_ptr(), g2.data_ptr(), cnt.data_ptr(), B, G, cfg["pos_iou"], cfg["neg_iou"], cfg["h"],
              pos.data_ptr(), neg.data_ptr(), tgt.data_ptr(), ws.data_ptr(), nb, st)
         name = "vn_rpn_targets"
+    elif kind == "atss":
+        nb = lib.vn_rpn_targets_atss_workspace_bytes(B, N, G, args.atss_top_k)
+        ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+        a = (anchors.data_ptr(), N, gt.data_ptr(), cnt.data_ptr(), B, G, _lib.VN_ASSIGN_ROTATED, args.atss_top_k, cfg["h"],
+             pos.data_ptr(), neg.data_ptr(), tgt.data_ptr(), None, None, ws.data_ptr(), nb, st)
+        name = "vn_rpn_targets_atss"
     else:
         nb = lib.vn_rpn_targets_iou_workspace_bytes(B, N, G)
         ws = torch.empty(nb, dtype=torch.uint8, device=dev)
@@ -91,19 +101,20 @@ def assigner(kind, G):
 
 arms = []
 for G in (8, 128):
-    for kind in ("reference", "standup", "rotated"):
+    for kind in ("reference", "standup", "rotated", "atss"):
         run, keep = assigner(kind, G)
         arms.append((f"assign {kind}", f"{G} boxes", run, keep))
 
 # the encoder's forward on the benchmark's two Car frames
-M.set_precision("bf16")
-model = M.RPN3D("Car").to(dev).eval()
-grid = grid_config("Car")
 feats, coords = [], []
-for b, cloud in enumerate(synth.workload_frames(1, batch=B)):
-    f, c, _ = voxelize_device(torch.from_numpy(cloud).to(dev), grid, b, coord_cols=4)
-    feats.append(f)
-    coords.append(c)
+if not args.assign_only:
+    M.set_precision("bf16")
+    model = M.RPN3D("Car").to(dev).eval()
+    grid = grid_config("Car")
+    for b, cloud in enumerate(synth.workload_frames(1, batch=B)):
+        f, c, _ = voxelize_device(torch.from_numpy(cloud).to(dev), grid, b, coord_cols=4)
+        feats.append(f)
+        coords.append(c)
 
 
 def encoder():
@@ -111,7 +122,8 @@ def encoder():
         model.feature_net(feats, coords)
 
 
-arms.append(("encoder forward", f"K = {sum(f.shape[0] for f in feats)}", encoder, None))
+if not args.assign_only:
+    arms.append(("encoder forward", f"K = {sum(f.shape[0] for f in feats)}", encoder, None))
 
 # the detection tail
 rng = np.random.default_rng(5)
@@ -136,9 +148,10 @@ def flat_with_transposes():
     detect(probs.permute(0, 2, 3, 1).contiguous(), deltas.permute(0, 2, 3, 1).contiguous(), _lib.VN_DETECT_FLAT)
 
 
-arms.append(("detect flat", f"pre {pre}", lambda: detect(probs, deltas, _lib.VN_DETECT_FLAT), None))
-arms.append(("detect site", f"pre {pre}", lambda: detect(probs, deltas, _lib.VN_DETECT_SITE), None))
-arms.append(("detect flat + 2 transposes", f"pre {pre}", flat_with_transposes, None))
+if not args.assign_only:
+    arms.append(("detect flat", f"pre {pre}", lambda: detect(probs, deltas, _lib.VN_DETECT_FLAT), None))
+    arms.append(("detect site", f"pre {pre}", lambda: detect(probs, deltas, _lib.VN_DETECT_SITE), None))
+    arms.append(("detect flat + 2 transposes", f"pre {pre}", flat_with_transposes, None))
 
 for _, _, run, _ in arms:                              # warm-up: code objects, the caches
     for _ in range(10):
@@ -161,6 +174,9 @@ say(f"== target assignment (full Car grid, {N} anchors, B = {B}) and the evaluat
 for a, b, *_ in arms:
     v = us[(a, b)]
     say(f"{a:28s} {b:12s} {statistics.median(v):9.2f} [{min(v):8.2f}, {max(v):8.2f}]")
+for G in (8, 128):
+    r, t = statistics.median(us[("assign rotated", f"{G} boxes")]), statistics.median(us[("assign atss", f"{G} boxes")])
+    say(f"atss (top_k {args.atss_top_k}) / rotated at {G} boxes: {t:.2f} / {r:.2f} = {t / r:.2f}")
 if args.out:
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     open(args.out, "w").write("\n".join(lines) + "\n")

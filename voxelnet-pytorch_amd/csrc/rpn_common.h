@@ -1,4 +1,4 @@
-// Shared by the RPN tail — iou_loss.hip, dir_head.hip, iou_head.hip, predict.hip, detect.hip, targets.hip, targets_iou.hip — and by nothing
+// Shared by the RPN tail — iou_loss.hip, dir_head.hip, iou_head.hip, predict.hip, detect.hip, targets.hip, targets_iou.hip, targets_atss.hip — and by nothing
 // else: the ONE copy of the anchor box codec and of the scaffold of a loss term summed over the (B, h, w) anchor sites
 // (DESIGN.md 1j).  common.h goes into every translation unit; the two kernels here do not belong in the convolution files.
 #pragma once
@@ -65,6 +65,29 @@ __device__ __forceinline__ void vn_box_encode(const double *g, const double *a, 
     t[4] = (float)log(g[4] / a[4]);
     t[5] = (float)log(g[5] / a[5]);
     t[6] = (float)(g[6] - a[6]);
+}
+
+// ---- the stand-up IoU of the target assignments (targets_iou.hip, targets_atss.hip) ----
+// the axis-aligned hull of the rotated footprint of (x, y, ., ., w, l, r) as (x, y, half width hx, half height hy, area)
+__device__ __forceinline__ void ti_hull(const double (&q)[7], double (&h)[5]) {
+    const double c = fabs(cos(q[6])), s = fabs(sin(q[6]));
+    h[0] = q[0]; h[1] = q[1];
+    h[2] = (q[5] * c + q[4] * s) / 2;
+    h[3] = (q[5] * s + q[4] * c) / 2;
+    h[4] = (2.0 * h[2]) * (2.0 * h[3]);
+}
+
+// The overlap of [xa - ha, xa + ha] and [xg - hg, xg + hg] written from the centres: min(ha + hg - |xg - xa|, 2 min(ha, hg)).
+// Where one interval contains the other the second term is taken, which does not depend on the position: the anchors of a
+// row that all contain a box's hull along x (or lie inside it) get THE SAME IoU bit for bit, not values that differ by the
+// rounding of x +- ha, and the smallest index wins the tie in every implementation that writes the overlap this way.
+__device__ __forceinline__ double ti_standup_iou(const double (&a)[5], const double *__restrict__ g) {
+    const double iw = fmin((a[2] + g[2]) - fabs(g[0] - a[0]), 2.0 * fmin(a[2], g[2]));
+    const double ih = fmin((a[3] + g[3]) - fabs(g[1] - a[1]), 2.0 * fmin(a[3], g[3]));
+    if (!(iw > 0.0) || !(ih > 0.0)) return 0.0;
+    const double inter = iw * ih;
+    const double v = inter / ((a[4] + g[4]) - inter);
+    return v > 0.0 ? v : 0.0;          // (a NaN from infinite extents is 0)
 }
 
 // stand-up rectangle (x1, y1, x2, y2) of a float32 box (utils.py:230-252, 283-330): float64 rotation, float32 corners

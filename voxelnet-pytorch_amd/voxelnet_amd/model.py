@@ -1060,8 +1060,9 @@ class RPN3D(nn.Module):
     iou_loss, iou_weight, iou_metric = None, 1.0, "3d"
     last_iou = None          # the latest (L_iou, mean_iou) pair: detached device scalars, no synchronisation
     # how anchors are assigned to ground truths (targets.TargetGenerator(assign=)): "reference" keeps the
-    # reference's assignment, "standup" / "rotated" assign by a real IoU
-    target_assign = "reference"
+    # reference's assignment, "standup" / "rotated" assign by a real IoU, "atss" by every box's own threshold over its
+    # atss_top_k nearest anchors per rotation, IoU of kind atss_iou
+    target_assign, atss_top_k, atss_iou = "reference", 9, "rotated"
     # the direction-classifier head (voxelnet_amd/dir_head.py): False = nothing is registered or launched
     dir_head, dir_weight, dir_offset = False, 0.2, math.pi / 4
     last_dir = None          # the latest (L_dir, acc) pair: detached device scalars, no synchronisation
@@ -1078,12 +1079,16 @@ class RPN3D(nn.Module):
     def __init__(self, cls_name="Car", alpha=ALPHA, beta=BETA, sigma=SIGMA, *, cls_loss="bce", focal_alpha=0.25, focal_gamma=2.0,
                  yaw_loss="diff", iou_loss=None, iou_weight=1.0, iou_metric="3d", target_assign="reference", dir_head=False,
                  dir_weight=0.2, dir_offset=math.pi / 4, anchor_area_threshold=None, iou_head=False, iou_head_weight=1.0,
-                 iou_head_metric="3d", iou_rectify=0.5):
+                 iou_head_metric="3d", iou_rectify=0.5, atss_top_k=9, atss_iou="rotated"):
         super().__init__()
-        from .targets import ASSIGN_KINDS
+        from .targets import ASSIGN_KINDS, ATSS_IOU_KINDS, ATSS_MAX_TOPK
         if target_assign not in ASSIGN_KINDS:
             raise ValueError(f"target_assign must be one of {sorted(ASSIGN_KINDS)}, not {target_assign!r}")
-        self.target_assign = target_assign
+        if isinstance(atss_top_k, bool) or not isinstance(atss_top_k, int) or not 1 <= atss_top_k <= ATSS_MAX_TOPK:
+            raise ValueError(f"atss_top_k must be an int in 1..{ATSS_MAX_TOPK}, not {atss_top_k!r}")
+        if atss_iou not in ATSS_IOU_KINDS:
+            raise ValueError(f"atss_iou must be one of {sorted(ATSS_IOU_KINDS)}, not {atss_iou!r}")
+        self.target_assign, self.atss_top_k, self.atss_iou = target_assign, atss_top_k, atss_iou
         if anchor_area_threshold is not None:
             from .anchor_mask import check_threshold
             self.anchor_area_threshold = check_threshold(anchor_area_threshold)
@@ -1181,9 +1186,10 @@ class RPN3D(nn.Module):
         from .targets import TargetGenerator
         gen = self.__dict__.get("_targets")
         if (gen is None or gen.device != torch.device(device) or gen.assign != self.target_assign
-                or gen.keep_heading != bool(self.dir_head)):
+                or gen.keep_heading != bool(self.dir_head) or gen.atss_top_k != self.atss_top_k or gen.atss_iou != self.atss_iou):
             # (with the direction head the labels keep their heading: its target is the bin of the box's yaw)
-            gen = TargetGenerator(self.cls_name, device, assign=self.target_assign, keep_heading=bool(self.dir_head))
+            gen = TargetGenerator(self.cls_name, device, assign=self.target_assign, keep_heading=bool(self.dir_head),
+                                  atss_top_k=self.atss_top_k, atss_iou=self.atss_iou)
             # the maps the network EMITS, not rpn_output_shape: for Pedestrian / Cyclist that attribute repeats the anchor
             # grid (100 x 120, as the reference has it) while block 1 does not stride and the maps are 200 x 240
             g, s = grid_config(self.cls_name), self.middle_rpn._block1_stride

@@ -10,7 +10,8 @@ There is no CPU fallback: the HIP library must be present.
 
 `TargetGenerator(assign=)`: "reference" is that assignment, quirks included; "standup" and "rotated" assign by a real IoU
 (csrc/targets_iou.hip, `vn_rpn_targets_iou`) — what a model that is to be evaluated has to be
-trained with."""
+trained with.  "atss" (csrc/targets_atss.hip, `vn_rpn_targets_atss`) drops the two fixed
+thresholds: every box takes the `atss_top_k` nearest anchors of each rotation and sets its own threshold from their IoUs."""
 import ctypes
 import os
 
@@ -20,7 +21,10 @@ import torch
 from . import _lib
 
 MAX_GT = 128     # VN_TARGETS_MAX_GT (include/voxelnet_hip.h)
-ASSIGN_KINDS = {"reference": None, "standup": _lib.VN_ASSIGN_STANDUP, "rotated": _lib.VN_ASSIGN_ROTATED}
+# assign -> vn_rpn_targets_iou's iou_kind (None: not that call — "reference" is vn_rpn_targets, "atss" vn_rpn_targets_atss)
+ASSIGN_KINDS = {"reference": None, "standup": _lib.VN_ASSIGN_STANDUP, "rotated": _lib.VN_ASSIGN_ROTATED, "atss": None}
+ATSS_IOU_KINDS = {"standup": _lib.VN_ASSIGN_STANDUP, "rotated": _lib.VN_ASSIGN_ROTATED}
+ATSS_MAX_TOPK = 32     # VN_ATSS_MAX_TOPK
 
 # voxelnet/config.py:36-92 (anchor geometry, IoU thresholds) and :99-111 (mean KITTI calibration)
 CLASS_CFG = {
@@ -126,12 +130,21 @@ class TargetGenerator:
     assign: "reference" — the reference's assignment (vn_rpn_targets); "standup" / "rotated" — by the IoU of the stand-up
     hulls / of the rotated footprints (vn_rpn_targets_iou), pos and neg then exclusive.  pos_iou /
     neg_iou: the two thresholds (default: the class's).  keep_heading: label lines are parsed with their heading
-    (label_to_gt_box_3d), so that targets[..., 7a+6] + the anchor's yaw is the box's yaw and not its fold into [-pi/2, pi/2)."""
+    (label_to_gt_box_3d), so that targets[..., 7a+6] + the anchor's yaw is the box's yaw and not its fold into [-pi/2, pi/2).
+    assign "atss" (vn_rpn_targets_atss): per box the atss_top_k (1..32) nearest anchors of each rotation
+    are its candidates, its threshold is the mean + standard deviation of their IoUs (atss_iou: "rotated" or "standup"), and a
+    candidate at or above it whose centre lies inside the box is positive; every other anchor is negative.  pos_iou / neg_iou
+    are accepted and IGNORED for "atss"; atss_top_k / atss_iou are checked always and used by "atss" only."""
 
     def __init__(self, cls_name="Car", device="cuda:0", anchors=None, assign="reference", pos_iou=None, neg_iou=None,
-                 keep_heading=False):
+                 keep_heading=False, atss_top_k=9, atss_iou="rotated"):
         if assign not in ASSIGN_KINDS:
             raise ValueError(f"assign must be one of {sorted(ASSIGN_KINDS)}, not {assign!r}")
+        if isinstance(atss_top_k, bool) or not isinstance(atss_top_k, (int, np.integer)) or not 1 <= atss_top_k <= ATSS_MAX_TOPK:
+            raise ValueError(f"atss_top_k must be an int in 1..{ATSS_MAX_TOPK}, not {atss_top_k!r}")
+        if atss_iou not in ATSS_IOU_KINDS:
+            raise ValueError(f"atss_iou must be one of {sorted(ATSS_IOU_KINDS)}, not {atss_iou!r}")
+        self.atss_top_k, self.atss_iou = int(atss_top_k), atss_iou
         self.cls_name = cls_name
         self.cfg = CLASS_CFG[cls_name]
         self.assign = assign
@@ -163,12 +176,14 @@ class TargetGenerator:
         N = self.n_anchors
         return (mask_probs(pos, anchor_mask, N, _lib.VN_DETECT_FLAT), mask_probs(neg, anchor_mask, N, _lib.VN_DETECT_FLAT)) + tuple(out[2:])
 
-    def _from_boxes_iou(self, gt_boxes, return_matched):
-        """assign = "standup" / "rotated": everything per box happens on the device too (no stand-up rectangles here)"""
+    def _from_boxes_iou(self, gt_boxes, return_matched, return_stats=False):
+        """assign = "standup" / "rotated" / "atss": everything per box happens on the device too (no stand-up rectangles here)"""
+        atss = self.assign == "atss"
+        name = "vn_rpn_targets_atss" if atss else "vn_rpn_targets_iou"
         B = len(gt_boxes)
         G = max([b.shape[0] for b in gt_boxes] + [1])
         if G > MAX_GT:
-            raise _lib.VoxelnetHipError(f"{G} ground-truth boxes in one sample; vn_rpn_targets_iou takes at most {MAX_GT}")
+            raise _lib.VoxelnetHipError(f"{G} ground-truth boxes in one sample; {name} takes at most {MAX_GT}")
         gt = np.zeros((B, G, 7), dtype=np.float64)
         cnt = np.zeros(B, dtype=np.int32)
         for b, boxes in enumerate(gt_boxes):
@@ -180,6 +195,18 @@ class TargetGenerator:
         neg = torch.empty((B, *self.shape, 2), dtype=torch.float32, device=dev)
         tgt = torch.empty((B, *self.shape, 14), dtype=torch.float32, device=dev)
         matched = torch.empty((B, *self.shape, 2), dtype=torch.int32, device=dev) if return_matched else None
+        if atss:
+            stats = torch.empty((B, G, 4), dtype=torch.float64, device=dev) if return_stats else None
+            nbytes = _lib.load().vn_rpn_targets_atss_workspace_bytes(B, N, G, self.atss_top_k)
+            if nbytes == 0:
+                raise _lib.VoxelnetHipError("vn_rpn_targets_atss_workspace_bytes: unsupported sizes")
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            with _lib.on_device(dev):
+                _lib.call("vn_rpn_targets_atss", self._anchors_dev.data_ptr(), N, gt_d.data_ptr(), cnt_d.data_ptr(), B, G,
+                          ATSS_IOU_KINDS[self.atss_iou], self.atss_top_k, float(self.cfg["h"]), pos.data_ptr(), neg.data_ptr(),
+                          tgt.data_ptr(), matched.data_ptr() if return_matched else None,
+                          stats.data_ptr() if return_stats else None, ws.data_ptr(), nbytes, _lib.raw_stream())
+            return (pos, neg, tgt) + ((matched,) if return_matched else ()) + ((stats,) if return_stats else ())
         nbytes = _lib.load().vn_rpn_targets_iou_workspace_bytes(B, N, G)
         if nbytes == 0:
             raise _lib.VoxelnetHipError("vn_rpn_targets_iou_workspace_bytes: unsupported sizes")
@@ -190,15 +217,19 @@ class TargetGenerator:
                       tgt.data_ptr(), matched.data_ptr() if return_matched else None, ws.data_ptr(), nbytes, _lib.raw_stream())
         return (pos, neg, tgt, matched) if return_matched else (pos, neg, tgt)
 
-    def from_boxes(self, gt_boxes, return_matched=False, anchor_mask=None):
-        """gt_boxes: list of (G_i, 7) float64 lidar boxes per sample.  return_matched (assign "standup" / "rotated" only): a
-        fourth tensor (B,h,w,2) int32, every anchor's ground-truth index or -1.  anchor_mask (None: nothing new is launched): a
+    def from_boxes(self, gt_boxes, return_matched=False, anchor_mask=None, return_stats=False):
+        """gt_boxes: list of (G_i, 7) float64 lidar boxes per sample.  return_matched (assign "standup" / "rotated" / "atss"
+        only): a fourth tensor (B,h,w,2) int32, every anchor's ground-truth index or -1.  return_stats (assign "atss" only):
+        appends the (B, G, 4) float64 tensor of every box's (mean, standard deviation, threshold, number of anchors matched to
+        it), zeros for a slot without a valid box.  anchor_mask (None: nothing new is launched): a
         (B,h,w,2) uint8 device mask (anchor_mask.AnchorMasker) — after the assignment, forced positives included,
         an anchor it leaves out is ignored: pos = neg = 0; targets and matched are not touched."""
+        if return_stats and self.assign != "atss":
+            raise ValueError('return_stats needs assign="atss": the other assignments have no per-box threshold')
         if self.assign != "reference":
-            return self._apply_mask(self._from_boxes_iou(gt_boxes, return_matched), anchor_mask)
+            return self._apply_mask(self._from_boxes_iou(gt_boxes, return_matched, return_stats), anchor_mask)
         if return_matched:
-            raise ValueError('return_matched needs assign="standup" or "rotated": the reference assignment reports no index')
+            raise ValueError('return_matched needs assign="standup", "rotated" or "atss": the reference assignment reports no index')
         B = len(gt_boxes)
         G = max([b.shape[0] for b in gt_boxes] + [1])
         if G > MAX_GT:
