@@ -1315,6 +1315,51 @@ int vn_rpn_targets_atss(const double *anchors, int32_t n_anchors, const double *
                         double *stats /*[B,max_gt,4]; may be NULL*/, void *workspace, size_t workspace_bytes,
                         vnStream stream);
 
+/* ---- RPN training targets by SimOTA (csrc/targets_ota.hip) ------------------------------------------
+ * The prediction-aware dynamic-k assignment of YOLOX (Ge et al., 2021): a ground-truth box takes the anchors whose CURRENT
+ * PREDICTION fits it best, and how many it takes follows from how many predictions already overlap it.  Same anchors, gt,
+ * gt_count and output maps as vn_rpn_targets_atss; unlike its three siblings the call reads the network's outputs, so it
+ * runs after the forward.  All arithmetic is float64; every float32 input is widened exactly.
+ * Inputs: anchors [n_anchors,7], anchor n = 2 * site + a, n_anchors even, S = n_anchors / 2 sites.  gt [B,max_gt,7];
+ *   gt_count[b] (device) is clamped to [0, max_gt].  probs [B,2,S] and deltas [B,14,S] float32 in the SITE layout — the
+ *   module's NCHW outputs as they lie in memory: anchor (s, a) has p = probs[b,a,s] and d_j = deltas[b,7a+j,s], j = 0..6.
+ *   1 <= q <= VN_OTA_MAX_Q (YOLOX: 10); radius >= 0, finite, in metres; iou_weight >= 0, finite (YOLOX: 3); metric
+ *   VN_IOU_BEV or VN_IOU_3D.
+ * Validity as in vn_rpn_targets_atss: box k of sample b is valid when k < gt_count[b], all seven fields are finite and
+ *   h, w, l > 0.  For a valid box k and anchor n, dx = x_n - x_k, dy = y_n - y_k, c = cos r_k, s = sin r_k,
+ *   u = dx*c + dy*s, w' = -(dx*s) + dy*c (vn_rpn_targets_atss rules 1 and 5, the same expressions):
+ *   1. in_box(n,k): |u| <= l/2 and |w'| <= w/2, edges inside — the footprint test of vn_rpn_targets_atss rule 5.
+ *   2. in_ctr(n,k): |dx| <= radius and |dy| <= radius, edges inside; a NaN compares false.
+ *   3. Candidates: C_k = {n : in_box(n,k) or in_ctr(n,k)}.  There is no bound on |C_k|.
+ *   4. P(n) = the box d decodes to on anchor n (the decode of vn_rpn_iou_loss: x, y by the anchor's diagonal, z by its
+ *      height, sizes by exp, yaw added).  v(n,k) = the iou_bev / iou_3d of "detection scoring" below for (P(n), gt_k): 0,
+ *      never NaN, when a decoded field is not finite or a size is <= 0.
+ *   5. cost(n,k) = -log(pc) + iou_weight * (-log(v + 1e-8)) + (in_box and in_ctr ? 0 : 1e5), the three terms added left to
+ *      right; pc = min(max(p, 1e-12), 1), a NaN p counts as 1e-12.
+ *   6. m = min(q, |C_k|); sum_k = the sum of the m largest v over C_k, added in descending order (equal values in any
+ *      order: the sum is the same); dyn_k = max(1, int(floor(sum_k))), which is <= m because v <= 1.
+ *   7. Box k selects the dyn_k candidates with the smallest (cost, n), lexicographic.
+ *   8. matched[n] = the selecting box of the smallest cost(n,k), the smallest k among equals; -1 when none selected n.
+ *      An anchor lost to another box is not replaced (plain SimOTA), so a box may end with fewer than dyn_k anchors, or none.
+ *   9. pos = matched >= 0; neg = not pos.
+ *  10. targets: vn_rpn_targets_iou's encoding of gt[matched[n]] on anchor n, float64 rounded to float32; zeros for a
+ *      non-positive.
+ *  11. stats [B,max_gt,5] float64, or NULL: (|C_k|, sum_k, dyn_k, the cost of the last selected candidate, the number of
+ *      anchors with matched == k); zeros for an invalid box, for k >= gt_count[b] and for a box with no candidate.
+ * Limits as vn_rpn_targets_atss.  VN_EINVAL, before anything is launched, for a size outside the limits, an odd n_anchors,
+ * q outside its range, a NaN, negative or infinite radius or iou_weight, an unknown metric, a null pointer (matched and
+ * stats excepted) or anchor_h == 0; VN_EWORKSPACE for a workspace below the query's answer (0 for unsupported sizes).
+ * Asynchronous on `stream`, no host synchronisation; no floating-point atomics, integer atomics of order-independent
+ * results only: outputs are bit-identical from run to run. */
+#define VN_OTA_MAX_Q 16
+size_t vn_rpn_targets_ota_workspace_bytes(int32_t B, int32_t n_anchors, int32_t max_gt, int32_t q);
+int vn_rpn_targets_ota(const double *anchors, int32_t n_anchors, const double *gt /*[B,max_gt,7]*/,
+                       const int32_t *gt_count /*device [B]*/, int32_t B, int32_t max_gt, const float *probs /*[B,2,S]*/,
+                       const float *deltas /*[B,14,S]*/, int32_t metric, int32_t q, double radius, double iou_weight,
+                       double anchor_h, float *pos, float *neg, float *targets, int32_t *matched /*may be NULL*/,
+                       double *stats /*[B,max_gt,5]; may be NULL*/, void *workspace, size_t workspace_bytes,
+                       vnStream stream);
+
 /* ---- inference tail (voxelnet/model.py:364-395 RPN3D.predict: utils.deltas_to_boxes_3d utils.py:476-489,
  * filter_boxes model.py:28-57, utils.nms utils.py:492-553) ----------------------------------------------
  * probs (B,2,h,w) and deltas (B,14,h,w): the module's fp32 NCHW outputs, read as the flat (B, n_anchors) and

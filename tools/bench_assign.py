@@ -1,4 +1,4 @@
-"""Time the four target assigners and the two detection layouts (DESIGN.md sections 1h, 1o), alternated inside one process.
+"""Time the five target assigners and the two detection layouts (DESIGN.md sections 1h, 1o, 1p), alternated inside one process.
 
 1. Assignment on the full Car grid (70,400 anchors), B = 2, with 8 and with 128 boxes per frame: us per call (every launch
    of the call: vn_rpn_targets' three, vn_rpn_targets_iou's memset + three, vn_rpn_targets_atss' memset + three) for
@@ -6,6 +6,10 @@
      standup     vn_rpn_targets_iou, VN_ASSIGN_STANDUP
      rotated     vn_rpn_targets_iou, VN_ASSIGN_ROTATED
      atss        vn_rpn_targets_atss, VN_ASSIGN_ROTATED, top_k = --atss-top-k (9), no stats; its ratio to `rotated` is printed
+     simota      vn_rpn_targets_ota, VN_IOU_BEV, q = --ota-q (10), radius 2.5 site pitches, iou_weight 3, no stats, on seeded
+                 maps (probs uniform, deltas N(0, 0.3): what a box's candidates predict does not change how many they are);
+                 its ratios to `rotated` and `atss` are printed.  Unlike the others it runs AFTER the forward, on the step's
+                 dependency chain — hence part 3
    and, from the same run, the encoder's forward (RPN3D.feature_net on the benchmark's two Car frames, bf16 mode) — the
    assigner runs on the targets stream beside it, off the step's dependency chain.
 2. The evaluation tail at predict.EVAL_DECODE (pre-NMS 1024, rotated NMS at 0.1, cap 20) on random full-grid maps, B = 2:
@@ -13,10 +17,14 @@
      site            vn_rpn_detect_layout, VN_DETECT_SITE
      flat + 2 transposes   the two channels-last copies (torch permute + contiguous), then vn_rpn_detect: what the site
                            layout replaces
+3. (--train-step) RPN3D.train_step on the benchmark's two Car frames with 6 labelled cars each, bf16 mode, ClipSGD: target_assign
+   "simota" against "atss", both on the separate-calls path (forward, backward, step: what "simota" takes; "atss" is driven
+   through the same three calls instead of its one-call step), two models alternated round by round, ms per step.
 Method of tools/bench_loss.py: per arm and round --round-launches calls back to back between two device events, the arms
 alternated round by round; reported: median [min, max] over the rounds.  No threshold is set on these numbers.
---assign-only leaves out the encoder and the evaluation tail.
-usage: python tools/bench_assign.py [--rounds 20] [--round-launches 50] [--atss-top-k 9] [--assign-only] [--out FILE]"""
+--assign-only leaves out the encoder and the evaluation tail (not part 3).
+usage: python tools/bench_assign.py [--rounds 20] [--round-launches 50] [--atss-top-k 9] [--ota-q 10] [--assign-only] [--train-step]
+       [--out FILE]"""
 import argparse
 import os
 import statistics
@@ -46,7 +54,11 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--rounds", type=int, default=20)
 ap.add_argument("--round-launches", type=int, default=50)
 ap.add_argument("--atss-top-k", type=int, default=9)
+ap.add_argument("--ota-q", type=int, default=10)
 ap.add_argument("--assign-only", action="store_true")
+ap.add_argument("--train-step", action="store_true")
+ap.add_argument("--step-rounds", type=int, default=10)
+ap.add_argument("--round-steps", type=int, default=10)
 ap.add_argument("--out")
 args = ap.parse_args()
 if not torch.cuda.is_available():
@@ -59,6 +71,10 @@ B = 2
 cfg = T.CLASS_CFG["Car"]
 anchors = torch.from_numpy(np.ascontiguousarray(T.generate_anchors("Car").reshape(-1, 7))).to(dev)
 N = anchors.shape[0]
+ota_rng = np.random.default_rng(3)
+ota_probs = torch.from_numpy(ota_rng.random((B, 2, 200, 176)).astype(np.float32)).to(dev)
+ota_deltas = torch.from_numpy((ota_rng.standard_normal((B, 14, 200, 176)) * 0.3).astype(np.float32)).to(dev)
+ota_radius = T.OTA_RADIUS_PITCHES * T.site_pitch(T.generate_anchors("Car"))
 
 
 def boxes_of(n, seed):
@@ -89,6 +105,12 @@ def assigner(kind, G):
         a = (anchors.data_ptr(), N, gt.data_ptr(), cnt.data_ptr(), B, G, _lib.VN_ASSIGN_ROTATED, args.atss_top_k, cfg["h"],
              pos.data_ptr(), neg.data_ptr(), tgt.data_ptr(), None, None, ws.data_ptr(), nb, st)
         name = "vn_rpn_targets_atss"
+    elif kind == "simota":
+        nb = lib.vn_rpn_targets_ota_workspace_bytes(B, N, G, args.ota_q)
+        ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+        a = (anchors.data_ptr(), N, gt.data_ptr(), cnt.data_ptr(), B, G, ota_probs.data_ptr(), ota_deltas.data_ptr(), _lib.VN_IOU_BEV,
+             args.ota_q, ota_radius, 3.0, cfg["h"], pos.data_ptr(), neg.data_ptr(), tgt.data_ptr(), None, None, ws.data_ptr(), nb, st)
+        name = "vn_rpn_targets_ota"
     else:
         nb = lib.vn_rpn_targets_iou_workspace_bytes(B, N, G)
         ws = torch.empty(nb, dtype=torch.uint8, device=dev)
@@ -101,7 +123,7 @@ def assigner(kind, G):
 
 arms = []
 for G in (8, 128):
-    for kind in ("reference", "standup", "rotated", "atss"):
+    for kind in ("reference", "standup", "rotated", "atss", "simota"):
         run, keep = assigner(kind, G)
         arms.append((f"assign {kind}", f"{G} boxes", run, keep))
 
@@ -177,6 +199,56 @@ for a, b, *_ in arms:
 for G in (8, 128):
     r, t = statistics.median(us[("assign rotated", f"{G} boxes")]), statistics.median(us[("assign atss", f"{G} boxes")])
     say(f"atss (top_k {args.atss_top_k}) / rotated at {G} boxes: {t:.2f} / {r:.2f} = {t / r:.2f}")
+    o = statistics.median(us[("assign simota", f"{G} boxes")])
+    say(f"simota (q {args.ota_q}) / rotated at {G} boxes: {o:.2f} / {r:.2f} = {o / r:.2f};  / atss: {o:.2f} / {t:.2f} = {o / t:.2f}")
+
+if args.train_step:
+    from voxelnet_amd.optim import ClipSGD
+    M.set_precision("bf16")
+    grid = grid_config("Car")
+    sf, sc = [], []
+    for b, cloud in enumerate(synth.workload_frames(1, batch=B)):
+        f, c, _ = voxelize_device(torch.from_numpy(cloud).to(dev), grid, b, coord_cols=4)
+        sf.append(f)
+        sc.append(c)
+    labels = np.empty(B, dtype=object)
+    for b in range(B):
+        labels[b] = synth.synth_labels("Car", 6, seed=7000 + b)
+    batch = (None, labels, sf, None, sc, None, None)
+    steppers = {}
+    for kind in ("atss", "simota"):
+        torch.manual_seed(0)
+        m = M.RPN3D("Car", target_assign=kind).to(dev).train()
+        opt = ClipSGD(list(m.parameters()), 1e-3, 5.0)
+
+        def step(m=m, opt=opt):          # RPN3D.train_step's separate-calls branch, for both kinds
+            out = m(batch, dev)
+            out[2].backward()
+            opt.step()
+            for p in m.parameters():
+                p.grad = None
+        steppers[kind] = step
+    for step in steppers.values():
+        for _ in range(5):
+            step()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in steppers}
+    for _ in range(args.step_rounds):
+        for kind, step in steppers.items():
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            s.record()
+            for _ in range(args.round_steps):
+                step()
+            e.record()
+            torch.cuda.synchronize()
+            ms[kind].append(s.elapsed_time(e) / args.round_steps)
+    say(f"== RPN3D.train_step, separate calls, Car, B = {B}, 6 cars per frame, bf16: {args.step_rounds} alternated rounds of "
+        f"{args.round_steps} steps; ms per step, median [min, max] ==")
+    for kind, v in ms.items():
+        say(f"target_assign {kind:8s} {statistics.median(v):9.3f} [{min(v):8.3f}, {max(v):8.3f}]")
+    a_, o_ = statistics.median(ms["atss"]), statistics.median(ms["simota"])
+    say(f"simota / atss: {o_:.3f} / {a_:.3f} = {o_ / a_:.3f}")
 if args.out:
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     open(args.out, "w").write("\n".join(lines) + "\n")

@@ -24,6 +24,7 @@
 //                (one lane per chunk), one lane per candidate evaluates v, thread 0 adds the <= 64 values in candidate
 //                order, and an accepted candidate enters the dense per-anchor word by an integer atomicMax on v's float64
 //                bits (a non-negative double orders as its bits) and is recorded, bits and all, in the workspace.
+//   (k_as_arg, k_as_count, k_as_encode, the wave arg-min and the footprint test: rpn_common.h, shared with targets_ota.hip)
 //   k_as_arg     reads the RECORDED bits (nothing is evaluated twice): where they equal the anchor's maximum, an atomicMax
 //                on ~k leaves the smallest k.
 //   k_as_count   stats[..., 3]: a box counts its own recorded candidates that it won — no atomics.
@@ -40,22 +41,7 @@ constexpr int AS_THREADS = 128;                  // k_as_scan, k_as_pick: two wa
 constexpr int AS_K = VN_ATSS_MAX_TOPK;
 constexpr int AS_CAND = 2 * AS_K;                // candidates of a box, at most: one wave
 constexpr int AS_UNROLL = 8;                     // sites a lane loads before it looks at any of them
-constexpr int AS_MAX_CHUNKS = VN_WAVE;           // k_as_pick: one lane per chunk
-constexpr int AS_MIN_CHUNK = 64;                 // sites of a chunk, at least (but for the last)
-constexpr int AS_TARGET_WGS = 1024;              // k_as_scan: workgroups wanted (256 CUs x 3 resident, and a tail)
-constexpr int AS_ENC_THREADS = 256;
-constexpr int AS_NONE = 0x7fffffff;              // the index of a list's padding: behind every anchor at d2 = +inf
 static_assert(AS_CAND == VN_WAVE, "one lane per candidate");
-
-// One round of a wave's lexicographic arg-min: every lane leaves with the smallest (d, n) of the 64.
-__device__ __forceinline__ void as_wave_min(double &d, int &n) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const double od = __shfl_xor(d, o, VN_WAVE);
-        const int on = __shfl_xor(n, o, VN_WAVE);
-        if (od < d || (od == d && on < n)) { d = od; n = on; }
-    }
-}
 
 // part_d / part_n [B, max_gt, chunks, 2, AS_K]: the K best (d2, n) of group a inside chunk c, ascending
 __global__ void __launch_bounds__(AS_THREADS) k_as_scan(const double *__restrict__ anchors, int N, const double *__restrict__ gt,
@@ -207,9 +193,7 @@ __global__ void __launch_bounds__(AS_THREADS) k_as_pick(const double *__restrict
     if (tid < AS_CAND) {
         unsigned long long bits = 0ull;
         if (tid < C && v > 0.0 && v >= s_stat[2]) {
-            const double dx = an[0] - q[0], dy = an[1] - q[1], cr = cos(q[6]), sr = sin(q[6]);
-            const double u = dx * cr + dy * sr, w = -(dx * sr) + dy * cr;
-            if (fabs(u) <= q[5] / 2 && fabs(w) <= q[4] / 2) bits = (unsigned long long)__double_as_longlong(v);
+            if (as_in_footprint(an[0] - q[0], an[1] - q[1], cos(q[6]), sin(q[6]), q)) bits = (unsigned long long)__double_as_longlong(v);
         }
         if (bits) atomicMax(best_bits + (size_t)b * N + n, bits);
         cand_n[kb * AS_CAND + tid] = n;
@@ -217,65 +201,10 @@ __global__ void __launch_bounds__(AS_THREADS) k_as_pick(const double *__restrict
     }
 }
 
-// an accepted candidate whose recorded bits are its anchor's maximum enters the anchor's arg word: the smallest k stays
-__global__ void __launch_bounds__(AS_CAND) k_as_arg(int N, int max_gt, const unsigned long long *__restrict__ best_bits,
-                                                    uint32_t *__restrict__ best_arg, const int32_t *__restrict__ cand_n,
-                                                    const unsigned long long *__restrict__ cand_bits) {
-    const int k = blockIdx.x, b = blockIdx.y;
-    const size_t ci = ((size_t)b * max_gt + k) * AS_CAND + threadIdx.x;
-    const unsigned long long bits = cand_bits[ci];
-    if (!bits) return;
-    const size_t o = (size_t)b * N + cand_n[ci];
-    if (best_bits[o] == bits) atomicMax(best_arg + o, ~(uint32_t)k);
-}
-
-// stats[..., 3] = the anchors matched to box k: its own accepted candidates (distinct anchors) that it won
-__global__ void __launch_bounds__(AS_CAND) k_as_count(int N, int max_gt, const unsigned long long *__restrict__ best_bits,
-                                                      const uint32_t *__restrict__ best_arg, const int32_t *__restrict__ cand_n,
-                                                      const unsigned long long *__restrict__ cand_bits, double *__restrict__ stats) {
-    const int k = blockIdx.x, b = blockIdx.y;
-    const size_t kb = (size_t)b * max_gt + k, ci = kb * AS_CAND + threadIdx.x;
-    const unsigned long long bits = cand_bits[ci];
-    bool won = false;
-    if (bits) {
-        const size_t o = (size_t)b * N + cand_n[ci];
-        won = best_bits[o] == bits && best_arg[o] == ~(uint32_t)k;
-    }
-    const unsigned long long m = __ballot(won);
-    if (threadIdx.x == 0) stats[kb * 4 + 3] = (double)__popcll(m);
-}
-
-__global__ void __launch_bounds__(AS_ENC_THREADS) k_as_encode(const double *__restrict__ anchors, int N, const double *__restrict__ gt,
-                                                              int max_gt, const unsigned long long *__restrict__ best_bits,
-                                                              const uint32_t *__restrict__ best_arg, double anchor_h,
-                                                              float *__restrict__ pos, float *__restrict__ neg,
-                                                              float *__restrict__ targets, int32_t *__restrict__ matched) {
-    const int b = blockIdx.y, n = blockIdx.x * AS_ENC_THREADS + threadIdx.x;
-    if (n >= N) return;
-    const size_t o = (size_t)b * N + n;
-    const int box = best_bits[o] ? (int)~best_arg[o] : -1;
-    pos[o] = box >= 0 ? 1.f : 0.f;
-    neg[o] = box >= 0 ? 0.f : 1.f;
-    if (matched) matched[o] = box;
-    float t[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (box >= 0)
-        vn_box_encode(gt + ((size_t)b * max_gt + box) * 7, anchors + (size_t)n * 7, anchor_h, t);
-#pragma unroll
-    for (int j = 0; j < 7; ++j) targets[o * 7 + j] = t[j];
-}
-
 // the limits of vn_rpn_targets_iou, an even anchor count, top_k in its range
 inline bool as_args_ok(int32_t B, int32_t N, int32_t max_gt, int32_t top_k) {
-    return B > 0 && N > 0 && N % 2 == 0 && max_gt > 0 && max_gt <= VN_TARGETS_MAX_GT && (int64_t)B * N < (1ll << 31) / 8 &&
-           top_k >= 1 && top_k <= VN_ATSS_MAX_TOPK;
+    return as_sizes_ok(B, N, max_gt) && top_k >= 1 && top_k <= VN_ATSS_MAX_TOPK;
 }
-// ranges the sites are cut into: AS_TARGET_WGS workgroups of k_as_scan over the B * max_gt boxes, chunks of >= AS_MIN_CHUNK sites
-inline int as_chunks(int32_t B, int32_t N, int32_t max_gt) {
-    const int64_t want = AS_TARGET_WGS / ((int64_t)B * max_gt), fit = (N / 2 + AS_MIN_CHUNK - 1) / AS_MIN_CHUNK;
-    return (int)std::max<int64_t>(1, std::min<int64_t>(std::min(want, fit), AS_MAX_CHUNKS));
-}
-inline size_t as_bits_bytes(int32_t B, int32_t N) { return vn_align((size_t)B * N * sizeof(unsigned long long)); }
-inline size_t as_arg_bytes(int32_t B, int32_t N) { return vn_align((size_t)B * N * sizeof(uint32_t)); }
 inline size_t as_cand_n_bytes(int32_t B, int32_t max_gt) { return vn_align((size_t)B * max_gt * AS_CAND * sizeof(int32_t)); }
 inline size_t as_cand_bits_bytes(int32_t B, int32_t max_gt) { return vn_align((size_t)B * max_gt * AS_CAND * sizeof(unsigned long long)); }
 inline size_t as_part_d_bytes(int32_t B, int32_t max_gt, int chunks) { return vn_align((size_t)B * max_gt * chunks * AS_CAND * sizeof(double)); }
@@ -321,14 +250,14 @@ extern "C" int vn_rpn_targets_atss(const double *anchors, int32_t n_anchors, con
         k_as_pick<VN_ASSIGN_ROTATED><<<boxes, AS_THREADS, 0, st>>>(anchors, n_anchors, gt, gt_count, max_gt, top_k, chunks, part_d, part_n,
                                                                    best_bits, cand_n, cand_bits, stats);
     VN_LAUNCH_STATUS();
-    k_as_arg<<<boxes, AS_CAND, 0, st>>>(n_anchors, max_gt, best_bits, best_arg, cand_n, cand_bits);
+    k_as_arg<AS_CAND><<<boxes, AS_CAND, 0, st>>>(n_anchors, max_gt, best_bits, best_arg, cand_n, cand_bits);
     VN_LAUNCH_STATUS();
     if (stats) {
-        k_as_count<<<boxes, AS_CAND, 0, st>>>(n_anchors, max_gt, best_bits, best_arg, cand_n, cand_bits, stats);
+        k_as_count<AS_CAND><<<boxes, AS_CAND, 0, st>>>(n_anchors, max_gt, best_bits, best_arg, cand_n, cand_bits, stats, 4, 3);
         VN_LAUNCH_STATUS();
     }
     const dim3 grid((unsigned)((n_anchors + AS_ENC_THREADS - 1) / AS_ENC_THREADS), (unsigned)B);
-    k_as_encode<<<grid, AS_ENC_THREADS, 0, st>>>(anchors, n_anchors, gt, max_gt, best_bits, best_arg, anchor_h, pos, neg, targets,
+    k_as_encode<AS_ENC_THREADS><<<grid, AS_ENC_THREADS, 0, st>>>(anchors, n_anchors, gt, max_gt, best_bits, best_arg, anchor_h, pos, neg, targets,
                                                  matched);
     VN_LAUNCH_STATUS();
     return VN_OK;

@@ -337,6 +337,9 @@ SIGNATURES = {
     "vn_rpn_targets_atss_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32, c_i32]),
     "vn_rpn_targets_atss": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, ctypes.c_double, c_vp, c_vp, c_vp, c_vp,
                                     c_vp, c_vp, c_sz, c_vp]),
+    "vn_rpn_targets_ota_workspace_bytes": (c_sz, [c_i32, c_i32, c_i32, c_i32]),
+    "vn_rpn_targets_ota": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, ctypes.c_double, ctypes.c_double,
+                                   ctypes.c_double, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "vn_rpn_predict_workspace_bytes": (c_sz, [c_i32, c_i32]),
     "vn_rpn_predict": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_f32, ctypes.c_double, c_i32, ctypes.c_double, c_vp, c_vp, c_vp,
                                c_vp, c_sz, c_vp]),

@@ -1061,8 +1061,10 @@ class RPN3D(nn.Module):
     last_iou = None          # the latest (L_iou, mean_iou) pair: detached device scalars, no synchronisation
     # how anchors are assigned to ground truths (targets.TargetGenerator(assign=)): "reference" keeps the
     # reference's assignment, "standup" / "rotated" assign by a real IoU, "atss" by every box's own threshold over its
-    # atss_top_k nearest anchors per rotation, IoU of kind atss_iou
+    # atss_top_k nearest anchors per rotation, IoU of kind atss_iou; "simota"  by the network's
+    # own predictions — the targets are then generated AFTER detect(), from its detached maps, on the step's dependency chain
     target_assign, atss_top_k, atss_iou = "reference", 9, "rotated"
+    ota_q, ota_radius, ota_iou_weight, ota_metric = 10, None, 3.0, "bev"
     # the direction-classifier head (voxelnet_amd/dir_head.py): False = nothing is registered or launched
     dir_head, dir_weight, dir_offset = False, 0.2, math.pi / 4
     last_dir = None          # the latest (L_dir, acc) pair: detached device scalars, no synchronisation
@@ -1079,9 +1081,10 @@ class RPN3D(nn.Module):
     def __init__(self, cls_name="Car", alpha=ALPHA, beta=BETA, sigma=SIGMA, *, cls_loss="bce", focal_alpha=0.25, focal_gamma=2.0,
                  yaw_loss="diff", iou_loss=None, iou_weight=1.0, iou_metric="3d", target_assign="reference", dir_head=False,
                  dir_weight=0.2, dir_offset=math.pi / 4, anchor_area_threshold=None, iou_head=False, iou_head_weight=1.0,
-                 iou_head_metric="3d", iou_rectify=0.5, atss_top_k=9, atss_iou="rotated"):
+                 iou_head_metric="3d", iou_rectify=0.5, atss_top_k=9, atss_iou="rotated", ota_q=10, ota_radius=None,
+                 ota_iou_weight=3.0, ota_metric="bev"):
         super().__init__()
-        from .targets import ASSIGN_KINDS, ATSS_IOU_KINDS, ATSS_MAX_TOPK
+        from .targets import ASSIGN_KINDS, ATSS_IOU_KINDS, ATSS_MAX_TOPK, check_ota_params
         if target_assign not in ASSIGN_KINDS:
             raise ValueError(f"target_assign must be one of {sorted(ASSIGN_KINDS)}, not {target_assign!r}")
         if isinstance(atss_top_k, bool) or not isinstance(atss_top_k, int) or not 1 <= atss_top_k <= ATSS_MAX_TOPK:
@@ -1089,6 +1092,8 @@ class RPN3D(nn.Module):
         if atss_iou not in ATSS_IOU_KINDS:
             raise ValueError(f"atss_iou must be one of {sorted(ATSS_IOU_KINDS)}, not {atss_iou!r}")
         self.target_assign, self.atss_top_k, self.atss_iou = target_assign, atss_top_k, atss_iou
+        check_ota_params(ota_q, ota_radius, ota_iou_weight, ota_metric)
+        self.ota_q, self.ota_radius, self.ota_iou_weight, self.ota_metric = ota_q, ota_radius, ota_iou_weight, ota_metric
         if anchor_area_threshold is not None:
             from .anchor_mask import check_threshold
             self.anchor_area_threshold = check_threshold(anchor_area_threshold)
@@ -1186,10 +1191,12 @@ class RPN3D(nn.Module):
         from .targets import TargetGenerator
         gen = self.__dict__.get("_targets")
         if (gen is None or gen.device != torch.device(device) or gen.assign != self.target_assign
-                or gen.keep_heading != bool(self.dir_head) or gen.atss_top_k != self.atss_top_k or gen.atss_iou != self.atss_iou):
+                or gen.keep_heading != bool(self.dir_head) or gen.atss_top_k != self.atss_top_k or gen.atss_iou != self.atss_iou
+                or gen.ota_params != (self.ota_q, self.ota_radius, self.ota_iou_weight, self.ota_metric)):
             # (with the direction head the labels keep their heading: its target is the bin of the box's yaw)
             gen = TargetGenerator(self.cls_name, device, assign=self.target_assign, keep_heading=bool(self.dir_head),
-                                  atss_top_k=self.atss_top_k, atss_iou=self.atss_iou)
+                                  atss_top_k=self.atss_top_k, atss_iou=self.atss_iou, ota_q=self.ota_q, ota_radius=self.ota_radius,
+                                  ota_iou_weight=self.ota_iou_weight, ota_metric=self.ota_metric)
             # the maps the network EMITS, not rpn_output_shape: for Pedestrian / Cyclist that attribute repeats the anchor
             # grid (100 x 120, as the reference has it) while block 1 does not stride and the maps are 200 x 240
             g, s = grid_config(self.cls_name), self.middle_rpn._block1_stride
@@ -1643,10 +1650,14 @@ class RPN3D(nn.Module):
             self.__dict__["_step_sc"] = sc
         return sc
 
-    def _step_fused_ok(self, mode, optimizer):
+    def _step_fused_ok(self, mode, optimizer, targets=None):
+        """whether train_step may take the one library call.  Under target_assign "simota" the module's own targets need the
+        forward's maps, which vn_net_step does not hand out between its forward and its loss: only a step that
+        is handed its targets can."""
         from .optim import ClipAdamW, ClipSGD
         red = self.grad_reducer
-        return (self._native_ok(mode) and self.training and self.direct_grads and self.overlap_wgrad and self.sparse_first_layer
+        return (self._native_ok(mode) and (self.target_assign != "simota" or targets is not None)
+                and self.training and self.direct_grads and self.overlap_wgrad and self.sparse_first_layer
                 and torch.is_grad_enabled() and self.target_fn is None and E.SECTIONS is None and self.iou_loss is None
                 and not (int(self.grad_storage) & 16)
                 and (red is None or (red.comm_stream is not None and HEADS_W in _grad_views(self)))
@@ -1665,13 +1676,14 @@ class RPN3D(nn.Module):
         Whatever the fused call does not cover — per-layer orchestration, eval mode, target_fn, gradient accumulation, a
         reducer without a communication stream, bench.py's per-section timer, the rotated-IoU term (iou_loss set: it is
         not part of vnStep), the direction head (dir_head=True: it runs on the per-layer orchestration, outside
-        the native executor), the IoU-aware head (iou_head=True, likewise) — takes the separate
-        calls, same results."""
+        the native executor), the IoU-aware head (iou_head=True, likewise), the SimOTA assignment
+        without targets= (target_assign="simota": its targets come from the forward's own maps) — takes the
+        separate calls, same results."""
         from .optim import ClipSGD
         mode = _mode()
         spec = self._loss_spec()            # (checked before anything is launched)
         self._iou_spec()
-        fused = self._step_fused_ok(mode, optimizer)
+        fused = self._step_fused_ok(mode, optimizer, targets)
         plist = self._flat_params() if fused else None
         if fused and (not self._all_need_grad(plist) or any(p.grad is not None for p in plist)):
             fused = False            # (frozen parameters / accumulation into existing .grad: autograd's business)
@@ -1828,8 +1840,10 @@ class RPN3D(nn.Module):
         # model.py:309 generates the targets AFTER the network ran; they depend on the labels only, so here their three small
         # launches (and the host-side box parsing) are issued first, on a stream of their own, and run beside the VFE /
         # first layers; the loss waits for them (529 -> 545 point-clouds/s with the targets generated inside the step)
+        # (target_assign "simota" reads the maps detect() is about to produce: nothing to launch early)
         early = None
-        if targets is None and self.target_fn is None and label is not None and voxel_features and voxel_features[0].is_cuda:
+        if (targets is None and self.target_fn is None and label is not None and voxel_features and voxel_features[0].is_cuda
+                and self.target_assign != "simota"):
             dev_ = voxel_features[0].device
             ts = self.__dict__.get("_tgt_stream")
             if ts is None or ts.device != dev_:
@@ -1856,7 +1870,8 @@ class RPN3D(nn.Module):
                 raise _lib.VoxelnetHipError("RPN3D.forward needs the batch's labels (x[1]), targets=(pos,neg,targets) or a "
                                             "target_fn")
             else:
-                targets = self._target_generator(prob_out.device)(label)
+                maps = dict(probs=prob_out.detach(), deltas=delta_out.detach()) if self.target_assign == "simota" else {}
+                targets = self._target_generator(prob_out.device)(label, **maps)
                 if self.anchor_area_threshold is not None:
                     targets = self._mask_targets(targets, voxel_coordinates, None)
         loss, cls_loss, reg_loss, cpos, cneg = self.loss(prob_out, delta_out, *targets)

@@ -11,7 +11,9 @@ There is no CPU fallback: the HIP library must be present.
 `TargetGenerator(assign=)`: "reference" is that assignment, quirks included; "standup" and "rotated" assign by a real IoU
 (csrc/targets_iou.hip, `vn_rpn_targets_iou`) — what a model that is to be evaluated has to be
 trained with.  "atss" (csrc/targets_atss.hip, `vn_rpn_targets_atss`) drops the two fixed
-thresholds: every box takes the `atss_top_k` nearest anchors of each rotation and sets its own threshold from their IoUs."""
+thresholds: every box takes the `atss_top_k` nearest anchors of each rotation and sets its own threshold from their IoUs.
+"simota" (csrc/targets_ota.hip, `vn_rpn_targets_ota`) is prediction-aware: it reads the network's
+`probs` / `deltas` maps, and a box takes the anchors whose decoded prediction fits it best, as many as overlap it already."""
 import ctypes
 import os
 
@@ -21,10 +23,15 @@ import torch
 from . import _lib
 
 MAX_GT = 128     # VN_TARGETS_MAX_GT (include/voxelnet_hip.h)
-# assign -> vn_rpn_targets_iou's iou_kind (None: not that call — "reference" is vn_rpn_targets, "atss" vn_rpn_targets_atss)
-ASSIGN_KINDS = {"reference": None, "standup": _lib.VN_ASSIGN_STANDUP, "rotated": _lib.VN_ASSIGN_ROTATED, "atss": None}
+# assign -> vn_rpn_targets_iou's iou_kind (None: not that call — "reference" is vn_rpn_targets, "atss" vn_rpn_targets_atss,
+# "simota" vn_rpn_targets_ota)
+ASSIGN_KINDS = {"reference": None, "standup": _lib.VN_ASSIGN_STANDUP, "rotated": _lib.VN_ASSIGN_ROTATED, "atss": None,
+                "simota": None}
 ATSS_IOU_KINDS = {"standup": _lib.VN_ASSIGN_STANDUP, "rotated": _lib.VN_ASSIGN_ROTATED}
 ATSS_MAX_TOPK = 32     # VN_ATSS_MAX_TOPK
+OTA_METRICS = {"bev": _lib.VN_IOU_BEV, "3d": _lib.VN_IOU_3D}
+OTA_MAX_Q = 16         # VN_OTA_MAX_Q
+OTA_RADIUS_PITCHES = 2.5          # ota_radius=None: this many site pitches (YOLOX's centre radius, there in strides)
 
 # voxelnet/config.py:36-92 (anchor geometry, IoU thresholds) and :99-111 (mean KITTI calibration)
 CLASS_CFG = {
@@ -124,6 +131,48 @@ def gt_standup_boxes(gt):
 _LABEL_CACHE = os.environ.get("VN_LABEL_CACHE", "1") != "0"
 
 
+def check_ota_params(ota_q, ota_radius, ota_iou_weight, ota_metric):
+    """ValueError for a SimOTA parameter outside vn_rpn_targets_ota's ranges (ota_radius None: derived from the anchors)"""
+    if isinstance(ota_q, bool) or not isinstance(ota_q, (int, np.integer)) or not 1 <= ota_q <= OTA_MAX_Q:
+        raise ValueError(f"ota_q must be an int in 1..{OTA_MAX_Q}, not {ota_q!r}")
+    for name, v in (("ota_radius", ota_radius), ("ota_iou_weight", ota_iou_weight)):
+        if v is None and name == "ota_radius":
+            continue
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not (0 <= v < float("inf")):
+            raise ValueError(f"{name} must be a finite number >= 0, not {v!r}")
+    if ota_metric not in OTA_METRICS:
+        raise ValueError(f"ota_metric must be one of {sorted(OTA_METRICS)}, not {ota_metric!r}")
+
+
+def site_pitch(anchors):
+    """the anchor grid's site pitch in metres, read from an (h, w, 2, 7) anchor array: the larger of the mean column pitch
+    (x) and the mean row pitch (y); ValueError for a grid of one site, which has none"""
+    a = np.asarray(anchors, dtype=np.float64)
+    h, w = a.shape[:2]
+    pitches = ([abs(a[0, -1, 0, 0] - a[0, 0, 0, 0]) / (w - 1)] if w > 1 else []) + \
+              ([abs(a[-1, 0, 0, 1] - a[0, 0, 0, 1]) / (h - 1)] if h > 1 else [])
+    if not pitches or not np.isfinite(max(pitches)):
+        raise ValueError("ota_radius=None needs an anchor grid of more than one site to read the pitch from: pass ota_radius")
+    return float(max(pitches))
+
+
+def check_maps(assign, probs, deltas, B, shape):
+    """the rule of from_boxes' probs= / deltas=: both there, float32 and (B, 2, h, w) / (B, 14, h, w) under "simota"; neither
+    under any other kind.  ValueError otherwise."""
+    if assign != "simota":
+        if probs is not None or deltas is not None:
+            raise ValueError(f'probs= / deltas= belong to assign="simota": assign={assign!r} does not look at predictions')
+        return
+    if probs is None or deltas is None:
+        raise ValueError('assign="simota" needs the prediction maps: probs=(B,2,h,w) and deltas=(B,14,h,w)')
+    want = ((B, 2, *shape), (B, 14, *shape))
+    for name, t, w in (("probs", probs, want[0]), ("deltas", deltas, want[1])):
+        if not torch.is_tensor(t) or t.dtype != torch.float32:
+            raise ValueError(f"{name} must be a float32 tensor, not {type(t).__name__ if not torch.is_tensor(t) else t.dtype}")
+        if tuple(t.shape) != w:
+            raise ValueError(f"{name} {tuple(t.shape)} is not the generator's grid: {w} expected")
+
+
 class TargetGenerator:
     """Device-resident anchors of one class + the launch: `gen(labels)` -> (pos_equal_one (B,h,w,2), neg_equal_one
     (B,h,w,2), targets (B,h,w,14)) float32 tensors on `device`, the arrays of utils.generate_targets (utils.py:473).
@@ -134,10 +183,17 @@ class TargetGenerator:
     assign "atss" (vn_rpn_targets_atss): per box the atss_top_k (1..32) nearest anchors of each rotation
     are its candidates, its threshold is the mean + standard deviation of their IoUs (atss_iou: "rotated" or "standup"), and a
     candidate at or above it whose centre lies inside the box is positive; every other anchor is negative.  pos_iou / neg_iou
-    are accepted and IGNORED for "atss"; atss_top_k / atss_iou are checked always and used by "atss" only."""
+    are accepted and IGNORED for "atss"; atss_top_k / atss_iou are checked always and used by "atss" only.
+    assign "simota" (vn_rpn_targets_ota): needs from_boxes(..., probs=, deltas=), the module's fp32 NCHW
+    outputs.  Per box the candidates are the anchors inside its footprint or within ota_radius metres of its centre along x
+    and y (None: 2.5 site pitches of the anchor grid); it takes dyn_k = max(1, floor(sum of its ota_q largest IoUs between
+    decoded prediction and box)) of them by the smallest cost -log p + ota_iou_weight * -log IoU (+1e5 outside footprint and
+    radius both); an anchor two boxes select goes to the smaller cost.  ota_metric: "bev" or "3d".  pos_iou / neg_iou are
+    ignored; the ota_* are checked always and used by "simota" only."""
 
     def __init__(self, cls_name="Car", device="cuda:0", anchors=None, assign="reference", pos_iou=None, neg_iou=None,
-                 keep_heading=False, atss_top_k=9, atss_iou="rotated"):
+                 keep_heading=False, atss_top_k=9, atss_iou="rotated", ota_q=10, ota_radius=None, ota_iou_weight=3.0,
+                 ota_metric="bev"):
         if assign not in ASSIGN_KINDS:
             raise ValueError(f"assign must be one of {sorted(ASSIGN_KINDS)}, not {assign!r}")
         if isinstance(atss_top_k, bool) or not isinstance(atss_top_k, (int, np.integer)) or not 1 <= atss_top_k <= ATSS_MAX_TOPK:
@@ -145,6 +201,10 @@ class TargetGenerator:
         if atss_iou not in ATSS_IOU_KINDS:
             raise ValueError(f"atss_iou must be one of {sorted(ATSS_IOU_KINDS)}, not {atss_iou!r}")
         self.atss_top_k, self.atss_iou = int(atss_top_k), atss_iou
+        check_ota_params(ota_q, ota_radius, ota_iou_weight, ota_metric)
+        self.ota_q, self.ota_iou_weight, self.ota_metric = int(ota_q), float(ota_iou_weight), ota_metric
+        self.ota_radius = None if ota_radius is None else float(ota_radius)
+        self.ota_params = (ota_q, ota_radius, ota_iou_weight, ota_metric)          # as given: what RPN3D compares its own with
         self.cls_name = cls_name
         self.cfg = CLASS_CFG[cls_name]
         self.assign = assign
@@ -158,6 +218,8 @@ class TargetGenerator:
             raise _lib.VoxelnetHipError("TargetGenerator needs a HIP device (no CPU path)")
         self.anchors = generate_anchors(cls_name) if anchors is None else np.asarray(anchors, dtype=np.float64)
         self.shape = self.anchors.shape[:2]
+        if assign == "simota" and self.ota_radius is None:
+            self.ota_radius = OTA_RADIUS_PITCHES * site_pitch(self.anchors)
         self._anchors_dev = torch.from_numpy(np.ascontiguousarray(self.anchors.reshape(-1, 7))).to(self.device)
         self.n_anchors = self._anchors_dev.shape[0]
         self._parsed = {}          # (label lines, coordinate) -> (G, 7) float64 boxes
@@ -176,10 +238,11 @@ class TargetGenerator:
         N = self.n_anchors
         return (mask_probs(pos, anchor_mask, N, _lib.VN_DETECT_FLAT), mask_probs(neg, anchor_mask, N, _lib.VN_DETECT_FLAT)) + tuple(out[2:])
 
-    def _from_boxes_iou(self, gt_boxes, return_matched, return_stats=False):
-        """assign = "standup" / "rotated" / "atss": everything per box happens on the device too (no stand-up rectangles here)"""
-        atss = self.assign == "atss"
-        name = "vn_rpn_targets_atss" if atss else "vn_rpn_targets_iou"
+    def _from_boxes_iou(self, gt_boxes, return_matched, return_stats=False, probs=None, deltas=None):
+        """assign = "standup" / "rotated" / "atss" / "simota": everything per box happens on the device too (no stand-up
+        rectangles here)"""
+        atss, ota = self.assign == "atss", self.assign == "simota"
+        name = "vn_rpn_targets_atss" if atss else "vn_rpn_targets_ota" if ota else "vn_rpn_targets_iou"
         B = len(gt_boxes)
         G = max([b.shape[0] for b in gt_boxes] + [1])
         if G > MAX_GT:
@@ -195,6 +258,22 @@ class TargetGenerator:
         neg = torch.empty((B, *self.shape, 2), dtype=torch.float32, device=dev)
         tgt = torch.empty((B, *self.shape, 14), dtype=torch.float32, device=dev)
         matched = torch.empty((B, *self.shape, 2), dtype=torch.int32, device=dev) if return_matched else None
+        if ota:
+            if probs.device != dev or deltas.device != dev:
+                raise ValueError(f"probs / deltas must live on the generator's device {dev}")
+            probs, deltas = probs.contiguous(), deltas.contiguous()
+            stats = torch.empty((B, G, 5), dtype=torch.float64, device=dev) if return_stats else None
+            nbytes = _lib.load().vn_rpn_targets_ota_workspace_bytes(B, N, G, self.ota_q)
+            if nbytes == 0:
+                raise _lib.VoxelnetHipError("vn_rpn_targets_ota_workspace_bytes: unsupported sizes")
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            with _lib.on_device(dev):
+                _lib.call("vn_rpn_targets_ota", self._anchors_dev.data_ptr(), N, gt_d.data_ptr(), cnt_d.data_ptr(), B, G,
+                          probs.data_ptr(), deltas.data_ptr(), OTA_METRICS[self.ota_metric], self.ota_q, self.ota_radius,
+                          self.ota_iou_weight, float(self.cfg["h"]), pos.data_ptr(), neg.data_ptr(), tgt.data_ptr(),
+                          matched.data_ptr() if return_matched else None, stats.data_ptr() if return_stats else None,
+                          ws.data_ptr(), nbytes, _lib.raw_stream())
+            return (pos, neg, tgt) + ((matched,) if return_matched else ()) + ((stats,) if return_stats else ())
         if atss:
             stats = torch.empty((B, G, 4), dtype=torch.float64, device=dev) if return_stats else None
             nbytes = _lib.load().vn_rpn_targets_atss_workspace_bytes(B, N, G, self.atss_top_k)
@@ -217,19 +296,23 @@ class TargetGenerator:
                       tgt.data_ptr(), matched.data_ptr() if return_matched else None, ws.data_ptr(), nbytes, _lib.raw_stream())
         return (pos, neg, tgt, matched) if return_matched else (pos, neg, tgt)
 
-    def from_boxes(self, gt_boxes, return_matched=False, anchor_mask=None, return_stats=False):
-        """gt_boxes: list of (G_i, 7) float64 lidar boxes per sample.  return_matched (assign "standup" / "rotated" / "atss"
-        only): a fourth tensor (B,h,w,2) int32, every anchor's ground-truth index or -1.  return_stats (assign "atss" only):
+    def from_boxes(self, gt_boxes, return_matched=False, anchor_mask=None, return_stats=False, probs=None, deltas=None):
+        """gt_boxes: list of (G_i, 7) float64 lidar boxes per sample.  return_matched (every assign but "reference"): a fourth
+        tensor (B,h,w,2) int32, every anchor's ground-truth index or -1.  return_stats (assign "atss" / "simota" only):
         appends the (B, G, 4) float64 tensor of every box's (mean, standard deviation, threshold, number of anchors matched to
-        it), zeros for a slot without a valid box.  anchor_mask (None: nothing new is launched): a
+        it) — under "simota" the (B, G, 5) tensor of (candidates, sum of the top IoUs, dyn_k, cost of the last selected
+        candidate, anchors matched to it) —, zeros for a slot without a valid box.  probs / deltas (assign "simota" only, and
+        required there): the module's (B,2,h,w) / (B,14,h,w) float32 outputs on the device, read on the current stream;
+        ValueError when they are missing, given under another kind, or not the generator's grid.  anchor_mask (None: nothing new is launched): a
         (B,h,w,2) uint8 device mask (anchor_mask.AnchorMasker) — after the assignment, forced positives included,
         an anchor it leaves out is ignored: pos = neg = 0; targets and matched are not touched."""
-        if return_stats and self.assign != "atss":
-            raise ValueError('return_stats needs assign="atss": the other assignments have no per-box threshold')
+        if return_stats and self.assign not in ("atss", "simota"):
+            raise ValueError('return_stats needs assign="atss" or "simota": the other assignments have no per-box statistics')
+        check_maps(self.assign, probs, deltas, len(gt_boxes), self.shape)
         if self.assign != "reference":
-            return self._apply_mask(self._from_boxes_iou(gt_boxes, return_matched, return_stats), anchor_mask)
+            return self._apply_mask(self._from_boxes_iou(gt_boxes, return_matched, return_stats, probs, deltas), anchor_mask)
         if return_matched:
-            raise ValueError('return_matched needs assign="standup", "rotated" or "atss": the reference assignment reports no index')
+            raise ValueError('return_matched needs assign="standup", "rotated", "atss" or "simota": the reference assignment reports no index')
         B = len(gt_boxes)
         G = max([b.shape[0] for b in gt_boxes] + [1])
         if G > MAX_GT:
@@ -269,7 +352,7 @@ class TargetGenerator:
                       _lib.raw_stream())
         return self._apply_mask((pos, neg, tgt), anchor_mask)
 
-    def __call__(self, labels, feature_map_shape=None, coordinate="lidar", anchor_mask=None):
+    def __call__(self, labels, feature_map_shape=None, coordinate="lidar", anchor_mask=None, probs=None, deltas=None):
         if feature_map_shape is not None and tuple(feature_map_shape) != tuple(self.shape):
             raise ValueError(f"feature map {tuple(feature_map_shape)} does not match the anchors {tuple(self.shape)}")
         # label lines -> lidar boxes is a pure function of the TEXT of a sample's label: remembered per sample (an epoch
@@ -286,7 +369,7 @@ class TargetGenerator:
                 hit.setflags(write=False)
                 self._parsed[key] = hit
             boxes.append(hit)
-        return self.from_boxes(boxes, anchor_mask=anchor_mask)
+        return self.from_boxes(boxes, anchor_mask=anchor_mask, probs=probs, deltas=deltas)
 
 
 def generate_targets(labels, feature_map_shape, anchors, cls_name="Car", coordinate="lidar", device="cuda:0"):
