@@ -99,8 +99,8 @@ def test_every_tuning_knob_is_listed_and_the_environment_is_read_in_one_place():
 
 
 def test_build_id_names_the_sources_the_library_was_built_from():
-    """vn_build_id() = first 12 hex digits of the SHA-256 over csrc/*.hip (sorted), every csrc/*.h (sorted: common.h,
-    rpn_common.h — an edit to any header changes the id) and the public header — the identity profiles/*_pmc_traffic.json
+    """vn_build_id() = first 12 hex digits of the SHA-256 over csrc/*.hip (sorted), every csrc/*.h (sorted: assign_common.h,
+    common.h, rpn_common.h — an edit to any header changes the id) and the public header — the identity profiles/*_pmc_traffic.json
     carries and bench.py compares before it reports `roofline.traffic`.  (Round 5: a phony make prerequisite once left the
     id ONE BUILD BEHIND the sources; it is now computed when the Makefile is read.)"""
     import glob
@@ -111,7 +111,7 @@ def test_build_id_names_the_sources_the_library_was_built_from():
     csrc = os.path.join(ROOT, "voxelnet-pytorch_amd", "csrc")
     h = hashlib.sha256()
     headers = sorted(glob.glob(os.path.join(csrc, "*.h")))
-    assert [os.path.basename(f) for f in headers][:2] == ["common.h", "rpn_common.h"]
+    assert [os.path.basename(f) for f in headers][:3] == ["assign_common.h", "common.h", "rpn_common.h"]
     for f in sorted(glob.glob(os.path.join(csrc, "*.hip"))) + headers + [os.path.join(ROOT, "include", "voxelnet_hip.h")]:
         h.update(open(f, "rb").read())
     lib = _lib.load()

@@ -1,6 +1,8 @@
-// Shared by the RPN tail — iou_loss.hip, dir_head.hip, iou_head.hip, predict.hip, detect.hip, targets.hip, targets_iou.hip, targets_atss.hip, targets_ota.hip — and by nothing
-// else: the ONE copy of the anchor box codec and of the scaffold of a loss term summed over the (B, h, w) anchor sites
-// (DESIGN.md 1j).  common.h goes into every translation unit; the two kernels here do not belong in the convolution files.
+// Shared by the RPN tail — iou_loss.hip, dir_head.hip, iou_head.hip, predict.hip, detect.hip and, through assign_common.h, the
+// four targets*.hip — and by nothing else: the ONE copy of the anchor box codec, of the rows of the concatenation as the 1x1
+// heads read them, and of the scaffold of a loss term summed over the (B, h, w) anchor sites.  What only the
+// target assigners share is in assign_common.h.  common.h goes into every translation unit; the two kernels here do not
+// belong in the convolution files.
 #pragma once
 #include "common.h"
 
@@ -66,124 +68,6 @@ __device__ __forceinline__ void vn_box_encode(const double *g, const double *a, 
     t[5] = (float)log(g[5] / a[5]);
     t[6] = (float)(g[6] - a[6]);
 }
-
-// ---- the stand-up IoU of the target assignments (targets_iou.hip, targets_atss.hip) ----
-// the axis-aligned hull of the rotated footprint of (x, y, ., ., w, l, r) as (x, y, half width hx, half height hy, area)
-__device__ __forceinline__ void ti_hull(const double (&q)[7], double (&h)[5]) {
-    const double c = fabs(cos(q[6])), s = fabs(sin(q[6]));
-    h[0] = q[0]; h[1] = q[1];
-    h[2] = (q[5] * c + q[4] * s) / 2;
-    h[3] = (q[5] * s + q[4] * c) / 2;
-    h[4] = (2.0 * h[2]) * (2.0 * h[3]);
-}
-
-// The overlap of [xa - ha, xa + ha] and [xg - hg, xg + hg] written from the centres: min(ha + hg - |xg - xa|, 2 min(ha, hg)).
-// Where one interval contains the other the second term is taken, which does not depend on the position: the anchors of a
-// row that all contain a box's hull along x (or lie inside it) get THE SAME IoU bit for bit, not values that differ by the
-// rounding of x +- ha, and the smallest index wins the tie in every implementation that writes the overlap this way.
-__device__ __forceinline__ double ti_standup_iou(const double (&a)[5], const double *__restrict__ g) {
-    const double iw = fmin((a[2] + g[2]) - fabs(g[0] - a[0]), 2.0 * fmin(a[2], g[2]));
-    const double ih = fmin((a[3] + g[3]) - fabs(g[1] - a[1]), 2.0 * fmin(a[3], g[3]));
-    if (!(iw > 0.0) || !(ih > 0.0)) return 0.0;
-    const double inter = iw * ih;
-    const double v = inter / ((a[4] + g[4]) - inter);
-    return v > 0.0 ? v : 0.0;          // (a NaN from infinite extents is 0)
-}
-
-// ---- the per-box assignments (targets_atss.hip, targets_ota.hip): bounded per-lane lists merged by wave
-// arg-min rounds, an integer-atomic arg-best over the boxes' recorded candidates, one encode ----
-constexpr int AS_MAX_CHUNKS = VN_WAVE;           // the per-box merge: one lane per chunk
-constexpr int AS_MIN_CHUNK = 64;                 // sites of a chunk, at least (but for the last)
-constexpr int AS_TARGET_WGS = 1024;              // the scan: workgroups wanted (256 CUs x 3 resident, and a tail)
-constexpr int AS_ENC_THREADS = 256;
-constexpr int AS_NONE = 0x7fffffff;              // the index of a list's padding: behind every anchor at +inf
-
-// One round of a wave's lexicographic arg-min: every lane leaves with the smallest (d, n) of the 64.
-__device__ __forceinline__ void as_wave_min(double &d, int &n) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const double od = __shfl_xor(d, o, VN_WAVE);
-        const int on = __shfl_xor(n, o, VN_WAVE);
-        if (od < d || (od == d && on < n)) { d = od; n = on; }
-    }
-}
-
-// whether an anchor's centre, (dx, dy) from box q's, lies inside q's bird's-eye footprint, edges inside: u along the box's
-// length l, w' along its width w; cr, sr = cos, sin of q's yaw
-__device__ __forceinline__ bool as_in_footprint(double dx, double dy, double cr, double sr, const double (&q)[7]) {
-    const double u = dx * cr + dy * sr, w = -(dx * sr) + dy * cr;
-    return fabs(u) <= q[5] / 2 && fabs(w) <= q[4] / 2;
-}
-
-// A box's recorded candidates: SLOTS of (anchor n, bits), bits == 0 for an empty slot, else the value the box offered the
-// anchor's best word by atomicMax.  Where the recorded bits equal the anchor's maximum — nothing is evaluated twice — an
-// atomicMax on ~k leaves the smallest k.  (Templates, as k_pos_norm below: only the files that launch them instantiate them.)
-template <int SLOTS>
-__global__ void __launch_bounds__(SLOTS) k_as_arg(int N, int max_gt, const unsigned long long *__restrict__ best_bits,
-                                                  uint32_t *__restrict__ best_arg, const int32_t *__restrict__ cand_n,
-                                                  const unsigned long long *__restrict__ cand_bits) {
-    static_assert(SLOTS <= VN_WAVE, "one wave per box");
-    const int k = blockIdx.x, b = blockIdx.y;
-    const size_t ci = ((size_t)b * max_gt + k) * SLOTS + threadIdx.x;
-    const unsigned long long bits = cand_bits[ci];
-    if (!bits) return;
-    const size_t o = (size_t)b * N + cand_n[ci];
-    if (best_bits[o] == bits) atomicMax(best_arg + o, ~(uint32_t)k);
-}
-
-// stats[(b * max_gt + k) * stride + col] = the anchors matched to box k: its own recorded candidates (distinct anchors) that it
-// won — no atomics
-template <int SLOTS>
-__global__ void __launch_bounds__(SLOTS) k_as_count(int N, int max_gt, const unsigned long long *__restrict__ best_bits,
-                                                    const uint32_t *__restrict__ best_arg, const int32_t *__restrict__ cand_n,
-                                                    const unsigned long long *__restrict__ cand_bits, double *__restrict__ stats,
-                                                    int stride, int col) {
-    static_assert(SLOTS <= VN_WAVE, "one wave per box");
-    const int k = blockIdx.x, b = blockIdx.y;
-    const size_t kb = (size_t)b * max_gt + k, ci = kb * SLOTS + threadIdx.x;
-    const unsigned long long bits = cand_bits[ci];
-    bool won = false;
-    if (bits) {
-        const size_t o = (size_t)b * N + cand_n[ci];
-        won = best_bits[o] == bits && best_arg[o] == ~(uint32_t)k;
-    }
-    const unsigned long long m = __ballot(won);
-    if (threadIdx.x == 0) stats[kb * stride + col] = (double)__popcll(m);
-}
-
-// matched, pos, neg and the seven regression targets of every anchor from its best word and its arg word
-template <int THREADS>
-__global__ void __launch_bounds__(THREADS) k_as_encode(const double *__restrict__ anchors, int N, const double *__restrict__ gt,
-                                                       int max_gt, const unsigned long long *__restrict__ best_bits,
-                                                       const uint32_t *__restrict__ best_arg, double anchor_h,
-                                                       float *__restrict__ pos, float *__restrict__ neg,
-                                                       float *__restrict__ targets, int32_t *__restrict__ matched) {
-    const int b = blockIdx.y, n = blockIdx.x * THREADS + threadIdx.x;
-    if (n >= N) return;
-    const size_t o = (size_t)b * N + n;
-    const int box = best_bits[o] ? (int)~best_arg[o] : -1;
-    pos[o] = box >= 0 ? 1.f : 0.f;
-    neg[o] = box >= 0 ? 0.f : 1.f;
-    if (matched) matched[o] = box;
-    float t[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (box >= 0)
-        vn_box_encode(gt + ((size_t)b * max_gt + box) * 7, anchors + (size_t)n * 7, anchor_h, t);
-#pragma unroll
-    for (int j = 0; j < 7; ++j) targets[o * 7 + j] = t[j];
-}
-
-// the limits of vn_rpn_targets_iou and an even anchor count
-inline bool as_sizes_ok(int32_t B, int32_t N, int32_t max_gt) {
-    return B > 0 && N > 0 && N % 2 == 0 && max_gt > 0 && max_gt <= VN_TARGETS_MAX_GT && (int64_t)B * N < (1ll << 31) / 8;
-}
-// ranges the sites are cut into: AS_TARGET_WGS workgroups of the scan over the B * max_gt boxes, chunks of >= AS_MIN_CHUNK sites
-inline int as_chunks(int32_t B, int32_t N, int32_t max_gt) {
-    const int64_t want = AS_TARGET_WGS / ((int64_t)B * max_gt), fit = (N / 2 + AS_MIN_CHUNK - 1) / AS_MIN_CHUNK;
-    return (int)std::max<int64_t>(1, std::min<int64_t>(std::min(want, fit), AS_MAX_CHUNKS));
-}
-// the two dense per-anchor words, adjacent in the workspace so that one memset clears both
-inline size_t as_bits_bytes(int32_t B, int32_t N) { return vn_align((size_t)B * N * sizeof(unsigned long long)); }
-inline size_t as_arg_bytes(int32_t B, int32_t N) { return vn_align((size_t)B * N * sizeof(uint32_t)); }
 
 // stand-up rectangle (x1, y1, x2, y2) of a float32 box (utils.py:230-252, 283-330): float64 rotation, float32 corners
 __device__ __forceinline__ void vn_box_standup_f32(const float (&o)[7], float (&r)[4]) {

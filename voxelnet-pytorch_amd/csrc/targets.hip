@@ -15,7 +15,7 @@
 // Three launches: per-workgroup argmax partials (value, first index) -> per-box argmax (fixed order) -> per-anchor
 // classification and encoding (the IoUs are recomputed: G*12 flops per anchor, cheaper than storing them).
 // HBM-bound and tiny: 56 B read + 36 B written per anchor.
-#include "rpn_common.h"
+#include "assign_common.h"
 
 namespace {
 
@@ -136,27 +136,29 @@ __global__ void __launch_bounds__(TG_THREADS) k_tg_encode(const double *__restri
     if (box < 0)
         for (int k = 0; k < G; ++k)
             if (gmax[k] == n) { box = k; break; }
-    const size_t o = (size_t)b * N + n;
-    pos[o] = box >= 0 ? 1.f : 0.f;
-    neg[o] = all_neg ? 1.f : 0.f;
-    float t[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (box >= 0)
-        vn_box_encode(gt + ((size_t)b * max_gt + box) * 7, a, anchor_h, t);
-#pragma unroll
-    for (int j = 0; j < 7; ++j) targets[o * 7 + j] = t[j];
+    as_write_targets((size_t)b * N + n, box, all_neg, gt + (size_t)b * max_gt * 7, a, anchor_h, pos, neg, targets, nullptr);
 }
 
-inline bool tg_args_ok(int32_t B, int32_t N, int32_t max_gt) {
-    return B > 0 && N > 0 && max_gt > 0 && max_gt <= TG_MAX_GT && (int64_t)B * N < (1ll << 31) / 8;
-}
 inline int tg_blocks(int32_t N) { return (N + TG_THREADS - 1) / TG_THREADS; }
+
+// workspace: [the workgroups' argmax values | their indices | the boxes' first best anchor]
+struct TgWs : AsLayout {
+    int nblk;
+    AsRegion<float> part_val;
+    AsRegion<int32_t> part_idx, idmax;
+    TgWs(int32_t B, int32_t N, int32_t max_gt) : nblk(tg_blocks(N)) {
+        const size_t part = (size_t)B * nblk * max_gt;
+        part_val = add<float>(part);
+        part_idx = add<int32_t>(part);
+        idmax = add<int32_t>((size_t)B * max_gt);
+    }
+};
 
 }  // namespace
 
 extern "C" size_t vn_rpn_targets_workspace_bytes(int32_t B, int32_t n_anchors, int32_t max_gt) {
-    if (!tg_args_ok(B, n_anchors, max_gt)) return 0;
-    const size_t part = (size_t)B * tg_blocks(n_anchors) * max_gt;
-    return vn_align(part * sizeof(float)) + vn_align(part * sizeof(int32_t)) + vn_align((size_t)B * max_gt * sizeof(int32_t));
+    if (!tg_sizes_ok(B, n_anchors, max_gt)) return 0;
+    return TgWs(B, n_anchors, max_gt).bytes();
 }
 
 extern "C" int vn_rpn_targets(const double *anchors, int32_t n_anchors, const double *gt, const float *gt_standup,
@@ -164,15 +166,13 @@ extern "C" int vn_rpn_targets(const double *anchors, int32_t n_anchors, const do
                               double anchor_h, float *pos, float *neg, float *targets, void *workspace,
                               size_t workspace_bytes, vnStream stream) {
     VN_CHECK_ARG(anchors && gt && gt_standup && gt_count && pos && neg && targets && workspace &&
-                 tg_args_ok(B, n_anchors, max_gt) && anchor_h != 0.0);
-    if (workspace_bytes < vn_rpn_targets_workspace_bytes(B, n_anchors, max_gt)) return VN_EWORKSPACE;
+                 tg_sizes_ok(B, n_anchors, max_gt) && anchor_h != 0.0);
+    const TgWs ws(B, n_anchors, max_gt);
+    if (workspace_bytes < ws.bytes()) return VN_EWORKSPACE;
     hipStream_t st = vn_stream(stream);
-    const int nblk = tg_blocks(n_anchors);
-    const size_t part = (size_t)B * nblk * max_gt;
-    char *ws = static_cast<char *>(workspace);
-    float *part_val = reinterpret_cast<float *>(ws);
-    int32_t *part_idx = reinterpret_cast<int32_t *>(ws + vn_align(part * sizeof(float)));
-    int32_t *idmax = reinterpret_cast<int32_t *>(ws + vn_align(part * sizeof(float)) + vn_align(part * sizeof(int32_t)));
+    const int nblk = ws.nblk;
+    float *part_val = ws.part_val(workspace);
+    int32_t *part_idx = ws.part_idx(workspace), *idmax = ws.idmax(workspace);
     const dim3 grid((unsigned)nblk, (unsigned)B);
     k_tg_argmax_part<<<grid, TG_THREADS, 0, st>>>(anchors, n_anchors, gt_standup, gt_count, max_gt, part_val, part_idx);
     VN_LAUNCH_STATUS();

@@ -6,7 +6,7 @@
 // anchors with (n & 1) == a.  For a valid box k (common.h box_ok) of sample b:
 //   d2(n,k) = dx*dx + dy*dy, dx = x_n - x_k, dy = y_n - y_k;
 //   C_k     = per group the min(top_k, n_anchors / 2) anchors with the smallest (d2, n), lexicographic;
-//   v(n,k)  = the IoU vn_rpn_targets_iou computes for the pair (rpn_common.h ti_standup_iou / common.h box_iou_pair);
+//   v(n,k)  = the IoU vn_rpn_targets_iou computes for the pair (assign_common.h ti_pair_iou: ti_standup_iou / common.h box_iou_pair);
 //   mu, sd  = mean and unbiased standard deviation of v over C_k, summed in candidate order (group 0 by rank, then
 //             group 1 by rank);  t = mu + sd;
 //   accepted: v >= t, v > 0, and the anchor's centre inside the box's footprint (|u| <= l/2 along the box's length axis,
@@ -24,7 +24,7 @@
 //                (one lane per chunk), one lane per candidate evaluates v, thread 0 adds the <= 64 values in candidate
 //                order, and an accepted candidate enters the dense per-anchor word by an integer atomicMax on v's float64
 //                bits (a non-negative double orders as its bits) and is recorded, bits and all, in the workspace.
-//   (k_as_arg, k_as_count, k_as_encode, the wave arg-min and the footprint test: rpn_common.h, shared with targets_ota.hip)
+//   (k_as_arg, k_as_count, k_as_encode, the lists, the wave arg-min and the footprint test: assign_common.h, shared with targets_ota.hip)
 //   k_as_arg     reads the RECORDED bits (nothing is evaluated twice): where they equal the anchor's maximum, an atomicMax
 //                on ~k leaves the smallest k.
 //   k_as_count   stats[..., 3]: a box counts its own recorded candidates that it won — no atomics.
@@ -33,7 +33,7 @@
 // LDS: k_as_scan 128 lanes x 32 entries x (8 + 4) B = 48 KB of lists, k_as_pick 2 x 64 chunks x 32 x (8 + 4) B = 48 KB + 1.3 KB:
 // one workgroup's static allocation, three workgroups fit the CU's 160 KB.  Only the 2 * top_k candidates of a box reach the
 // pair function.
-#include "rpn_common.h"
+#include "assign_common.h"
 
 namespace {
 
@@ -60,8 +60,7 @@ __global__ void __launch_bounds__(AS_THREADS) k_as_scan(const double *__restrict
     const int a = tid >> 6, lane = tid & 63;
     const int per = (S + chunks - 1) / chunks, s_lo = ch * per, s_hi = min(S, s_lo + per);
 
-    // ---- scan: this lane's K best (d2, n) of group a, ascending.  n grows along the scan, so an anchor whose d2 EQUALS an
-    // entry's ranks behind it: strict compares keep the (d2, n) order exact.
+    // ---- scan: this lane's K best (d2, n) of group a, ascending (as_list_insert: n grows along the scan)
     int c = 0;
     double worst = INFINITY;          // the K-th entry once the list is full
     for (int s0 = s_lo + lane; s0 < s_hi; s0 += VN_WAVE * AS_UNROLL) {
@@ -79,18 +78,7 @@ __global__ void __launch_bounds__(AS_THREADS) k_as_scan(const double *__restrict
             const double dx = x[u] - q[0], dy = y[u] - q[1];
             double d = dx * dx + dy * dy;
             if (!(d == d)) d = INFINITY;          // an anchor without a position ranks last
-            if (s < s_hi && (c < K || d < worst)) {
-                int j = min(c, K - 1);
-                while (j > 0 && l_d[j - 1][tid] > d) {
-                    l_d[j][tid] = l_d[j - 1][tid];
-                    l_n[j][tid] = l_n[j - 1][tid];
-                    --j;
-                }
-                l_d[j][tid] = d;
-                l_n[j][tid] = s * 2 + a;
-                c = min(c + 1, K);
-                if (c == K) worst = l_d[K - 1][tid];
-            }
+            if (s < s_hi) as_list_insert(l_d, tid, K, c, worst, d, l_n, s * 2 + a);
         }
     }
 
@@ -98,14 +86,8 @@ __global__ void __launch_bounds__(AS_THREADS) k_as_scan(const double *__restrict
     const size_t po = ((kb * chunks + ch) * 2 + a) * AS_K;
     int head = 0;
     for (int r = 0; r < K; ++r) {
-        const bool have = head < c;
-        const double hd = have ? l_d[min(head, AS_K - 1)][tid] : INFINITY;
-        const int hn = have ? l_n[min(head, AS_K - 1)][tid] : AS_NONE;
-        double d = hd;
-        int n = hn;
-        as_wave_min(d, n);
-        if (have && hn == n) ++head;          // anchor indices are unique: exactly one lane advances
-        if (lane == 0) { part_d[po + r] = d; part_n[po + r] = n; }
+        const AsHead m = as_merge_round(l_d, tid, lane, true, c, head, l_n);
+        if (lane == 0) { part_d[po + r] = m.key; part_n[po + r] = m.id; }
     }
 }
 
@@ -142,14 +124,8 @@ __global__ void __launch_bounds__(AS_THREADS) k_as_pick(const double *__restrict
     }
     int head = 0;
     for (int r = 0; r < K; ++r) {
-        const bool have = lane < chunks && head < K;
-        const double hd = have ? p_d[a][min(head, AS_K - 1)][lane] : INFINITY;
-        const int hn = have ? p_n[a][min(head, AS_K - 1)][lane] : AS_NONE;
-        double d = hd;
-        int n = hn;
-        as_wave_min(d, n);
-        if (have && hn == n) ++head;
-        if (lane == 0) s_cand[a][r] = n;
+        const AsHead m = as_merge_round(p_d[a], lane, lane, lane < chunks, K, head, p_n[a]);
+        if (lane == 0) s_cand[a][r] = m.id;
     }
     __syncthreads();
 
@@ -161,21 +137,10 @@ __global__ void __launch_bounds__(AS_THREADS) k_as_pick(const double *__restrict
         n = s_cand[tid / K][tid % K];
 #pragma unroll
         for (int j = 0; j < 7; ++j) an[j] = anchors[(size_t)n * 7 + j];
-        if (KIND == VN_ASSIGN_STANDUP) {
-            double ah[5], gh[5];
-            ti_hull(an, ah);
-            ti_hull(q, gh);
-            v = ti_standup_iou(ah, gh);
-        } else if (box_ok(an)) {
-            const double hd_a = 0.5 * sqrt(an[4] * an[4] + an[5] * an[5]) * 1.000001;
-            const double hd = 0.5 * sqrt(q[4] * q[4] + q[5] * q[5]) * 1.000001;
-            const double dx = q[0] - an[0], dy = q[1] - an[1], r = hd + hd_a;
-            if (!(dx * dx + dy * dy > r * r)) {          // (disjoint footprints: exactly 0, k_ti_pairs' reject)
-                double v3;
-                box_iou_pair(an, q, v, v3);
-            }
-        }
-        if (!(v > 0.0)) v = 0.0;
+        double ah[5], gh[5];
+        ti_pair_side<KIND>(an, ah);
+        ti_pair_side<KIND>(q, gh);
+        if (!ti_pair_iou<KIND>(an, ah, q, gh, v)) v = 0.0;
         s_v[tid] = v;
     }
     __syncthreads();
@@ -205,20 +170,24 @@ __global__ void __launch_bounds__(AS_THREADS) k_as_pick(const double *__restrict
 inline bool as_args_ok(int32_t B, int32_t N, int32_t max_gt, int32_t top_k) {
     return as_sizes_ok(B, N, max_gt) && top_k >= 1 && top_k <= VN_ATSS_MAX_TOPK;
 }
-inline size_t as_cand_n_bytes(int32_t B, int32_t max_gt) { return vn_align((size_t)B * max_gt * AS_CAND * sizeof(int32_t)); }
-inline size_t as_cand_bits_bytes(int32_t B, int32_t max_gt) { return vn_align((size_t)B * max_gt * AS_CAND * sizeof(unsigned long long)); }
-inline size_t as_part_d_bytes(int32_t B, int32_t max_gt, int chunks) { return vn_align((size_t)B * max_gt * chunks * AS_CAND * sizeof(double)); }
-inline size_t as_part_n_bytes(int32_t B, int32_t max_gt, int chunks) { return vn_align((size_t)B * max_gt * chunks * AS_CAND * sizeof(int32_t)); }
-
-}  // namespace
 
 // workspace: [v bits of every anchor | ~k of every anchor | candidates' n | candidates' bits | chunk lists' d2 | chunk lists' n];
 // the first two are adjacent so that one memset clears both.  top_k does not enter: a box records AS_CAND slots whatever it is.
+struct AtssWs : AsBoxWs {
+    int chunks;
+    AsRegion<double> part_d;
+    AsRegion<int32_t> part_n;
+    AtssWs(int32_t B, int32_t N, int32_t max_gt) : AsBoxWs(B, N, max_gt, AS_CAND), chunks(as_chunks(B, N, max_gt)) {
+        part_d = add<double>((size_t)B * max_gt * chunks * AS_CAND);
+        part_n = add<int32_t>((size_t)B * max_gt * chunks * AS_CAND);
+    }
+};
+
+}  // namespace
+
 extern "C" size_t vn_rpn_targets_atss_workspace_bytes(int32_t B, int32_t n_anchors, int32_t max_gt, int32_t top_k) {
     if (!as_args_ok(B, n_anchors, max_gt, top_k)) return 0;
-    const int chunks = as_chunks(B, n_anchors, max_gt);
-    return as_bits_bytes(B, n_anchors) + as_arg_bytes(B, n_anchors) + as_cand_n_bytes(B, max_gt) + as_cand_bits_bytes(B, max_gt) +
-           as_part_d_bytes(B, max_gt, chunks) + as_part_n_bytes(B, max_gt, chunks);
+    return AtssWs(B, n_anchors, max_gt).bytes();
 }
 
 extern "C" int vn_rpn_targets_atss(const double *anchors, int32_t n_anchors, const double *gt, const int32_t *gt_count, int32_t B,
@@ -228,17 +197,14 @@ extern "C" int vn_rpn_targets_atss(const double *anchors, int32_t n_anchors, con
     VN_CHECK_ARG(anchors && gt && gt_count && pos && neg && targets && workspace && as_args_ok(B, n_anchors, max_gt, top_k) &&
                  anchor_h != 0.0);
     VN_CHECK_ARG(iou_kind == VN_ASSIGN_STANDUP || iou_kind == VN_ASSIGN_ROTATED);
-    if (workspace_bytes < vn_rpn_targets_atss_workspace_bytes(B, n_anchors, max_gt, top_k)) return VN_EWORKSPACE;
+    const AtssWs ws(B, n_anchors, max_gt);
+    if (workspace_bytes < ws.bytes()) return VN_EWORKSPACE;
     hipStream_t st = vn_stream(stream);
-    const int chunks = as_chunks(B, n_anchors, max_gt);
-    char *p = static_cast<char *>(workspace);
-    unsigned long long *best_bits = reinterpret_cast<unsigned long long *>(p);   p += as_bits_bytes(B, n_anchors);
-    uint32_t *best_arg = reinterpret_cast<uint32_t *>(p);                        p += as_arg_bytes(B, n_anchors);
-    int32_t *cand_n = reinterpret_cast<int32_t *>(p);                            p += as_cand_n_bytes(B, max_gt);
-    unsigned long long *cand_bits = reinterpret_cast<unsigned long long *>(p);   p += as_cand_bits_bytes(B, max_gt);
-    double *part_d = reinterpret_cast<double *>(p);                              p += as_part_d_bytes(B, max_gt, chunks);
-    int32_t *part_n = reinterpret_cast<int32_t *>(p);
-    VN_HIP(hipMemsetAsync(best_bits, 0, as_bits_bytes(B, n_anchors) + as_arg_bytes(B, n_anchors), st));
+    const int chunks = ws.chunks;
+    unsigned long long *best_bits = ws.best_bits(workspace), *cand_bits = ws.cand_bits(workspace);
+    int32_t *cand_n = ws.cand_n(workspace), *part_n = ws.part_n(workspace);
+    double *part_d = ws.part_d(workspace);
+    VN_HIP(hipMemsetAsync(best_bits, 0, ws.dense_bytes, st));
     const dim3 boxes((unsigned)max_gt, (unsigned)B);
     k_as_scan<<<dim3((unsigned)(max_gt * chunks), (unsigned)B), AS_THREADS, 0, st>>>(anchors, n_anchors, gt, gt_count, max_gt, top_k,
                                                                                      chunks, part_d, part_n);
@@ -250,15 +216,5 @@ extern "C" int vn_rpn_targets_atss(const double *anchors, int32_t n_anchors, con
         k_as_pick<VN_ASSIGN_ROTATED><<<boxes, AS_THREADS, 0, st>>>(anchors, n_anchors, gt, gt_count, max_gt, top_k, chunks, part_d, part_n,
                                                                    best_bits, cand_n, cand_bits, stats);
     VN_LAUNCH_STATUS();
-    k_as_arg<AS_CAND><<<boxes, AS_CAND, 0, st>>>(n_anchors, max_gt, best_bits, best_arg, cand_n, cand_bits);
-    VN_LAUNCH_STATUS();
-    if (stats) {
-        k_as_count<AS_CAND><<<boxes, AS_CAND, 0, st>>>(n_anchors, max_gt, best_bits, best_arg, cand_n, cand_bits, stats, 4, 3);
-        VN_LAUNCH_STATUS();
-    }
-    const dim3 grid((unsigned)((n_anchors + AS_ENC_THREADS - 1) / AS_ENC_THREADS), (unsigned)B);
-    k_as_encode<AS_ENC_THREADS><<<grid, AS_ENC_THREADS, 0, st>>>(anchors, n_anchors, gt, max_gt, best_bits, best_arg, anchor_h, pos, neg, targets,
-                                                 matched);
-    VN_LAUNCH_STATUS();
-    return VN_OK;
+    return as_launch_tail<AS_CAND>(ws, workspace, st, anchors, n_anchors, gt, B, max_gt, anchor_h, pos, neg, targets, matched, stats, 4, 3);
 }

@@ -21,14 +21,14 @@
 //   pair function returns exactly 0 for it, and it is skipped without clipping (k_dt_nms's reject): ~1,000 of the 70,400
 //   anchors reach the float64 clipping per box.
 //   k_ti_encode         matched, pos, neg and the seven regression targets (rpn_common.h's vn_box_encode, as k_tg_encode) of every anchor.
-#include "rpn_common.h"
+#include "assign_common.h"
 
 namespace {
 
 constexpr int TI_THREADS = 256;
 constexpr int TI_MAX_GT = VN_TARGETS_MAX_GT;
 
-// (ti_hull / ti_standup_iou: rpn_common.h, shared with targets_atss.hip)
+// (ti_pair_side / ti_pair_iou: assign_common.h, shared with targets_atss.hip)
 
 template <int KIND>
 __global__ void __launch_bounds__(TI_THREADS) k_ti_pairs(const double *__restrict__ anchors, int N, const double *__restrict__ gt,
@@ -43,14 +43,10 @@ __global__ void __launch_bounds__(TI_THREADS) k_ti_pairs(const double *__restric
         double q[7];
 #pragma unroll
         for (int j = 0; j < 7; ++j) { q[j] = gt[((size_t)b * max_gt + k) * 7 + j]; sg[k][j] = q[j]; }
-        if (KIND == VN_ASSIGN_STANDUP) {
-            double h[5];
-            ti_hull(q, h);
+        double h[5];
+        ti_pair_side<KIND>(q, h);
 #pragma unroll
-            for (int j = 0; j < 5; ++j) sd[k][j] = h[j];
-        } else {
-            sd[k][0] = box_ok(q) ? 0.5 * sqrt(q[4] * q[4] + q[5] * q[5]) * 1.000001 : -1.0;
-        }
+        for (int j = 0; j < ti_side_len<KIND>(); ++j) sd[k][j] = h[j];
         unsigned long long mk = 0;
         if (phase == 1) {
             mk = box_max[(size_t)b * max_gt + k];
@@ -64,31 +60,15 @@ __global__ void __launch_bounds__(TI_THREADS) k_ti_pairs(const double *__restric
     double a[7];
 #pragma unroll
     for (int j = 0; j < 7; ++j) a[j] = anchors[(size_t)n * 7 + j];
-    double ah[5] = {0.0, 0.0, 0.0, 0.0, 0.0}, hd_a = -1.0;
-    if (KIND == VN_ASSIGN_STANDUP) {
-        ti_hull(a, ah);
-    } else {
-        hd_a = box_ok(a) ? 0.5 * sqrt(a[4] * a[4] + a[5] * a[5]) * 1.000001 : -1.0;
-    }
+    double ah[5];
+    ti_pair_side<KIND>(a, ah);
     double m = 0.0;
     int kn = 0;
 #pragma unroll 1
     for (int k = 0; k < G; ++k) {
         if (phase == 1 && smax[k] == 0) continue;
         double v = 0.0;
-        if (KIND == VN_ASSIGN_STANDUP) {
-            v = ti_standup_iou(ah, sd[k]);
-        } else {
-            const double hd = sd[k][0];
-            if (hd_a < 0.0 || hd < 0.0) continue;          // an invalid box: IoU 0
-            const double dx = sg[k][0] - a[0], dy = sg[k][1] - a[1], r = hd + hd_a;
-            if (dx * dx + dy * dy > r * r) continue;          // disjoint footprints: IoU exactly 0
-            double q[7], v3;
-#pragma unroll
-            for (int j = 0; j < 7; ++j) q[j] = sg[k][j];
-            box_iou_pair(a, q, v, v3);
-        }
-        if (!(v > 0.0)) continue;
+        if (!ti_pair_iou<KIND>(a, ah, sg[k], sd[k], v)) continue;
         const unsigned long long bits = (unsigned long long)__double_as_longlong(v);
         if (phase == 0) {
             if (v > m) { m = v; kn = k; }          // strict: the smallest k of the maximum
@@ -130,23 +110,24 @@ __global__ void __launch_bounds__(TI_THREADS) k_ti_encode(const double *__restri
                 if (garg[k] == n) { box = k; break; }
         }
     }
-    pos[o] = box >= 0 ? 1.f : 0.f;
-    neg[o] = (box < 0 && (G == 0 || m < neg_iou)) ? 1.f : 0.f;
-    if (matched) matched[o] = box;
-    float t[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (box >= 0)
-        vn_box_encode(gt + ((size_t)b * max_gt + box) * 7, anchors + (size_t)n * 7, anchor_h, t);
-#pragma unroll
-    for (int j = 0; j < 7; ++j) targets[o * 7 + j] = t[j];
+    as_write_targets(o, box, box < 0 && (G == 0 || m < neg_iou), gt + (size_t)b * max_gt * 7, anchors + (size_t)n * 7, anchor_h, pos, neg,
+                     targets, matched);
 }
 
-inline bool ti_args_ok(int32_t B, int32_t N, int32_t max_gt) {
-    return B > 0 && N > 0 && max_gt > 0 && max_gt <= TI_MAX_GT && (int64_t)B * N < (1ll << 31) / 8;
-}
-inline size_t ti_best_iou_bytes(int32_t B, int32_t N) { return vn_align((size_t)B * N * sizeof(double)); }
-inline size_t ti_best_k_bytes(int32_t B, int32_t N) { return vn_align((size_t)B * N * sizeof(int32_t)); }
-inline size_t ti_box_max_bytes(int32_t B, int32_t max_gt) { return vn_align((size_t)B * max_gt * sizeof(unsigned long long)); }
-inline size_t ti_box_arg_bytes(int32_t B, int32_t max_gt) { return vn_align((size_t)B * max_gt * sizeof(uint32_t)); }
+// workspace: [m_n | k_n | M_k bits | ~n_k]; the last two are adjacent so that one memset clears both
+struct TiWs : AsLayout {
+    AsRegion<double> best_iou;
+    AsRegion<int32_t> best_k;
+    AsRegion<unsigned long long> box_max;
+    AsRegion<uint32_t> box_arg;
+    TiWs(int32_t B, int32_t N, int32_t max_gt) {
+        best_iou = add<double>((size_t)B * N);
+        best_k = add<int32_t>((size_t)B * N);
+        box_max = add<unsigned long long>((size_t)B * max_gt);
+        box_arg = add<uint32_t>((size_t)B * max_gt);
+    }
+    size_t box_bytes() const { return total - box_max.off; }          // the memset
+};
 
 template <int KIND>
 int ti_launch_pairs(dim3 grid, hipStream_t st, const double *anchors, int N, const double *gt, const int32_t *counts, int max_gt,
@@ -160,28 +141,27 @@ int ti_launch_pairs(dim3 grid, hipStream_t st, const double *anchors, int N, con
 
 }  // namespace
 
-// workspace: [m_n | k_n | M_k bits | ~n_k]; the last two are adjacent so that one memset clears both
 extern "C" size_t vn_rpn_targets_iou_workspace_bytes(int32_t B, int32_t n_anchors, int32_t max_gt) {
-    if (!ti_args_ok(B, n_anchors, max_gt)) return 0;
-    return ti_best_iou_bytes(B, n_anchors) + ti_best_k_bytes(B, n_anchors) + ti_box_max_bytes(B, max_gt) + ti_box_arg_bytes(B, max_gt);
+    if (!tg_sizes_ok(B, n_anchors, max_gt)) return 0;
+    return TiWs(B, n_anchors, max_gt).bytes();
 }
 
 extern "C" int vn_rpn_targets_iou(const double *anchors, int32_t n_anchors, const double *gt, const int32_t *gt_count, int32_t B,
                                   int32_t max_gt, int32_t iou_kind, float pos_iou, float neg_iou, double anchor_h, float *pos,
                                   float *neg, float *targets, int32_t *matched, void *workspace, size_t workspace_bytes,
                                   vnStream stream) {
-    VN_CHECK_ARG(anchors && gt && gt_count && pos && neg && targets && workspace && ti_args_ok(B, n_anchors, max_gt) &&
+    VN_CHECK_ARG(anchors && gt && gt_count && pos && neg && targets && workspace && tg_sizes_ok(B, n_anchors, max_gt) &&
                  anchor_h != 0.0);
     VN_CHECK_ARG(iou_kind == VN_ASSIGN_STANDUP || iou_kind == VN_ASSIGN_ROTATED);
     VN_CHECK_ARG(pos_iou == pos_iou && neg_iou == neg_iou);          // a NaN threshold
-    if (workspace_bytes < vn_rpn_targets_iou_workspace_bytes(B, n_anchors, max_gt)) return VN_EWORKSPACE;
+    const TiWs ws(B, n_anchors, max_gt);
+    if (workspace_bytes < ws.bytes()) return VN_EWORKSPACE;
     hipStream_t st = vn_stream(stream);
-    char *p = static_cast<char *>(workspace);
-    double *best_iou = reinterpret_cast<double *>(p);                          p += ti_best_iou_bytes(B, n_anchors);
-    int32_t *best_k = reinterpret_cast<int32_t *>(p);                          p += ti_best_k_bytes(B, n_anchors);
-    unsigned long long *box_max = reinterpret_cast<unsigned long long *>(p);   p += ti_box_max_bytes(B, max_gt);
-    uint32_t *box_arg = reinterpret_cast<uint32_t *>(p);
-    VN_HIP(hipMemsetAsync(box_max, 0, ti_box_max_bytes(B, max_gt) + ti_box_arg_bytes(B, max_gt), st));
+    double *best_iou = ws.best_iou(workspace);
+    int32_t *best_k = ws.best_k(workspace);
+    unsigned long long *box_max = ws.box_max(workspace);
+    uint32_t *box_arg = ws.box_arg(workspace);
+    VN_HIP(hipMemsetAsync(box_max, 0, ws.box_bytes(), st));
     const dim3 grid((unsigned)((n_anchors + TI_THREADS - 1) / TI_THREADS), (unsigned)B);
     const double pd = (double)pos_iou, nd = (double)neg_iou;
     const int rc = iou_kind == VN_ASSIGN_STANDUP

@@ -5,7 +5,7 @@
 //
 // Rules (include/voxelnet_hip.h states them in full), float64 throughout.  Anchor n = site * 2 + rotation a.  For a valid box k
 // (common.h box_ok) of sample b, dx = x_n - x_k, dy = y_n - y_k:
-//   in_box   the anchor's centre inside the box's footprint (rpn_common.h as_in_footprint: ATSS rule 5);
+//   in_box   the anchor's centre inside the box's footprint (assign_common.h as_in_footprint: ATSS rule 5);
 //   in_ctr   |dx| <= radius and |dy| <= radius;          C_k = {n : in_box or in_ctr}
 //   v(n,k)   = box_iou_pair(vn_box_decode_f64(deltas of n on anchor n), gt_k), BEV or 3D
 //   cost     = -log(pc) + iou_weight * -log(v + 1e-8) + (in_box and in_ctr ? 0 : 1e5),  pc = p clamped to [1e-12, 1]
@@ -15,7 +15,7 @@
 //
 // C_k has no bound (one very large box: every anchor), so it is never materialised: both selections are bounded top-q lists.
 // Launches: one memset (the per-anchor words), k_ot_scan, k_ot_pick, k_as_arg, k_as_count (only with stats), k_as_encode.
-//   k_ot_scan    The sites are cut into `chunks` ranges (rpn_common.h as_chunks); one 64-thread workgroup per (chunk, box,
+//   k_ot_scan    The sites are cut into `chunks` ranges (assign_common.h as_chunks); one 64-thread workgroup per (chunk, box,
 //                sample), a lane on a site and both its rotations.  The geometric test is two compares per anchor; only a
 //                candidate loads its deltas and reaches the decode and the pair function.  Every lane keeps the q largest v
 //                (as -v, ascending) and the q smallest (cost, n) of its candidates as sorted lists in LDS (bounded insertion,
@@ -25,11 +25,11 @@
 //                m largest in the order they come out, wave 1 merges the cost lists; then lane r < dyn_k enters its selected
 //                anchor's dense word by an integer atomicMax on the complement of the cost's ordered bits (ot_key: the largest
 //                complement is the smallest cost) and records (n, bits) in the workspace.
-//   k_as_arg / k_as_count / k_as_encode (rpn_common.h, shared with targets_atss.hip) read the RECORDED bits: nothing is
+//   k_as_arg / k_as_count / k_as_encode (assign_common.h, shared with targets_atss.hip) read the RECORDED bits: nothing is
 //                evaluated twice, the smallest k stays.
 //   Integer atomics of an order-independent result only: outputs are bit-identical from run to run.
 // LDS: k_ot_scan 64 lanes x 16 entries x (8 + 8 + 4) B = 20 KB; k_ot_pick 64 chunks x 16 x (8 + 8 + 4) B = 20 KB + 0.3 KB.
-#include "rpn_common.h"
+#include "assign_common.h"
 
 namespace {
 
@@ -75,8 +75,7 @@ __global__ void __launch_bounds__(OT_SCAN_THREADS) k_ot_scan(const double *__res
     const int per = (S + chunks - 1) / chunks, s_lo = ch * per, s_hi = min(S, s_lo + per);
     const double cr = cos(g[6]), sr = sin(g[6]);
 
-    // ---- scan.  n grows along a lane's scan, so a candidate whose cost EQUALS an entry's ranks behind it: strict compares
-    // keep the (cost, n) order exact.  Equal v need no order: they add up to the same sum.
+    // ---- scan (as_list_insert: n grows along a lane's scan; equal v need no order, they add up to the same sum)
     int cv = 0, cc = 0, cand = 0;
     double worst_v = INFINITY, worst_c = INFINITY;          // the q-th entries once the lists are full
     for (int s0 = s_lo + lane; s0 < s_hi; s0 += VN_WAVE * OT_UNROLL) {
@@ -114,26 +113,8 @@ __global__ void __launch_bounds__(OT_SCAN_THREADS) k_ot_scan(const double *__res
                 if (!(pc >= 1e-12)) pc = 1e-12;          // (a NaN p too)
                 if (pc > 1.0) pc = 1.0;
                 const double cost = (-log(pc) + iou_weight * (-log(v + 1e-8))) + (in_box && in_ctr ? 0.0 : OT_OUTSIDE);
-                const double nv = -v;
-                if (cv < q || nv < worst_v) {
-                    int j = min(cv, q - 1);
-                    while (j > 0 && l_v[j - 1][lane] > nv) { l_v[j][lane] = l_v[j - 1][lane]; --j; }
-                    l_v[j][lane] = nv;
-                    cv = min(cv + 1, q);
-                    if (cv == q) worst_v = l_v[q - 1][lane];
-                }
-                if (cc < q || cost < worst_c) {
-                    int j = min(cc, q - 1);
-                    while (j > 0 && l_c[j - 1][lane] > cost) {
-                        l_c[j][lane] = l_c[j - 1][lane];
-                        l_n[j][lane] = l_n[j - 1][lane];
-                        --j;
-                    }
-                    l_c[j][lane] = cost;
-                    l_n[j][lane] = n;
-                    cc = min(cc + 1, q);
-                    if (cc == q) worst_c = l_c[q - 1][lane];
-                }
+                as_list_insert(l_v, lane, q, cv, worst_v, -v);
+                as_list_insert(l_c, lane, q, cc, worst_c, cost, l_n, n);
             }
         }
     }
@@ -144,17 +125,8 @@ __global__ void __launch_bounds__(OT_SCAN_THREADS) k_ot_scan(const double *__res
     if (lane == 0) part_cnt[pc0] = total;
     int hv = 0, hc = 0;
     for (int r = 0; r < q; ++r) {
-        const bool have_v = hv < cv, have_c = hc < cc;
-        double dv = have_v ? l_v[min(hv, OT_Q - 1)][lane] : INFINITY;
-        int iv = have_v ? lane : AS_NONE;          // (equal v: any lane; the lane index makes the pick unique)
-        as_wave_min(dv, iv);
-        if (have_v && iv == lane) ++hv;
-        const int hn = have_c ? l_n[min(hc, OT_Q - 1)][lane] : AS_NONE;
-        double dc = have_c ? l_c[min(hc, OT_Q - 1)][lane] : INFINITY;
-        int ic = hn;
-        as_wave_min(dc, ic);
-        if (have_c && hn == ic) ++hc;          // anchor indices are unique: exactly one lane advances
-        if (lane == 0) { part_v[po + r] = dv; part_c[po + r] = dc; part_n[po + r] = ic; }
+        const AsHead mv = as_merge_round(l_v, lane, lane, true, cv, hv), mc = as_merge_round(l_c, lane, lane, true, cc, hc, l_n);
+        if (lane == 0) { part_v[po + r] = mv.key; part_c[po + r] = mc.key; part_n[po + r] = mc.id; }
     }
 }
 
@@ -195,26 +167,14 @@ __global__ void __launch_bounds__(OT_PICK_THREADS) k_ot_pick(int N, const double
         if (lane < chunks)
             for (int r = 0; r < q; ++r) p_v[r][lane] = part_v[po + r];
         double sum = 0.0;
-        for (int r = 0; r < m; ++r) {
-            const bool have = lane < chunks && head < q;
-            double d = have ? p_v[min(head, OT_Q - 1)][lane] : INFINITY;
-            int i = have ? lane : AS_NONE;
-            as_wave_min(d, i);
-            if (have && i == lane) ++head;
-            sum += -d;
-        }
+        for (int r = 0; r < m; ++r) sum += -as_merge_round(p_v, lane, lane, lane < chunks, q, head).key;
         if (lane == 0) s_sum = sum;
     } else {
         if (lane < chunks)
             for (int r = 0; r < q; ++r) { p_c[r][lane] = part_c[po + r]; p_n[r][lane] = part_n[po + r]; }
         for (int r = 0; r < m; ++r) {
-            const bool have = lane < chunks && head < q;
-            const int hn = have ? p_n[min(head, OT_Q - 1)][lane] : AS_NONE;
-            double d = have ? p_c[min(head, OT_Q - 1)][lane] : INFINITY;
-            int n = hn;
-            as_wave_min(d, n);
-            if (have && hn == n) ++head;
-            if (lane == 0) { s_cost[r] = d; s_n[r] = n; }
+            const AsHead h = as_merge_round(p_c, lane, lane, lane < chunks, q, head, p_n);
+            if (lane == 0) { s_cost[r] = h.key; s_n[r] = h.id; }
         }
     }
     __syncthreads();
@@ -244,22 +204,27 @@ __global__ void __launch_bounds__(OT_PICK_THREADS) k_ot_pick(int N, const double
 inline bool ot_args_ok(int32_t B, int32_t N, int32_t max_gt, int32_t q) {
     return as_sizes_ok(B, N, max_gt) && q >= 1 && q <= VN_OTA_MAX_Q;
 }
-inline size_t ot_cand_n_bytes(int32_t B, int32_t max_gt) { return vn_align((size_t)B * max_gt * OT_Q * sizeof(int32_t)); }
-inline size_t ot_cand_bits_bytes(int32_t B, int32_t max_gt) { return vn_align((size_t)B * max_gt * OT_Q * sizeof(unsigned long long)); }
-inline size_t ot_part_f64_bytes(int32_t B, int32_t max_gt, int chunks) { return vn_align((size_t)B * max_gt * chunks * OT_Q * sizeof(double)); }
-inline size_t ot_part_n_bytes(int32_t B, int32_t max_gt, int chunks) { return vn_align((size_t)B * max_gt * chunks * OT_Q * sizeof(int32_t)); }
-inline size_t ot_part_cnt_bytes(int32_t B, int32_t max_gt, int chunks) { return vn_align((size_t)B * max_gt * chunks * sizeof(int32_t)); }
-
-}  // namespace
 
 // workspace: [cost words of every anchor | ~k of every anchor | selected n | selected bits | chunk lists' -v | chunk lists' cost |
 // chunk lists' n | chunk counts]; the first two are adjacent so that one memset clears both.  q does not enter: a list has
 // OT_Q slots whatever it is.
+struct OtaWs : AsBoxWs {
+    int chunks;
+    AsRegion<double> part_v, part_c;
+    AsRegion<int32_t> part_n, part_cnt;
+    OtaWs(int32_t B, int32_t N, int32_t max_gt) : AsBoxWs(B, N, max_gt, OT_Q), chunks(as_chunks(B, N, max_gt)) {
+        part_v = add<double>((size_t)B * max_gt * chunks * OT_Q);
+        part_c = add<double>((size_t)B * max_gt * chunks * OT_Q);
+        part_n = add<int32_t>((size_t)B * max_gt * chunks * OT_Q);
+        part_cnt = add<int32_t>((size_t)B * max_gt * chunks);
+    }
+};
+
+}  // namespace
+
 extern "C" size_t vn_rpn_targets_ota_workspace_bytes(int32_t B, int32_t n_anchors, int32_t max_gt, int32_t q) {
     if (!ot_args_ok(B, n_anchors, max_gt, q)) return 0;
-    const int chunks = as_chunks(B, n_anchors, max_gt);
-    return as_bits_bytes(B, n_anchors) + as_arg_bytes(B, n_anchors) + ot_cand_n_bytes(B, max_gt) + ot_cand_bits_bytes(B, max_gt) +
-           2 * ot_part_f64_bytes(B, max_gt, chunks) + ot_part_n_bytes(B, max_gt, chunks) + ot_part_cnt_bytes(B, max_gt, chunks);
+    return OtaWs(B, n_anchors, max_gt).bytes();
 }
 
 extern "C" int vn_rpn_targets_ota(const double *anchors, int32_t n_anchors, const double *gt, const int32_t *gt_count, int32_t B,
@@ -270,19 +235,14 @@ extern "C" int vn_rpn_targets_ota(const double *anchors, int32_t n_anchors, cons
                  ot_args_ok(B, n_anchors, max_gt, q) && anchor_h != 0.0);
     VN_CHECK_ARG(metric == VN_IOU_BEV || metric == VN_IOU_3D);
     VN_CHECK_ARG(radius >= 0.0 && std::isfinite(radius) && iou_weight >= 0.0 && std::isfinite(iou_weight));          // (NaN: false)
-    if (workspace_bytes < vn_rpn_targets_ota_workspace_bytes(B, n_anchors, max_gt, q)) return VN_EWORKSPACE;
+    const OtaWs ws(B, n_anchors, max_gt);
+    if (workspace_bytes < ws.bytes()) return VN_EWORKSPACE;
     hipStream_t st = vn_stream(stream);
-    const int chunks = as_chunks(B, n_anchors, max_gt);
-    char *p = static_cast<char *>(workspace);
-    unsigned long long *best_bits = reinterpret_cast<unsigned long long *>(p);   p += as_bits_bytes(B, n_anchors);
-    uint32_t *best_arg = reinterpret_cast<uint32_t *>(p);                        p += as_arg_bytes(B, n_anchors);
-    int32_t *cand_n = reinterpret_cast<int32_t *>(p);                            p += ot_cand_n_bytes(B, max_gt);
-    unsigned long long *cand_bits = reinterpret_cast<unsigned long long *>(p);   p += ot_cand_bits_bytes(B, max_gt);
-    double *part_v = reinterpret_cast<double *>(p);                              p += ot_part_f64_bytes(B, max_gt, chunks);
-    double *part_c = reinterpret_cast<double *>(p);                              p += ot_part_f64_bytes(B, max_gt, chunks);
-    int32_t *part_n = reinterpret_cast<int32_t *>(p);                            p += ot_part_n_bytes(B, max_gt, chunks);
-    int32_t *part_cnt = reinterpret_cast<int32_t *>(p);
-    VN_HIP(hipMemsetAsync(best_bits, 0, as_bits_bytes(B, n_anchors) + as_arg_bytes(B, n_anchors), st));
+    const int chunks = ws.chunks;
+    unsigned long long *best_bits = ws.best_bits(workspace), *cand_bits = ws.cand_bits(workspace);
+    int32_t *cand_n = ws.cand_n(workspace), *part_n = ws.part_n(workspace), *part_cnt = ws.part_cnt(workspace);
+    double *part_v = ws.part_v(workspace), *part_c = ws.part_c(workspace);
+    VN_HIP(hipMemsetAsync(best_bits, 0, ws.dense_bytes, st));
     const dim3 boxes((unsigned)max_gt, (unsigned)B);
     k_ot_scan<<<dim3((unsigned)(max_gt * chunks), (unsigned)B), OT_SCAN_THREADS, 0, st>>>(
         anchors, n_anchors, gt, gt_count, max_gt, probs, deltas, metric, q, radius, iou_weight, chunks, part_v, part_c, part_n, part_cnt);
@@ -290,15 +250,5 @@ extern "C" int vn_rpn_targets_ota(const double *anchors, int32_t n_anchors, cons
     k_ot_pick<<<boxes, OT_PICK_THREADS, 0, st>>>(n_anchors, gt, gt_count, max_gt, q, chunks, part_v, part_c, part_n, part_cnt, best_bits,
                                                  cand_n, cand_bits, stats);
     VN_LAUNCH_STATUS();
-    k_as_arg<OT_Q><<<boxes, OT_Q, 0, st>>>(n_anchors, max_gt, best_bits, best_arg, cand_n, cand_bits);
-    VN_LAUNCH_STATUS();
-    if (stats) {
-        k_as_count<OT_Q><<<boxes, OT_Q, 0, st>>>(n_anchors, max_gt, best_bits, best_arg, cand_n, cand_bits, stats, 5, 4);
-        VN_LAUNCH_STATUS();
-    }
-    const dim3 grid((unsigned)((n_anchors + AS_ENC_THREADS - 1) / AS_ENC_THREADS), (unsigned)B);
-    k_as_encode<AS_ENC_THREADS><<<grid, AS_ENC_THREADS, 0, st>>>(anchors, n_anchors, gt, max_gt, best_bits, best_arg, anchor_h, pos, neg,
-                                                                 targets, matched);
-    VN_LAUNCH_STATUS();
-    return VN_OK;
+    return as_launch_tail<OT_Q>(ws, workspace, st, anchors, n_anchors, gt, B, max_gt, anchor_h, pos, neg, targets, matched, stats, 5, 4);
 }

@@ -1084,15 +1084,9 @@ class RPN3D(nn.Module):
                  iou_head_metric="3d", iou_rectify=0.5, atss_top_k=9, atss_iou="rotated", ota_q=10, ota_radius=None,
                  ota_iou_weight=3.0, ota_metric="bev"):
         super().__init__()
-        from .targets import ASSIGN_KINDS, ATSS_IOU_KINDS, ATSS_MAX_TOPK, check_ota_params
-        if target_assign not in ASSIGN_KINDS:
-            raise ValueError(f"target_assign must be one of {sorted(ASSIGN_KINDS)}, not {target_assign!r}")
-        if isinstance(atss_top_k, bool) or not isinstance(atss_top_k, int) or not 1 <= atss_top_k <= ATSS_MAX_TOPK:
-            raise ValueError(f"atss_top_k must be an int in 1..{ATSS_MAX_TOPK}, not {atss_top_k!r}")
-        if atss_iou not in ATSS_IOU_KINDS:
-            raise ValueError(f"atss_iou must be one of {sorted(ATSS_IOU_KINDS)}, not {atss_iou!r}")
+        from .targets import check_assign_params
+        check_assign_params(target_assign, atss_top_k, atss_iou, ota_q, ota_radius, ota_iou_weight, ota_metric, name="target_assign")
         self.target_assign, self.atss_top_k, self.atss_iou = target_assign, atss_top_k, atss_iou
-        check_ota_params(ota_q, ota_radius, ota_iou_weight, ota_metric)
         self.ota_q, self.ota_radius, self.ota_iou_weight, self.ota_metric = ota_q, ota_radius, ota_iou_weight, ota_metric
         if anchor_area_threshold is not None:
             from .anchor_mask import check_threshold
@@ -1190,13 +1184,13 @@ class RPN3D(nn.Module):
     def _target_generator(self, device):
         from .targets import TargetGenerator
         gen = self.__dict__.get("_targets")
-        if (gen is None or gen.device != torch.device(device) or gen.assign != self.target_assign
-                or gen.keep_heading != bool(self.dir_head) or gen.atss_top_k != self.atss_top_k or gen.atss_iou != self.atss_iou
-                or gen.ota_params != (self.ota_q, self.ota_radius, self.ota_iou_weight, self.ota_metric)):
-            # (with the direction head the labels keep their heading: its target is the bin of the box's yaw)
-            gen = TargetGenerator(self.cls_name, device, assign=self.target_assign, keep_heading=bool(self.dir_head),
-                                  atss_top_k=self.atss_top_k, atss_iou=self.atss_iou, ota_q=self.ota_q, ota_radius=self.ota_radius,
-                                  ota_iou_weight=self.ota_iou_weight, ota_metric=self.ota_metric)
+        # TargetGenerator's arguments after the device and the anchors (None: the class's grid), as they are NOW — they may
+        # be set after construction —: its .key.  (With the direction head the labels keep their heading: its target is the
+        # bin of the box's yaw)
+        key = (self.cls_name, self.target_assign, None, None, bool(self.dir_head), self.atss_top_k, self.atss_iou, self.ota_q,
+               self.ota_radius, self.ota_iou_weight, self.ota_metric)
+        if gen is None or (gen.device, gen.key) != (torch.device(device), key):
+            gen = TargetGenerator(key[0], device, None, *key[1:])
             # the maps the network EMITS, not rpn_output_shape: for Pedestrian / Cyclist that attribute repeats the anchor
             # grid (100 x 120, as the reference has it) while block 1 does not stride and the maps are 200 x 240
             g, s = grid_config(self.cls_name), self.middle_rpn._block1_stride

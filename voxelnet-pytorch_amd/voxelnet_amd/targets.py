@@ -131,15 +131,24 @@ def gt_standup_boxes(gt):
 _LABEL_CACHE = os.environ.get("VN_LABEL_CACHE", "1") != "0"
 
 
-def check_ota_params(ota_q, ota_radius, ota_iou_weight, ota_metric):
-    """ValueError for a SimOTA parameter outside vn_rpn_targets_ota's ranges (ota_radius None: derived from the anchors)"""
-    if isinstance(ota_q, bool) or not isinstance(ota_q, (int, np.integer)) or not 1 <= ota_q <= OTA_MAX_Q:
-        raise ValueError(f"ota_q must be an int in 1..{OTA_MAX_Q}, not {ota_q!r}")
-    for name, v in (("ota_radius", ota_radius), ("ota_iou_weight", ota_iou_weight)):
-        if v is None and name == "ota_radius":
+def check_assign_params(assign, atss_top_k, atss_iou, ota_q, ota_radius, ota_iou_weight, ota_metric, name="assign"):
+    """ValueError for an assignment kind, or an ATSS / SimOTA parameter outside vn_rpn_targets_atss's / vn_rpn_targets_ota's
+    ranges (ota_radius None: derived from the anchors) — what TargetGenerator and RPN3D (name="target_assign") both check at
+    construction, whatever the kind"""
+    if assign not in ASSIGN_KINDS:
+        raise ValueError(f"{name} must be one of {sorted(ASSIGN_KINDS)}, not {assign!r}")
+    def int_in_range(what, v, hi):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= v <= hi:
+            raise ValueError(f"{what} must be an int in 1..{hi}, not {v!r}")
+    int_in_range("atss_top_k", atss_top_k, ATSS_MAX_TOPK)
+    if atss_iou not in ATSS_IOU_KINDS:
+        raise ValueError(f"atss_iou must be one of {sorted(ATSS_IOU_KINDS)}, not {atss_iou!r}")
+    int_in_range("ota_q", ota_q, OTA_MAX_Q)
+    for what, v in (("ota_radius", ota_radius), ("ota_iou_weight", ota_iou_weight)):
+        if v is None and what == "ota_radius":
             continue
         if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not (0 <= v < float("inf")):
-            raise ValueError(f"{name} must be a finite number >= 0, not {v!r}")
+            raise ValueError(f"{what} must be a finite number >= 0, not {v!r}")
     if ota_metric not in OTA_METRICS:
         raise ValueError(f"ota_metric must be one of {sorted(OTA_METRICS)}, not {ota_metric!r}")
 
@@ -194,17 +203,14 @@ class TargetGenerator:
     def __init__(self, cls_name="Car", device="cuda:0", anchors=None, assign="reference", pos_iou=None, neg_iou=None,
                  keep_heading=False, atss_top_k=9, atss_iou="rotated", ota_q=10, ota_radius=None, ota_iou_weight=3.0,
                  ota_metric="bev"):
-        if assign not in ASSIGN_KINDS:
-            raise ValueError(f"assign must be one of {sorted(ASSIGN_KINDS)}, not {assign!r}")
-        if isinstance(atss_top_k, bool) or not isinstance(atss_top_k, (int, np.integer)) or not 1 <= atss_top_k <= ATSS_MAX_TOPK:
-            raise ValueError(f"atss_top_k must be an int in 1..{ATSS_MAX_TOPK}, not {atss_top_k!r}")
-        if atss_iou not in ATSS_IOU_KINDS:
-            raise ValueError(f"atss_iou must be one of {sorted(ATSS_IOU_KINDS)}, not {atss_iou!r}")
+        check_assign_params(assign, atss_top_k, atss_iou, ota_q, ota_radius, ota_iou_weight, ota_metric)
+        # everything that defines this generator besides the device and the anchor grid, as given: RPN3D._target_generator
+        # builds the same tuple from its own attributes and makes a new generator when the two differ
+        self.key = (cls_name, assign, pos_iou, neg_iou, bool(keep_heading), atss_top_k, atss_iou, ota_q, ota_radius, ota_iou_weight,
+                    ota_metric)
         self.atss_top_k, self.atss_iou = int(atss_top_k), atss_iou
-        check_ota_params(ota_q, ota_radius, ota_iou_weight, ota_metric)
         self.ota_q, self.ota_iou_weight, self.ota_metric = int(ota_q), float(ota_iou_weight), ota_metric
         self.ota_radius = None if ota_radius is None else float(ota_radius)
-        self.ota_params = (ota_q, ota_radius, ota_iou_weight, ota_metric)          # as given: what RPN3D compares its own with
         self.cls_name = cls_name
         self.cfg = CLASS_CFG[cls_name]
         self.assign = assign
@@ -238,63 +244,48 @@ class TargetGenerator:
         N = self.n_anchors
         return (mask_probs(pos, anchor_mask, N, _lib.VN_DETECT_FLAT), mask_probs(neg, anchor_mask, N, _lib.VN_DETECT_FLAT)) + tuple(out[2:])
 
-    def _from_boxes_iou(self, gt_boxes, return_matched, return_stats=False, probs=None, deltas=None):
-        """assign = "standup" / "rotated" / "atss" / "simota": everything per box happens on the device too (no stand-up
-        rectangles here)"""
-        atss, ota = self.assign == "atss", self.assign == "simota"
-        name = "vn_rpn_targets_atss" if atss else "vn_rpn_targets_ota" if ota else "vn_rpn_targets_iou"
+    def _pack_boxes(self, gt_boxes, entry_name):
+        """the samples' (G_i, 7) boxes as one zero-padded host array -> gt (B, G, 7) float64, cnt (B,) int32, B, G"""
         B = len(gt_boxes)
         G = max([b.shape[0] for b in gt_boxes] + [1])
         if G > MAX_GT:
-            raise _lib.VoxelnetHipError(f"{G} ground-truth boxes in one sample; {name} takes at most {MAX_GT}")
+            raise _lib.VoxelnetHipError(f"{G} ground-truth boxes in one sample; {entry_name} takes at most {MAX_GT}")
         gt = np.zeros((B, G, 7), dtype=np.float64)
         cnt = np.zeros(B, dtype=np.int32)
         for b, boxes in enumerate(gt_boxes):
             cnt[b] = boxes.shape[0]
             gt[b, :boxes.shape[0]] = boxes
-        dev, N = self.device, self.n_anchors
-        gt_d, cnt_d = (torch.from_numpy(a).pin_memory().to(dev, non_blocking=True) for a in (gt, cnt))
-        pos = torch.empty((B, *self.shape, 2), dtype=torch.float32, device=dev)
-        neg = torch.empty((B, *self.shape, 2), dtype=torch.float32, device=dev)
-        tgt = torch.empty((B, *self.shape, 14), dtype=torch.float32, device=dev)
-        matched = torch.empty((B, *self.shape, 2), dtype=torch.int32, device=dev) if return_matched else None
-        if ota:
-            if probs.device != dev or deltas.device != dev:
-                raise ValueError(f"probs / deltas must live on the generator's device {dev}")
-            probs, deltas = probs.contiguous(), deltas.contiguous()
-            stats = torch.empty((B, G, 5), dtype=torch.float64, device=dev) if return_stats else None
-            nbytes = _lib.load().vn_rpn_targets_ota_workspace_bytes(B, N, G, self.ota_q)
-            if nbytes == 0:
-                raise _lib.VoxelnetHipError("vn_rpn_targets_ota_workspace_bytes: unsupported sizes")
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            with _lib.on_device(dev):
-                _lib.call("vn_rpn_targets_ota", self._anchors_dev.data_ptr(), N, gt_d.data_ptr(), cnt_d.data_ptr(), B, G,
-                          probs.data_ptr(), deltas.data_ptr(), OTA_METRICS[self.ota_metric], self.ota_q, self.ota_radius,
-                          self.ota_iou_weight, float(self.cfg["h"]), pos.data_ptr(), neg.data_ptr(), tgt.data_ptr(),
-                          matched.data_ptr() if return_matched else None, stats.data_ptr() if return_stats else None,
-                          ws.data_ptr(), nbytes, _lib.raw_stream())
-            return (pos, neg, tgt) + ((matched,) if return_matched else ()) + ((stats,) if return_stats else ())
-        if atss:
-            stats = torch.empty((B, G, 4), dtype=torch.float64, device=dev) if return_stats else None
-            nbytes = _lib.load().vn_rpn_targets_atss_workspace_bytes(B, N, G, self.atss_top_k)
-            if nbytes == 0:
-                raise _lib.VoxelnetHipError("vn_rpn_targets_atss_workspace_bytes: unsupported sizes")
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            with _lib.on_device(dev):
-                _lib.call("vn_rpn_targets_atss", self._anchors_dev.data_ptr(), N, gt_d.data_ptr(), cnt_d.data_ptr(), B, G,
-                          ATSS_IOU_KINDS[self.atss_iou], self.atss_top_k, float(self.cfg["h"]), pos.data_ptr(), neg.data_ptr(),
-                          tgt.data_ptr(), matched.data_ptr() if return_matched else None,
-                          stats.data_ptr() if return_stats else None, ws.data_ptr(), nbytes, _lib.raw_stream())
-            return (pos, neg, tgt) + ((matched,) if return_matched else ()) + ((stats,) if return_stats else ())
-        nbytes = _lib.load().vn_rpn_targets_iou_workspace_bytes(B, N, G)
+        return gt, cnt, B, G
+
+    def _standup_rects(self, gt_boxes, G):
+        """the reference assignment's host-made (B, G, 4) float32 stand-up rectangles, remembered by the boxes' bytes"""
+        g2 = np.zeros((len(gt_boxes), G, 4), dtype=np.float32)
+        for b, boxes in enumerate(gt_boxes):
+            n = boxes.shape[0]
+            if n:
+                key = boxes.tobytes()
+                su = self._standup.get(key) if _LABEL_CACHE else None
+                if su is None:
+                    if len(self._standup) >= 8192:
+                        self._standup.clear()
+                    su = self._standup[key] = gt_standup_boxes(boxes)
+                g2[b, :n] = su
+        return g2
+
+    def _outputs(self, B, return_matched):
+        """fresh pos, neg (B,h,w,2), targets (B,h,w,14) float32 and, if wanted, matched (B,h,w,2) int32 (else None)"""
+        new = lambda c, dtype: torch.empty((B, *self.shape, c), dtype=dtype, device=self.device)          # noqa: E731
+        return new(2, torch.float32), new(2, torch.float32), new(14, torch.float32), new(2, torch.int32) if return_matched else None
+
+    def _launch(self, name, ws_size_args, call_args):
+        """entry point `name` on the generator's device and the current stream, with a workspace of the size its
+        `name`_workspace_bytes(*ws_size_args) asks for appended to call_args"""
+        nbytes = getattr(_lib.load(), name + "_workspace_bytes")(*ws_size_args)
         if nbytes == 0:
-            raise _lib.VoxelnetHipError("vn_rpn_targets_iou_workspace_bytes: unsupported sizes")
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        with _lib.on_device(dev):
-            _lib.call("vn_rpn_targets_iou", self._anchors_dev.data_ptr(), N, gt_d.data_ptr(), cnt_d.data_ptr(), B, G,
-                      ASSIGN_KINDS[self.assign], self.pos_iou, self.neg_iou, float(self.cfg["h"]), pos.data_ptr(), neg.data_ptr(),
-                      tgt.data_ptr(), matched.data_ptr() if return_matched else None, ws.data_ptr(), nbytes, _lib.raw_stream())
-        return (pos, neg, tgt, matched) if return_matched else (pos, neg, tgt)
+            raise _lib.VoxelnetHipError(f"{name}_workspace_bytes: unsupported sizes")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        with _lib.on_device(self.device):
+            _lib.call(name, *call_args, ws.data_ptr(), nbytes, _lib.raw_stream())
 
     def from_boxes(self, gt_boxes, return_matched=False, anchor_mask=None, return_stats=False, probs=None, deltas=None):
         """gt_boxes: list of (G_i, 7) float64 lidar boxes per sample.  return_matched (every assign but "reference"): a fourth
@@ -309,48 +300,37 @@ class TargetGenerator:
         if return_stats and self.assign not in ("atss", "simota"):
             raise ValueError('return_stats needs assign="atss" or "simota": the other assignments have no per-box statistics')
         check_maps(self.assign, probs, deltas, len(gt_boxes), self.shape)
-        if self.assign != "reference":
-            return self._apply_mask(self._from_boxes_iou(gt_boxes, return_matched, return_stats, probs, deltas), anchor_mask)
-        if return_matched:
+        ref, atss, ota = (self.assign == a for a in ("reference", "atss", "simota"))
+        if ref and return_matched:
             raise ValueError('return_matched needs assign="standup", "rotated", "atss" or "simota": the reference assignment reports no index')
-        B = len(gt_boxes)
-        G = max([b.shape[0] for b in gt_boxes] + [1])
-        if G > MAX_GT:
-            raise _lib.VoxelnetHipError(f"{G} ground-truth boxes in one sample; vn_rpn_targets takes at most {MAX_GT}")
-        gt = np.zeros((B, G, 7), dtype=np.float64)
-        g2 = np.zeros((B, G, 4), dtype=np.float32)
-        cnt = np.zeros(B, dtype=np.int32)
-        for b, boxes in enumerate(gt_boxes):
-            n = boxes.shape[0]
-            cnt[b] = n
-            if n:
-                gt[b, :n] = boxes
-                key = boxes.tobytes()
-                su = self._standup.get(key) if _LABEL_CACHE else None
-                if su is None:
-                    if len(self._standup) >= 8192:
-                        self._standup.clear()
-                    su = self._standup[key] = gt_standup_boxes(boxes)
-                g2[b, :n] = su
-        dev = self.device
+        name = "vn_rpn_targets" + ("" if ref else "_atss" if atss else "_ota" if ota else "_iou")
+        gt, cnt, B, G = self._pack_boxes(gt_boxes, name)
+        # "reference" alone needs the boxes' stand-up rectangles from the host; for every other kind everything per box
+        # happens on the device too
+        host = (gt, self._standup_rects(gt_boxes, G), cnt) if ref else (gt, cnt)
+        dev, N = self.device, self.n_anchors
         # pinned staging + asynchronous copies on the current stream: a blocking copy from pageable memory would make the
         # host wait for everything queued before it — every step — and the train loop's enqueue could no longer run ahead
         # of the GPU (the caching host allocator keeps a pinned block until the copy that reads it has run)
-        gt_d, g2_d, cnt_d = (torch.from_numpy(a).pin_memory().to(dev, non_blocking=True) for a in (gt, g2, cnt))
-        N = self.n_anchors
-        pos = torch.empty((B, *self.shape, 2), dtype=torch.float32, device=dev)
-        neg = torch.empty((B, *self.shape, 2), dtype=torch.float32, device=dev)
-        tgt = torch.empty((B, *self.shape, 14), dtype=torch.float32, device=dev)
-        nbytes = _lib.load().vn_rpn_targets_workspace_bytes(B, N, G)
-        if nbytes == 0:
-            raise _lib.VoxelnetHipError("vn_rpn_targets_workspace_bytes: unsupported sizes")
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        with _lib.on_device(dev):
-            _lib.call("vn_rpn_targets", self._anchors_dev.data_ptr(), N, gt_d.data_ptr(), g2_d.data_ptr(), cnt_d.data_ptr(),
-                      B, G, self.pos_iou, self.neg_iou, float(self.cfg["h"]), pos.data_ptr(),
-                      neg.data_ptr(), tgt.data_ptr(), ws.data_ptr(), nbytes,
-                      _lib.raw_stream())
-        return self._apply_mask((pos, neg, tgt), anchor_mask)
+        boxes_d = [torch.from_numpy(a).pin_memory().to(dev, non_blocking=True) for a in host]
+        pos, neg, tgt, matched = self._outputs(B, return_matched)
+        stats = torch.empty((B, G, 5 if ota else 4), dtype=torch.float64, device=dev) if return_stats else None
+        if ref:
+            mid, tail = (self.pos_iou, self.neg_iou), ()
+        elif atss:
+            mid, tail = (ATSS_IOU_KINDS[self.atss_iou], self.atss_top_k), (matched, stats)
+        elif ota:
+            if probs.device != dev or deltas.device != dev:
+                raise ValueError(f"probs / deltas must live on the generator's device {dev}")
+            probs, deltas = probs.contiguous(), deltas.contiguous()
+            mid = (probs.data_ptr(), deltas.data_ptr(), OTA_METRICS[self.ota_metric], self.ota_q, self.ota_radius, self.ota_iou_weight)
+            tail = (matched, stats)
+        else:
+            mid, tail = (ASSIGN_KINDS[self.assign], self.pos_iou, self.neg_iou), (matched,)
+        self._launch(name, (B, N, G) + ((self.atss_top_k,) if atss else (self.ota_q,) if ota else ()),
+                     (self._anchors_dev.data_ptr(), N, *(t.data_ptr() for t in boxes_d), B, G, *mid, float(self.cfg["h"]),
+                      pos.data_ptr(), neg.data_ptr(), tgt.data_ptr(), *(None if t is None else t.data_ptr() for t in tail)))
+        return self._apply_mask((pos, neg, tgt) + tuple(t for t in (matched, stats) if t is not None), anchor_mask)
 
     def __call__(self, labels, feature_map_shape=None, coordinate="lidar", anchor_mask=None, probs=None, deltas=None):
         if feature_map_shape is not None and tuple(feature_map_shape) != tuple(self.shape):
