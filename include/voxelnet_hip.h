@@ -547,6 +547,62 @@ int vn_permute_points(const float *points, int64_t n, const int32_t *index, floa
 int vn_shuffle_points(const float *points, int64_t n, const uint32_t keys[6], float *out, vnStream stream);
 
 /* ------------------------------------------------------------------------
+ * Part-aware object augmentation (csrc/part_augment.hip; SE-SSD's "shape-aware", PA-AUG's
+ * "part-aware" augmentation): an object's box is cut into the six pyramids that join its centre to its faces; per object
+ * one pyramid may lose all its points (drop), one may be thinned (thin), one may be exchanged with the same pyramid of
+ * another object, rescaled to that object's box (swap).  The draw is O(boxes) host work (voxelnet_amd/part_augment.py);
+ * this is the per-point half, between the paste and the augmentation.  points / out: (n,4) fp32 [x,y,z,reflectance],
+ * 16-byte aligned; boxes = DEVICE table of 0 <= n_boxes <= VN_PART_MAX_BOXES entries, 16-byte aligned; gate = DEVICE
+ * int32 (n_boxes - gate_first values) or NULL.  Every decision widens float32 exactly to float64 and is evaluated as
+ * written, no contraction; the kernels hold no divide (the ratios ru, rv, rw are the host's).
+ *   live     entry o is DEAD when gate != NULL and o >= gate_first and gate[o - gate_first] < gate_min (with the visible
+ *            counts of vn_gt_paste_visible as the gate: the objects that paste rejected).  A dead entry holds no point, its
+ *            counts and stats are zero, and a swap whose partner is dead is void.
+ *   owner    a row with a NaN in x, y or z has no owner; otherwise the LOWEST live entry whose box holds the point
+ *            (vnGtBox's inside test, inclusive).  A row without an owner is a BIT copy of the input row (one 16-byte word).
+ *   pyramid  of an owned row, with dx, dy, u, v of the inside test:
+ *              hh = (z1 - z0) * 0.5;  w = pz - (z0 + hh)
+ *              m0 = |u| * (hw * hh);  m1 = |v| * (hl * hh);  m2 = |w| * (hl * hw)
+ *              axis = 0 when m0 >= m1 and m0 >= m2, else 1 when m1 >= m2, else 2
+ *              f = 2 * axis + (that axis's coordinate (u, v, w) < 0 ? 1 : 0)
+ *            (-0.0 and the box centre are face 0 of axis 0; diagonals go to the lower axis)
+ *   out_counts[o][f] = the rows owned by o in pyramid f, before any operation.
+ *   operations, the first that applies wins; all read the entry of the row's ORIGINAL owner o (masks are taken & 0x3F):
+ *     1. drop: bit f of drop_mask -> a NaN point (four 0x7FC00000 words); out_stats[o][0]++
+ *     2. thin: bit f of sparse_mask and out_counts[o][f] >= sparse_min and (fmix32((uint32)i ^ sparse_key) >> 8) >=
+ *              sparse_thresh, i = the row's index in this call, fmix32 as above -> a NaN point; out_stats[o][1]++
+ *     3. swap: bit f of swap_mask and p = swap_with in [0, n_boxes) and p != o and p live:
+ *                u' = u * ru;  v' = v * rv;  w' = w * rw;   hh_p = (p.z1 - p.z0) * 0.5
+ *                X = p.x + (u' * p.c - v' * p.s);  Y = p.y + (u' * p.s + v' * p.c);  Z = (p.z0 + hh_p) + w'
+ *              each rounded once to fp32, reflectance bit-copied; out_stats[o][2]++.  A moved row takes no rule from p.
+ *     otherwise the row is a bit copy.
+ * No table content makes a kernel read or write outside its buffers: a swap_with outside [0, n_boxes) means no partner.
+ * out may BE points (in place); otherwise it must not overlap it (VN_EINVAL).  n == 0 is a no-op apart from the zeroed
+ * counts and stats; n_boxes == 0 is a copy (nothing at all when in place) and out_counts / out_stats may then be NULL.
+ * VN_EINVAL: n outside [0, 2^31), n_boxes outside [0, VN_PART_MAX_BOXES], gate_first outside [0, n_boxes], a null pointer
+ * with work to do; VN_EWORKSPACE: a workspace below vn_part_augment_workspace_bytes(n, n_boxes) (0 for bad arguments);
+ * VN_EUNSUPPORTED: points, out, boxes or workspace off their 16-byte alignment, out_counts, out_stats or gate off their
+ * 4-byte alignment — all decided before the first launch.  Three launches: zero of the counts and stats; the count
+ * pass (owner + pyramid per row into the workspace as a uint16 code, a per-workgroup LDS histogram flushed with one
+ * global integer add per non-empty bin); the apply pass.  No workgroup waits on another one and only integers are
+ * added, so two runs give the same bits.  Asynchronous.
+ * ---------------------------------------------------------------------- */
+#define VN_PART_MAX_BOXES 128
+typedef struct vnPartBox {
+    double x, y, z0, z1, hl, hw, c, s;   /* vnGtBox's fields and its inside test */
+    double ru, rv, rw;                   /* partner extent / own extent along length, width, height */
+    int32_t drop_mask, sparse_mask, swap_mask;   /* bit f = pyramid f; only bits 0..5 are read */
+    int32_t swap_with;                   /* partner entry, -1: none */
+    uint32_t sparse_key, sparse_thresh;  /* thresh in 0 .. 2^24: a row of a thinned pyramid stays when its 24-bit hash is below it */
+    int32_t sparse_min, reserved;        /* a pyramid with fewer rows is not thinned */
+    double pad;
+} vnPartBox;                             /* 128 bytes */
+size_t vn_part_augment_workspace_bytes(int64_t n, int32_t n_boxes);
+int vn_part_augment(const float *points, int64_t n, const vnPartBox *boxes, int32_t n_boxes, const int32_t *gate,
+                    int32_t gate_first, int32_t gate_min, float *out, int32_t *out_counts, int32_t *out_stats,
+                    void *workspace, size_t workspace_bytes, vnStream stream);
+
+/* ------------------------------------------------------------------------
  * Native step executor — MiddleConvNet.forward (model.py:257-281) and its backward as ONE call
  * each (csrc/runtime.hip): layer table, launch geometry and workspace arena live in C++, so the
  * ~450 launches of a step cost microseconds of host time instead of a Python round trip each.

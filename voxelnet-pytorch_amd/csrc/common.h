@@ -168,6 +168,17 @@ __device__ __forceinline__ bool vn_gt_inside(double px, double py, double pz, co
     return fabs(u) <= q.hl && fabs(v) <= q.hw && pz >= q.z0 && pz <= q.z1;
 }
 
+// The 32-bit finalizer of MurmurHash3, as include/voxelnet_hip.h writes it: the round function of shuffle.hip's keyed
+// bijection and the per-row hash of part_augment.hip's thinning.  Exact uint32 arithmetic (wrapping multiplies).
+__device__ __forceinline__ uint32_t vn_fmix32(uint32_t x) {
+    x ^= x >> 16;
+    x *= 0x85EBCA6Bu;
+    x ^= x >> 13;
+    x *= 0xC2B2AE35u;
+    x ^= x >> 16;
+    return x;
+}
+
 // Buffer descriptor from values the compiler can PROVE wave-uniform (cdna_hip_programming.md T20): without
 // the readfirstlane of the pointer halves and the size, hipcc wraps every buffer_load ... lds that uses the
 // descriptor in a waterfall loop (v_readfirstlane x4 + s_and_saveexec + loop), ~15 instructions and a

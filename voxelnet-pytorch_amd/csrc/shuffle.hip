@@ -25,20 +25,11 @@ struct ShuffleKeys {
     uint32_t k[6];
 };
 
-__device__ __forceinline__ uint32_t fmix32(uint32_t x) {
-    x ^= x >> 16;
-    x *= 0x85EBCA6Bu;
-    x ^= x >> 13;
-    x *= 0xC2B2AE35u;
-    x ^= x >> 16;
-    return x;
-}
-
 __device__ __forceinline__ uint32_t feistel(uint32_t x, const ShuffleKeys &keys, int h, uint32_t mask) {
     uint32_t L = x >> h, R = x & mask;
 #pragma unroll
     for (int r = 0; r < 6; ++r) {
-        const uint32_t t = L ^ (fmix32(R ^ keys.k[r]) & mask);
+        const uint32_t t = L ^ (vn_fmix32(R ^ keys.k[r]) & mask);          // (common.h)
         L = R;
         R = t;
     }

@@ -161,7 +161,15 @@ class VnVisGrid(ctypes.Structure):   # vnVisGrid (vn_gt_paste_visible): the rang
                 ("margin", ctypes.c_double), ("min_visible", c_i32), ("reserved", c_i32)]
 
 
+class VnPartBox(ctypes.Structure):   # vnPartBox (vn_part_augment): one entry of the device table, 128 bytes
+    _fields_ = [(n, ctypes.c_double) for n in ("x", "y", "z0", "z1", "hl", "hw", "c", "s", "ru", "rv", "rw")] + \
+               [(n, c_i32) for n in ("drop_mask", "sparse_mask", "swap_mask", "swap_with")] + \
+               [("sparse_key", ctypes.c_uint32), ("sparse_thresh", ctypes.c_uint32), ("sparse_min", c_i32), ("reserved", c_i32),
+                ("pad", ctypes.c_double)]
+
+
 VN_GT_MAX_BOXES = 128
+VN_PART_MAX_BOXES = 128
 VN_EVAL_BEV, VN_EVAL_3D = 0, 1       # vn_box_iou_rotated's `metric`; axis 1 of vn_eval_match's outputs
 VN_EVAL_MAX_TOPK, VN_EVAL_MAX_DIFF = 32, 8
 VN_EVAL_BBOX, VN_EVAL_MAX_DC, VN_EVAL_IMAGE_ROW = 2, 64, 12       # vn_eval_match_image's third metric; vn_boxes_to_image's row
@@ -205,6 +213,8 @@ SIGNATURES = {
                                     c_vp, c_sz, c_vp]),
     "vn_permute_points": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp]),
     "vn_shuffle_points": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "vn_part_augment_workspace_bytes": (c_sz, [c_i64, c_i32]),
+    "vn_part_augment": (c_i32, [c_vp, c_i64, c_vp, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "vn_comm_rccl_version": (c_i32, []),
     "vn_comm_unique_id": (c_i32, [c_vp]),
     "vn_comm_create": (c_i32, [_P(c_vp), c_vp, c_i32, c_i32]),

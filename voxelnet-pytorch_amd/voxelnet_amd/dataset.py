@@ -26,6 +26,12 @@ hand the model labels + the pasted objects' lines.  A sampler with `visibility=g
 `vn_gt_paste_visible` instead: objects hidden behind scene points are rejected on the device,
 and `concat` drops their label lines once the sample's visible counts have arrived in pinned host memory.
 
+Part-aware object augmentation (part_augment.py; SE-SSD / PA-AUG, no counterpart in the reference) is the stage between
+the two: copy -> [field-of-view crop] -> paste -> parts -> augment -> voxelize.  `DeviceCollate(..., part_augment=
+part_augment.PartRecipe())` draws per sample after the sampler and before the augmentation, on the labels including the
+pasted lines, and drops, thins and swaps pyramids of the objects' points in place (csrc/part_augment.hip); the label lines
+stay as they are.
+
 The sample's shuffle (utils.py:35) is by default the reference's: `np.random.shuffle` of the host cloud, in the thread that
 also enqueues the train step.  `shuffle_points="index"` / `"device"` move the per-point half to the device (shuffle.py,
 csrc/shuffle.hip), as the first stage behind the copy: copy -> shuffle -> [field-of-view crop] -> paste -> augment ->
@@ -97,7 +103,7 @@ class DeviceCollate:
     GPU (not in a DataLoader worker)."""
 
     def __init__(self, device="cuda:0", target="Car", shuffle_points=True, fov_calib_dir=None, image_shape=(375, 1242),
-                 augment=False, gt_sampler=None):
+                 augment=False, gt_sampler=None, part_augment=None):
         """shuffle_points: the sample's shuffle in front of the voxelizer (utils.py:35).
           True / "host": np.random.shuffle of the sample's cloud on the host, in place like the reference; False: none.
           "index":  shuffle.draw_index at that place — the sample's first draw, the same np.random draws — the cloud is
@@ -126,7 +132,13 @@ class DeviceCollate:
         go) and the batch's `label` element holds labels + their lines (moved by the augmentation when it is on).  None:
         nothing is drawn, nothing is launched.  A sampler with a `visibility` pastes with vn_gt_paste_visible: the
         augmentation's draw still runs on labels + the lines of EVERY candidate (a rejected object still takes part in
-        its collision test), and `concat` removes the rejected objects' lines from the sample's (moved) labels."""
+        its collision test), and `concat` removes the rejected objects' lines from the sample's (moved) labels.
+        part_augment: a part_augment.PartRecipe — per sample, after the sampler's draw and before the augmentation's,
+        `part_augment.draw_parts` runs on the labels including the pasted lines; `vn_part_augment` then works on the cloud in
+        place, behind the paste and in front of the augmentation (pyramids of objects dropped, thinned, swapped between
+        objects of a class).  The label lines are unchanged.  With a visibility sampler
+        the paste's device-side visible counts gate the pasted objects' entries: a rejected object owns no point and is
+        nobody's partner.  None: nothing is drawn, nothing is launched; anything else raises ValueError."""
         # (strings are truthy: an unknown one must not fall through to the host shuffle)
         if isinstance(shuffle_points, str) and shuffle_points in ("host", "index", "device"):
             self._shuffle_mode = shuffle_points
@@ -149,6 +161,11 @@ class DeviceCollate:
                 raise ValueError(f"augment={augment!r}: expected True, False or an augment.ComposeRecipe")
             self.augment, self.recipe = False, augment
         self.gt_sampler = gt_sampler
+        if part_augment is not None:
+            from .part_augment import PartRecipe
+            if not isinstance(part_augment, PartRecipe):
+                raise ValueError(f"part_augment={part_augment!r}: expected None or a part_augment.PartRecipe")
+        self.part_augment = part_augment
         self.stream = pipeline_stream(self.device)      # (shared with the target generator: see voxelize.pipeline_stream)
 
     def launch(self, parts):
@@ -160,6 +177,8 @@ class DeviceCollate:
         if self.gt_sampler is not None:
             from . import gtsample as G
             visibility = getattr(self.gt_sampler, "visibility", None)
+        if self.part_augment is not None:
+            from . import part_augment as PA
         if self.augment or self.recipe is not None or self.gt_sampler is not None:
             parts = list(parts)
         mode = self._shuffle_mode
@@ -181,6 +200,8 @@ class DeviceCollate:
                         p = parts[b] = (p[0], p[1], p[2], list(p[3]) + pasted.lines, *p[4:])
                     else:
                         pasted = None                                          # nothing accepted: no launch, the cloud passes
+                if self.part_augment is not None:
+                    part_params = PA.draw_parts(p[3], self.part_augment)       # host: O(boxes); the lines stay as they are
                 if self.augment:
                     params = A.draw_augmentation(p[3])                         # dataset.py:122-219, host: O(boxes)
                     parts[b] = (p[0], p[1], p[2], A.augment_labels(p[3], params), *p[4:])
@@ -210,13 +231,22 @@ class DeviceCollate:
                 if pasted is not None and visibility is not None:
                     # the same place; the visible counts follow in pinned memory (concat reads them): the sample's last
                     # len(pasted.lines) label lines are pasted ones
-                    pts, keep, visible = G.enqueue_gt_paste_visible(pts, pasted, visibility)
+                    pts, keep, visible, pasted_result = G.enqueue_gt_paste_visible(pts, pasted, visibility, return_result=True)
                     host = (host, keep)
                     rejects = (visible, len(pasted.lines), visibility.min_visible)
                 elif pasted is not None:
                     # behind the copy / the crop on this stream; the NaN rows of the padded crop go, NaN rows come out, so
                     # the count is not read back either; `keep` = the staged table and object points
                     pts, keep = G.enqueue_gt_paste(pts, pasted)
+                    host = (host, keep)
+                if self.part_augment is not None:
+                    # in place, behind the paste on this stream; the entries of the pasted lines (the table's last ones) are
+                    # gated by the visible counts where they are, on the device: nothing is read back
+                    gate = {}
+                    if rejects is not None:
+                        gate = dict(gate=pasted_result.visible_device, gate_first=len(part_params.table) - len(pasted.lines),
+                                    gate_min=visibility.min_visible)
+                    pts, keep, _ = PA.enqueue_part_points(pts, part_params, out=pts, **gate)
                     host = (host, keep)
                 if self.augment:
                     # in place, behind the copy / the crop on this stream; `keep` = the staged box table, referenced
@@ -275,9 +305,10 @@ class DeviceBatcher:
     voxelized on the pipeline's own stream."""
 
     def __init__(self, loader, device="cuda:0", target="Car", shuffle_points=True, fov_calib_dir=None, image_shape=(375, 1242),
-                 augment=False, gt_sampler=None):
+                 augment=False, gt_sampler=None, part_augment=None):
         self.loader = loader
-        self.collate = DeviceCollate(device, target, shuffle_points, fov_calib_dir, image_shape, augment, gt_sampler=gt_sampler)
+        self.collate = DeviceCollate(device, target, shuffle_points, fov_calib_dir, image_shape, augment, gt_sampler=gt_sampler,
+                                     part_augment=part_augment)
 
     def __len__(self):
         return len(self.loader)

@@ -339,6 +339,11 @@ class GTVisibleResult:
         return self._visible.cpu().numpy()
 
     @property
+    def visible_device(self):
+        """the (G,) int32 device tensor itself: no synchronisation"""
+        return self._visible
+
+    @property
     def kept(self):
         return self._kept.cpu().numpy()
 
@@ -387,16 +392,19 @@ def _paste_visible(points, params, visibility, cap):
     return out[:max(cap, 0)], count, GTVisibleResult(visible, kept, stats, visibility.min_visible), keep + (ints, ws)
 
 
-def enqueue_gt_paste_visible(points, params, visibility, cap=None):
+def enqueue_gt_paste_visible(points, params, visibility, cap=None, return_result=False):
     """the occlusion-consistent paste without host synchronisation -> (out: the capacity-sized buffer of enqueue_gt_paste,
     tensors the queued work reads or writes: keep them referenced until the stream has run it, visible: a PINNED host
     (G,) int32 tensor — it is also among the kept references — into which a device->host copy of the visible counts is
     queued right behind the call: valid once the stream has run that copy; object o is accepted when visible[o] >=
-    visibility.min_visible)."""
+    visibility.min_visible).  return_result=True: a fourth element, the call's GTVisibleResult — its `visible_device` is
+    what a later stage on the same stream gates on (part_augment.enqueue_part_points)."""
     out, _, res, keep = _paste_visible(points, params, visibility, cap)
     with _lib.on_device(points.device):
         visible = torch.empty(res._visible.shape[0], dtype=torch.int32).pin_memory()
         visible.copy_(res._visible, non_blocking=True)
+    if return_result:
+        return out, keep + (visible,), visible, res
     return out, keep + (visible,), visible
 
 
